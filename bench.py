@@ -8,16 +8,24 @@ records) followed by srpc_gpu_unpack (wire -> 4 columns), both through the
 C ABI of srpc_amd/libsrpc_gpu.so.  Weak scaling: every rank owns 16M records
 (configs[2] of BASELINE.json per GPU; at 4 GPUs that is configs[3]'s 64M).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  `value` = wire GiB/s through a full
 pack+unpack round trip summed over all ranks (records * 16 B / 2^30 / step
-time, the max over ranks).  The roofline object prices the dominant kernel
-against HBM3E (8.0 TB/s spec) with algorithmic bytes (32 B per record per
-kernel); the cpu_baseline object times the reference packer (compiled from
-/root/reference into oracle/_ref, or the C restatement if that is absent) on
-this host.
+time, the max over ranks); `ms_per_step` = that step time.
+
+A plain run does what the headline needs and no more: inputs, W warm-up
+steps, K timed steps, the line.  `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs below).  `--full` adds every other
+measurement and check to the line: the digest of the packed bytes against the
+reference's, the kernel clock and its roofline object (the dominant kernel
+priced against HBM3E, 8.0 TB/s spec, with algorithmic bytes: 32 B per record
+per kernel), the cold-cache kernel clock, the strong-scaling line, the
+PCIe-inclusive legs, the RCCL gather at N > 1, and the cpu_baseline object
+(the reference packer where oracle/_ref holds it, else its C restatement,
+timed on this host).  --no-verify, --no-cold, --no-pcie, --cpu-seconds 0 and
+--strong-records 0 each leave one of those out of a --full run.
 """
 from __future__ import annotations
 
@@ -45,20 +53,29 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--records", type=int, default=1 << 24, help="records per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="every further measurement and check beside the headline: digest against the reference, "
+                         "kernel clock + roofline, cold-cache clock, strong scaling, PCIe legs, RCCL gather, "
+                         "CPU baseline (the options below each leave one out)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
-                    help="target CPU-baseline work (rank 0, N=1 only); 0 disables")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-cache kernel clock")
+                    help="--full: target CPU-baseline work (rank 0, N=1 only); 0 disables")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the round trip + digest check")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive legs")
+    ap.add_argument("--no-cold", action="store_true", help="--full: skip the cold-cache kernel clock")
     ap.add_argument("--path", choices=["auto", "dword", "tile"], default="auto")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--tune", default=None,
                     help="DWORD-path variant rpl,iter,nt (default: the library's tuned default)")
     ap.add_argument("--strong-records", type=int, default=1 << 26,
-                    help="strong-scaling line beside the weak one: this many records in all, "
+                    help="--full: strong-scaling line beside the weak one: this many records in all, "
                          "split over the ranks (configs[3]: 64M); 0 disables")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 XGMI_LINK_GBPS = 153.0  # per xGMI link and direction (the task's MI355X figure: 7 links x ~153 GB/s)
@@ -508,6 +525,54 @@ def cpu_baseline(n: int, target_s: float) -> dict | None:
     return out
 
 
+DUMP_EDGE = 1 << 12     # records kept whole from each end of the batch
+DUMP_SAMPLE = 1 << 18   # records drawn from the rest
+DUMP_SEED = 0xD0C5
+
+
+def dump_records(n: int):
+    """The records --dump-outputs keeps, a function of n alone: the first and
+    last DUMP_EDGE records (where a tail path would go wrong) and DUMP_SAMPLE
+    drawn from the rest by a fixed seed; sorted, no repeats.  Every record if
+    the batch has no more than that."""
+    import numpy as np
+
+    if n <= 2 * DUMP_EDGE + DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    mid = np.random.default_rng(DUMP_SEED).integers(DUMP_EDGE, n - DUMP_EDGE, size=DUMP_SAMPLE, dtype=np.int64)
+    return np.unique(np.concatenate([np.arange(DUMP_EDGE, dtype=np.int64), mid,
+                                     np.arange(n - DUMP_EDGE, n, dtype=np.int64)]))
+
+
+def dump_outputs(dirname: str, wire, back, n: int, dev, rank: int, world: int) -> dict:
+    """What a caller of the timed step receives, as left by the last timed
+    step: the wire bytes srpc_gpu_pack wrote and the four columns
+    srpc_gpu_unpack wrote, at the records dump_records(n) names (the whole
+    256 MiB + 256 MiB would not fit the 64 MB a dump may take).
+      records.npy  float64 [S]      the record numbers (exact: < 2^53)
+      wire.npy     float32 [S, 16]  the wire bytes of those records (0..255: exact)
+      col<f>.npy   float64 [S]      field f of those records (int32: exact)
+    With N > 1 every rank writes its own shard's files, `_rank<r>` appended to
+    the names.  The inputs are the splitmix stream of a fixed seed, so the same
+    arguments give the same files from every build that computes the same."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    rec = dump_records(n)
+    idx = torch.from_numpy(rec).to(dev)
+    arrays = {"records": rec.astype(np.float64),
+              "wire": wire.view(n, REC_BYTES).index_select(0, idx).cpu().numpy().astype(np.float32)}
+    for f, col in enumerate(back):
+        arrays[f"col{f}"] = col.index_select(0, idx).cpu().numpy().astype(np.float64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), a)
+        total += a.nbytes
+    return {"dir": dirname, "files": [k + sfx + ".npy" for k in arrays], "records": int(rec.size), "bytes": total}
+
+
 def main() -> None:
     args = parse()
     import torch
@@ -541,8 +606,9 @@ def main() -> None:
 
     # the exchange step: the library's own RCCL gather (srpc_gather_wire) on a
     # communicator it owns; the id travels over torch's process group
+    extras = args.full  # everything beside the headline
     comm, comm_note = None, None
-    if world > 1 and args.dist_backend == "nccl":
+    if extras and world > 1 and args.dist_backend == "nccl":
         try:
             comm = NativeComm.from_process_group(local)
         except Exception as e:  # keep the measurement; say which gather ran
@@ -569,7 +635,7 @@ def main() -> None:
 
     # correctness of the exact bytes being timed: round trip + reference digest
     verify = {}
-    if not args.no_verify:
+    if extras and not args.no_verify:
         step()
         torch.cuda.synchronize(dev)
         ok = all(torch.equal(a, b) for a, b in zip(cols, back))
@@ -592,7 +658,7 @@ def main() -> None:
     K = args.steps
     step0 = torch.cuda.Event(enable_timing=True)
     step1 = torch.cuda.Event(enable_timing=True)
-    kev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(K)]
+    kev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(K if extras else 0)]
     for e in [step0, step1] + [e for row in kev for e in row]:
         e.record(stream)  # torch creates the HIP event on its first record
 
@@ -614,26 +680,33 @@ def main() -> None:
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    gpu_ms = step0.elapsed_time(step1)
 
-    # Kernel clock (roofline): K further steps with every pack / unpack call
-    # armed by srpc_time_next_call, so its kernel stamps its own dispatch
+    # wire and back still hold what the last timed step wrote
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, wire, back, n, dev, rank, world)
+
+    # Kernel clock (roofline, --full): K further steps with every pack / unpack
+    # call armed by srpc_time_next_call, so its kernel stamps its own dispatch
     # begin/end into a per-call event pair -- the interval rocprofv3
     # --kernel-trace reports.  Arming costs ~5 us of GPU time per call
     # (profiles/r01_step_overhead.json), so it stays out of the step clock.
-    for i in range(K):
-        srpc_amd.time_next_call(kev[i][0], kev[i][1])
-        p.pack(cols, n, wire, stream=stream)
-        srpc_amd.time_next_call(kev[i][2], kev[i][3])
-        p.unpack(wire, n * REC_BYTES, n, back, stream=stream)
-    torch.cuda.synchronize(dev)
-
-    pack_ms = [kev[i][0].elapsed_time(kev[i][1]) for i in range(K)]
-    unpack_ms = [kev[i][2].elapsed_time(kev[i][3]) for i in range(K)]
+    pack_ms, unpack_ms = [0.0], [0.0]
+    if extras:
+        for i in range(K):
+            srpc_amd.time_next_call(kev[i][0], kev[i][1])
+            p.pack(cols, n, wire, stream=stream)
+            srpc_amd.time_next_call(kev[i][2], kev[i][3])
+            p.unpack(wire, n * REC_BYTES, n, back, stream=stream)
+        torch.cuda.synchronize(dev)
+        pack_ms = [kev[i][0].elapsed_time(kev[i][1]) for i in range(K)]
+        unpack_ms = [kev[i][2].elapsed_time(kev[i][3]) for i in range(K)]
 
     # Cold-cache kernel clock (SURVEY.md §8d's second regime): 512 MiB written
     # before every armed call evicts the 256 MiB Infinity Cache (and L2).
     cold = None
-    if not args.no_cold:
+    if extras and not args.no_cold:
         flush = torch.empty(512 << 20, dtype=torch.uint8, device=dev)
         kc = min(K, 10)
         for i in range(kc):
@@ -649,29 +722,31 @@ def main() -> None:
         cold = {"pack": round(cp, 4), "unpack": round(cu, 4), "reps": kc, "stat": "median",
                 "flush": "512 MiB written before each call (Infinity Cache is 256 MiB)"}
         del flush
-    gpu_ms = step0.elapsed_time(step1)
     t_rank = max(elapsed, gpu_ms / 1e3)
-    t = torch.tensor([t_rank, sum(pack_ms) / K, sum(unpack_ms) / K], dtype=torch.float64,
+    t = torch.tensor([t_rank, sum(pack_ms) / len(pack_ms), sum(unpack_ms) / len(unpack_ms)], dtype=torch.float64,
                      device=dev if args.dist_backend == "nccl" else "cpu")
-    # per-rank view before the max: each rank's own kernel clock and what its
-    # RCCL communicator says it is (srpc_comm_rank), so a multi-GPU line shows
-    # that RCCL saw every rank
-    mine = {"rank": rank, "device": local, "pack_ms": round(sum(pack_ms) / K, 4),
-            "unpack_ms": round(sum(unpack_ms) / K, 4),
-            "frac": round(ALG_BYTES_PER_REC * n / (max(sum(pack_ms), sum(unpack_ms)) / K / 1e3) / 1e9
-                          / HBM_PEAK_GBPS, 4),
-            "rccl": comm.info() if comm is not None else None}
-    per_rank = [mine]
+    # per-rank view before the max (--full): each rank's own kernel clock and
+    # what its RCCL communicator says it is (srpc_comm_rank), so a multi-GPU
+    # line shows that RCCL saw every rank
+    per_rank = None
+    if extras:
+        mine = {"rank": rank, "device": local, "pack_ms": round(sum(pack_ms) / K, 4),
+                "unpack_ms": round(sum(unpack_ms) / K, 4),
+                "frac": round(ALG_BYTES_PER_REC * n / (max(sum(pack_ms), sum(unpack_ms)) / K / 1e3) / 1e9
+                              / HBM_PEAK_GBPS, 4),
+                "rccl": comm.info() if comm is not None else None}
+        per_rank = [mine]
+        if world > 1:
+            per_rank = [None] * world
+            dist.all_gather_object(per_rank, mine)
     if world > 1:
-        per_rank = [None] * world
-        dist.all_gather_object(per_rank, mine)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     t_max, pack_avg, unpack_avg = t.tolist()
     ms_step = t_max * 1e3 / K
 
     # gather of the packed shards to rank 0 over RCCL (reported separately)
     gather = None
-    if world > 1:
+    if extras and world > 1:
         for _ in range(2):
             gather_packed(wire, REC_BYTES, n * world, comm=comm)
         torch.cuda.synchronize(dev)
@@ -702,7 +777,7 @@ def main() -> None:
     # Strong scaling (configs[3]): args.strong_records in all, split over the
     # ranks with the library's shard rule; same step, same clock, max over ranks
     strong = None
-    if args.strong_records > 0:
+    if extras and args.strong_records > 0:
         NS = args.strong_records
         lo, hi = shard_range(NS, rank, world)
         m = hi - lo
@@ -751,20 +826,12 @@ def main() -> None:
 
     # PCIe-inclusive legs (host buffers at both ends), rank 0 only
     pcie = None
-    if rank == 0 and world == 1 and not args.no_pcie:
+    if extras and rank == 0 and world == 1 and not args.no_pcie:
         pcie = pcie_inclusive(p, n, dev)
 
     if rank == 0:
         total_recs = n * world
         value = total_recs * K * REC_BYTES / 2**30 / t_max  # wire GiB/s, all ranks
-        dom_name, dom_ms = ("pack", pack_avg) if pack_avg >= unpack_avg else ("unpack", unpack_avg)
-        achieved = ALG_BYTES_PER_REC * n / (dom_ms / 1e3) / 1e9
-        # the same kernel from a cold Infinity Cache (512 MiB written before each
-        # call): the warm figure above is partly served on-die, cold is not
-        frac_cold = None
-        if cold:
-            frac_cold = round(ALG_BYTES_PER_REC * n / (cold[dom_name] / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
-        prof = committed_profiles(dom_name, n)
         line = {
             "metric": "packer GiB/s + Mrecords/s device-resident, 1/2/4/8 MI355X",
             "value": round(value, 3),
@@ -785,36 +852,50 @@ def main() -> None:
                        "tune": args.tune or "default"},
             "mrecords_per_s": round(total_recs * K / t_max / 1e6, 1),
             "hbm_algorithmic_GBps": round(2 * ALG_BYTES_PER_REC * total_recs * K / t_max / 1e9, 1),
-            "kernels_ms": {"pack": round(pack_avg, 4), "unpack": round(unpack_avg, 4),
-                           "clock": "dispatch begin/end stamped by hipExtLaunchKernel (srpc_time_next_call), K armed steps after the step clock"},
-            "kernels_ms_cold": cold,
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "frac_of_measured_copy": round(achieved / HBM_MEASURED_COPY_GBPS, 4),
-                         "frac_cold": frac_cold,
-                         "regime": "frac: warm steps (back to back; the 256 MiB Infinity Cache holds part "
-                                   "of the previous call's output); frac_cold: the same kernel after a "
-                                   "512 MiB flush",
-                         "alg_bytes_per_launch": ALG_BYTES_PER_REC * n,
-                         "traffic": prof["traffic"],
-                         "traffic_over_alg": (round(prof["traffic"] / (ALG_BYTES_PER_REC * n), 4)
-                                              if prof["traffic"] else None),
-                         "committed_rocprof_avg_us": prof["committed_rocprof_avg_us"],
-                         "kernel_stats_file": prof["kernel_stats_file"],
-                         "pmc_file": prof["pmc_file"]},
-            "verify": verify,
+            "full": extras,
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
+        if extras:
+            dom_name, dom_ms = ("pack", pack_avg) if pack_avg >= unpack_avg else ("unpack", unpack_avg)
+            achieved = ALG_BYTES_PER_REC * n / (dom_ms / 1e3) / 1e9
+            # the same kernel from a cold Infinity Cache (512 MiB written before each
+            # call): the warm figure above is partly served on-die, cold is not
+            frac_cold = None
+            if cold:
+                frac_cold = round(ALG_BYTES_PER_REC * n / (cold[dom_name] / 1e3) / 1e9 / HBM_PEAK_GBPS, 4)
+            prof = committed_profiles(dom_name, n)
+            line["kernels_ms"] = {"pack": round(pack_avg, 4), "unpack": round(unpack_avg, 4),
+                                  "clock": "dispatch begin/end stamped by hipExtLaunchKernel "
+                                           "(srpc_time_next_call), K armed steps after the step clock"}
+            line["kernels_ms_cold"] = cold
+            line["roofline"] = {"bound": "hbm", "kernel": dom_name, "achieved": round(achieved, 1),
+                                "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                                "frac_of_measured_copy": round(achieved / HBM_MEASURED_COPY_GBPS, 4),
+                                "frac_cold": frac_cold,
+                                "regime": "frac: warm steps (back to back; the 256 MiB Infinity Cache holds part "
+                                          "of the previous call's output); frac_cold: the same kernel after a "
+                                          "512 MiB flush",
+                                "alg_bytes_per_launch": ALG_BYTES_PER_REC * n,
+                                "traffic": prof["traffic"],
+                                "traffic_over_alg": (round(prof["traffic"] / (ALG_BYTES_PER_REC * n), 4)
+                                                     if prof["traffic"] else None),
+                                "committed_rocprof_avg_us": prof["committed_rocprof_avg_us"],
+                                "kernel_stats_file": prof["kernel_stats_file"],
+                                "pmc_file": prof["pmc_file"]}
+            line["verify"] = verify
         if gather:
             line["gather"] = gather
-        if world > 1:
+        if extras and world > 1:
             seen = [r["rccl"] for r in per_rank]
             line["rccl"] = {"ranks_seen": [r["rank"] for r in seen] if all(seen) else None,
                             "nranks_seen": sorted({r["nranks"] for r in seen}) if all(seen) else None,
                             "collective": gather["collective"] if gather else None,
                             "note": None if all(seen) else (comm_note or "no libsrpc_gpu communicator "
                                                             f"(--dist-backend {args.dist_backend})")}
-        line["per_rank"] = per_rank
+        if extras:
+            line["per_rank"] = per_rank
         if strong:
             with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
                 streams = json.load(f)["streams"]
@@ -824,7 +905,7 @@ def main() -> None:
             line["strong_scaling"] = strong
         if pcie:
             line["pcie_inclusive"] = pcie
-        if world == 1 and args.cpu_seconds > 0:
+        if extras and world == 1 and args.cpu_seconds > 0:
             line["cpu_baseline"] = cpu_baseline(n, args.cpu_seconds)
         line["native_lib"] = _lib.so_path()
         print(json.dumps(line), flush=True)

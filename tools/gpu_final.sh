@@ -9,7 +9,7 @@ P=${2:-all}
 mkdir -p gpurun_out
 if [ "$P" != 2 ]; then
   timeout -k 10 60 python3 -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke_${R}.log 2>&1 || exit 1
-  timeout -k 10 300 python3 bench.py > gpurun_out/bench_default_${R}.log 2>&1 || exit 2
+  bash tools/gpu_steps.sh -x "600 bench_default_${R}.log python3 bench.py --full" || exit 2
   bash tools/gpu_profile.sh "$R" || exit 3
 fi
 if [ "$P" != 1 ]; then
