@@ -170,6 +170,17 @@ int srpc_plan_force_path(srpc_plan* plan, int path);
                                         directions, 0 = generic kernels only        */
 #define SRPC_TUNE_GRID 5             /* DWORD path: max workgroups (0 = one per
                                         256*iter records; else grid-stride)       */
+#define SRPC_TUNE_SWEEP 14           /* DWORD path: order in which a call walks its records.
+                                        bit0: pack starts at the last record and walks
+                                        down, bit1: unpack does (0..3).  A consumer that
+                                        starts where its producer finished finds the
+                                        producer's last lines still on die where the cache
+                                        replaces least-recently-used lines first; measured
+                                        neutral on MI355X with the default stores, so the
+                                        default is 0.  Results are byte-identical for
+                                        every value.                                 */
+#define SRPC_TUNE_UNPACK_NONTEMPORAL 15 /* DWORD path: unpack's non-temporal bits alone
+                                        (SRPC_TUNE_NONTEMPORAL sets pack's and unpack's) */
 int srpc_plan_tune(srpc_plan* plan, int knob, int value);
 
 /* Pack n records.  d_cols[f] (host array of nfields device pointers) holds

@@ -25,16 +25,20 @@ static_assert(kMaxPrefix + 8u * kMaxFields <= kMaxTileStride, "fixed records wit
 constexpr int kNtStore = 1;
 constexpr int kNtLoad = 2;
 
-// DWORD-path variant: records per lane (1 or 4), iterations per lane, NT bits.
-// Default = the fastest in the steady-state bench loop on MI355X (16M Quad,
-// profiles/r01_tune.log): one record per lane, one iteration, non-temporal
-// loads and stores (streamed bytes are touched once per kernel).
+// DWORD-path variant: records per lane (1 or 4), iterations per lane, NT bits
+// of pack and of unpack, grid cap, sweep direction.  The values a plan starts
+// with come from default_dword_variant (srpc_gpu.hip), per record width.
 struct DwordVariant {
     int rpl = 1;
     int iter = 1;
     int nt = kNtStore | kNtLoad;
-    int grid = 0;  // 0: one workgroup per 256*iter records; >0: at most this many (grid-stride)
+    int nt_unpack = kNtStore | kNtLoad;  // unpack's bits (SRPC_TUNE_NONTEMPORAL sets both)
+    int grid = 0; // 0: one workgroup per 256*iter records; >0: at most this many (grid-stride)
+    int sweep = 0; // SRPC_TUNE_SWEEP: kSweep* bits, which direction walks the records downwards
 };
+
+constexpr int kSweepPackDown = 1;
+constexpr int kSweepUnpackDown = 2;
 
 __device__ __forceinline__ void report_bad(srpc_unpack_status* st, uint32_t flag, uint64_t rec) {
     atomicOr(&st->flags, flag);

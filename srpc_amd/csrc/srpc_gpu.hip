@@ -126,11 +126,19 @@ __device__ __forceinline__ void load_record(const uint8_t* p, uint32_t (&v)[W]) 
 // apart, so every wave instruction touches consecutive elements (256 B per
 // column load, 64*4W B per record store) while each lane keeps ITER*W
 // independent loads in flight.
+//
+// All four kernels walk blocks of kBlock*ITER lane slots: workgroup blockIdx.x
+// takes block numbers blockIdx.x, +gridDim.x, ... below nblk, and block number
+// i is slots [b*kBlock*ITER, (b+1)*kBlock*ITER) with b = i (ascending) or
+// nblk-1-i (`down`, SRPC_TUNE_SWEEP: the first workgroups dispatched take the
+// highest records, also under a capped grid).  nblk and down are kernel
+// arguments (SGPRs); inside a block, addresses still ascend with the lane.
 template <int W, int ITER, int NT>
 __global__ __launch_bounds__(kBlock) void k_pack_dword(DwordMap m, uint8_t* __restrict__ wire,
-                                                       uint64_t n) {
-    const uint64_t step = static_cast<uint64_t>(gridDim.x) * (kBlock * ITER);
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * (kBlock * ITER) + threadIdx.x; r0 < n; r0 += step) {
+                                                       uint64_t n, uint64_t nblk, uint32_t down) {
+    for (uint64_t i = blockIdx.x; i < nblk; i += gridDim.x) {
+        const uint64_t b = down ? nblk - 1 - i : i;
+        const uint64_t r0 = b * (kBlock * ITER) + threadIdx.x;
         uint32_t v[ITER][W];
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -150,9 +158,10 @@ __global__ __launch_bounds__(kBlock) void k_pack_dword(DwordMap m, uint8_t* __re
 
 template <int W, int ITER, int NT>
 __global__ __launch_bounds__(kBlock) void k_unpack_dword(DwordMap m, const uint8_t* __restrict__ wire,
-                                                         uint64_t n) {
-    const uint64_t step = static_cast<uint64_t>(gridDim.x) * (kBlock * ITER);
-    for (uint64_t r0 = static_cast<uint64_t>(blockIdx.x) * (kBlock * ITER) + threadIdx.x; r0 < n; r0 += step) {
+                                                         uint64_t n, uint64_t nblk, uint32_t down) {
+    for (uint64_t i = blockIdx.x; i < nblk; i += gridDim.x) {
+        const uint64_t b = down ? nblk - 1 - i : i;
+        const uint64_t r0 = b * (kBlock * ITER) + threadIdx.x;
         uint32_t v[ITER][W];
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -176,9 +185,10 @@ __global__ __launch_bounds__(kBlock) void k_unpack_dword(DwordMap m, const uint8
 // the one-record-per-lane kernel of the same variant (the host splits n).
 template <int W, int ITER, int NT>
 __global__ __launch_bounds__(kBlock) void k_pack_dword_x4(DwordMap m, uint8_t* __restrict__ wire,
-                                                          uint64_t nq) {
-    const uint64_t step = static_cast<uint64_t>(gridDim.x) * (kBlock * ITER);
-    for (uint64_t q0 = static_cast<uint64_t>(blockIdx.x) * (kBlock * ITER) + threadIdx.x; q0 < nq; q0 += step) {
+                                                          uint64_t nq, uint64_t nblk, uint32_t down) {
+    for (uint64_t i = blockIdx.x; i < nblk; i += gridDim.x) {
+        const uint64_t b = down ? nblk - 1 - i : i;
+        const uint64_t q0 = b * (kBlock * ITER) + threadIdx.x;
         u32x4 c[ITER][W];
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -208,9 +218,10 @@ __global__ __launch_bounds__(kBlock) void k_pack_dword_x4(DwordMap m, uint8_t* _
 
 template <int W, int ITER, int NT>
 __global__ __launch_bounds__(kBlock) void k_unpack_dword_x4(DwordMap m, const uint8_t* __restrict__ wire,
-                                                            uint64_t nq) {
-    const uint64_t step = static_cast<uint64_t>(gridDim.x) * (kBlock * ITER);
-    for (uint64_t q0 = static_cast<uint64_t>(blockIdx.x) * (kBlock * ITER) + threadIdx.x; q0 < nq; q0 += step) {
+                                                            uint64_t nq, uint64_t nblk, uint32_t down) {
+    for (uint64_t i = blockIdx.x; i < nblk; i += gridDim.x) {
+        const uint64_t b = down ? nblk - 1 - i : i;
+        const uint64_t q0 = b * (kBlock * ITER) + threadIdx.x;
         u32x4 c[ITER][W];
 #pragma unroll
         for (int it = 0; it < ITER; ++it) {
@@ -800,38 +811,43 @@ using namespace srpc_impl;
 constexpr bool kTilePackFlat = SRPC_TILE_PACK_FLAT != 0;
 
 template <int W, int ITER, int NT>
-int launch_dword_v(bool pack, const DwordMap& m, uint8_t* wire, uint64_t n, int rpl, int max_grid, hipStream_t s) {
+int launch_dword_v(bool pack, const DwordMap& m, uint8_t* wire, uint64_t n, int rpl, int max_grid, bool down,
+                   hipStream_t s) {
     const uint64_t per = static_cast<uint64_t>(kBlock) * ITER;
     // kernels are grid-stride: max_grid > 0 caps the workgroup count
     auto cap = [max_grid](uint64_t g) { return max_grid > 0 ? std::min<uint64_t>(g, max_grid) : g; };
-    uint64_t done = 0;
-    if (rpl == 4) {
-        const uint64_t nq = n / 4;
-        if (nq) {
-            const uint64_t grid = cap((nq + per - 1) / per);
-            if (grid > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
-            if (pack)
-                launch(k_pack_dword_x4<W, ITER, NT>, dim3(static_cast<uint32_t>(grid)),
-                                   dim3(kBlock), 0, s, m, wire, nq);
-            else
-                launch(k_unpack_dword_x4<W, ITER, NT>, dim3(static_cast<uint32_t>(grid)),
-                                   dim3(kBlock), 0, s, m, wire, nq);
-            done = nq * 4;
-        }
-    }
-    if (done < n) {
-        // remaining records (all of them for rpl == 1): shift the map to `done`
+    const uint32_t dn = down ? 1u : 0u;
+    // x4 body: the first nq quads; the rest (all records for rpl == 1) go one
+    // record per lane with the map shifted to `done`
+    const uint64_t nq = rpl == 4 ? n / 4 : 0;
+    const uint64_t done = nq * 4, rest = n - done;
+    const uint64_t nblk_q = (nq + per - 1) / per, nblk_r = (rest + per - 1) / per;
+    if (cap(nblk_q) > 0x7fffffffull || cap(nblk_r) > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
+    auto body = [&] {
+        if (!nq) return;
+        const dim3 grid(static_cast<uint32_t>(cap(nblk_q)));
+        if (pack)
+            launch(k_pack_dword_x4<W, ITER, NT>, grid, dim3(kBlock), 0, s, m, wire, nq, nblk_q, dn);
+        else
+            launch(k_unpack_dword_x4<W, ITER, NT>, grid, dim3(kBlock), 0, s, m, wire, nq, nblk_q, dn);
+    };
+    auto tail = [&] {
+        if (!rest) return;
         DwordMap t = m;
         for (int k = 0; k < W; ++k) t.src[k] += done << t.lg[k];
-        const uint64_t rest = n - done;
-        const uint64_t grid = cap((rest + per - 1) / per);
-        if (grid > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
+        const dim3 grid(static_cast<uint32_t>(cap(nblk_r)));
         if (pack)
-            launch(k_pack_dword<W, ITER, NT>, dim3(static_cast<uint32_t>(grid)), dim3(kBlock),
-                               0, s, t, wire + done * 4 * W, rest);
+            launch(k_pack_dword<W, ITER, NT>, grid, dim3(kBlock), 0, s, t, wire + done * 4 * W, rest, nblk_r, dn);
         else
-            launch(k_unpack_dword<W, ITER, NT>, dim3(static_cast<uint32_t>(grid)), dim3(kBlock),
-                               0, s, t, wire + done * 4 * W, rest);
+            launch(k_unpack_dword<W, ITER, NT>, grid, dim3(kBlock), 0, s, t, wire + done * 4 * W, rest, nblk_r, dn);
+    };
+    // a descending call starts with the highest records: the tail's
+    if (down) {
+        tail();
+        body();
+    } else {
+        body();
+        tail();
     }
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
@@ -842,13 +858,14 @@ int launch_dword_v(bool pack, const DwordMap& m, uint8_t* wire, uint64_t n, int 
 template <int W>
 int launch_dword(bool pack, const DwordMap& m, uint8_t* wire, uint64_t n, const DwordVariant& v,
                  hipStream_t s) {
+    const bool down = (v.sweep & (pack ? kSweepPackDown : kSweepUnpackDown)) != 0;
     if constexpr (W == 1 || W == 2 || W == 4) {
-#define SRPC_NT_CASES(IT)                                                        \
-    switch (v.nt) {                                                              \
-    case 0: return launch_dword_v<W, IT, 0>(pack, m, wire, n, v.rpl, v.grid, s);         \
-    case 1: return launch_dword_v<W, IT, 1>(pack, m, wire, n, v.rpl, v.grid, s);         \
-    case 2: return launch_dword_v<W, IT, 2>(pack, m, wire, n, v.rpl, v.grid, s);         \
-    default: return launch_dword_v<W, IT, 3>(pack, m, wire, n, v.rpl, v.grid, s);        \
+#define SRPC_NT_CASES(IT)                                                              \
+    switch (pack ? v.nt : v.nt_unpack) {                                                                 \
+    case 0: return launch_dword_v<W, IT, 0>(pack, m, wire, n, v.rpl, v.grid, down, s);  \
+    case 1: return launch_dword_v<W, IT, 1>(pack, m, wire, n, v.rpl, v.grid, down, s);  \
+    case 2: return launch_dword_v<W, IT, 2>(pack, m, wire, n, v.rpl, v.grid, down, s);  \
+    default: return launch_dword_v<W, IT, 3>(pack, m, wire, n, v.rpl, v.grid, down, s); \
     }
         switch (v.iter) {
         case 1: SRPC_NT_CASES(1)
@@ -858,7 +875,7 @@ int launch_dword(bool pack, const DwordMap& m, uint8_t* wire, uint64_t n, const 
         }
 #undef SRPC_NT_CASES
     } else {
-        return launch_dword_v<W, 4, 0>(pack, m, wire, n, 1, v.grid, s);
+        return launch_dword_v<W, 4, 0>(pack, m, wire, n, 1, v.grid, down, s);
     }
 }
 
@@ -927,23 +944,49 @@ int check_cols(const srpc_plan* p, const void* const* cols, uint64_t n) {
 // DWORD variant per record width, from the interleaved A/B sweeps of
 // profiles/r01_sweep_{quad,number,two}.log and the bench loop (r01_tune.log):
 // 1-dword records want 16-byte column loads (4 records per lane); 2-dword
-// records two records per lane-iteration with non-temporal loads; 4-dword
-// records one per lane with non-temporal loads and stores.
+// records two records per lane-iteration; 4-dword records one per lane.
+//
+// Loads are non-temporal in both directions.  Stores differ by direction
+// (profiles/r07_sweep_pair_ab.json, r07_sweep_pair_split_nt.json: `pack;
+// unpack` pairs, every setting alternated in one process):
+//  - pack stores the wire with plain stores, so its consumer finds part of it
+//    in the 256 MiB Infinity Cache.  Non-temporal stores leave nothing there:
+//    after such a pack a descending unpack of the wire's last 32-256 MiB
+//    takes as long as after a 512 MiB flush; after a plain-store pack it is
+//    2.7-3.6 us faster than after the flush, all of it won in the first
+//    32-64 MiB below the wire's end (r07_sweep_window.json).
+//  - unpack stores its columns non-temporally, so they do not push the wire
+//    out of that cache.
+// Against non-temporal stores in both directions (the Quad default before)
+// the pair of 16M Quads takes 151.8 us instead of 168.0, of 64M 645 instead
+// of 669; against plain stores in both (Number, TwoNumbers before) the 64M
+// pairs take 151 / 333 us instead of 162 / 364 and the 16M ones the same.
+// The price: a pack into a cache full of someone else's dirty lines (bench
+// `kernels_ms_cold`) takes 91 us instead of 85-89.
+//
+// Sweep direction (SRPC_TUNE_SWEEP) stays ascending.  The reuse-distance
+// argument -- an unpack that starts at the wire's end reads what pack wrote
+// last -- holds under LRU, and with plain stores in both directions a
+// descending unpack does gain 7-16 us per pair (r07: nt=2:2, sweep 2 against
+// 0).  With the stores above the direction no longer matters (16M Quad pair
+// 151.2 against 151.8 us, 64M 642.7 against 644.9, inside the spread): what
+// the cache keeps of a 256 MiB wire does not depend on which end was
+// written last, so it is not LRU.
 DwordVariant default_dword_variant(uint32_t W) {
     DwordVariant v;
     if (W == 1) {
         v.rpl = 4;
         v.iter = 1;
-        v.nt = kNtLoad;
     } else if (W == 4) {
         v.rpl = 1;
         v.iter = 1;
-        v.nt = kNtLoad | kNtStore;
     } else {
         v.rpl = 1;
         v.iter = 2;
-        v.nt = kNtLoad;
     }
+    v.nt = kNtLoad;
+    v.nt_unpack = kNtLoad | kNtStore;
+    v.sweep = 0;
     return v;
 }
 
@@ -1234,11 +1277,19 @@ int srpc_plan_tune(srpc_plan* p, int knob, int value) {
         return SRPC_OK;
     case SRPC_TUNE_NONTEMPORAL:
         if (value < 0 || value > 3) return SRPC_E_INVALID;
-        p->dv.nt = value;
+        p->dv.nt = p->dv.nt_unpack = value;
+        return SRPC_OK;
+    case SRPC_TUNE_UNPACK_NONTEMPORAL:
+        if (value < 0 || value > 3) return SRPC_E_INVALID;
+        p->dv.nt_unpack = value;
         return SRPC_OK;
     case SRPC_TUNE_GRID:
         if (value < 0) return SRPC_E_INVALID;
         p->dv.grid = value;
+        return SRPC_OK;
+    case SRPC_TUNE_SWEEP:
+        if (value < 0 || value > 3) return SRPC_E_INVALID;
+        p->dv.sweep = value;
         return SRPC_OK;
     case SRPC_TUNE_TILE_BYTES:
         if (value < 1024 || value > 49152 || p->has_string || p->stride > kMaxTileStride) return SRPC_E_INVALID;
