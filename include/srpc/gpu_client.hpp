@@ -1,0 +1,368 @@
+// srpc/gpu_client.hpp -- GPU-batched calls: the client-side mirror of
+// srpc::gpu::batch_server (gpu_server.hpp).
+//
+// The reference's generated stub makes one call at a time
+// (examples/calculator_srpc.cpp: pack_request -> send_data -> recv_data ->
+// unpack_response<R>).  batch_client makes a whole batch of calls of one
+// method from device columns, with the same frames on the wire:
+//
+//   request columns (device) -> srpc_gpu_pack with the framed request prefix
+//   (`BE32 len | str(method) | str(Req::name) | body` frames) -> D2H -> socket,
+//   sent while the replies are received (poll: the server answers while it
+//   still receives, and both socket buffers are finite) -> the CPU only walks
+//   the replies' BE32 lengths (walk_frames) -> H2D -> srpc_frames_unpack_replies:
+//   one status code per call and the reply columns, in call order.
+//
+// A reply may be a full `BE32 | code | str(Resp::name) | body` frame or the
+// bare `BE32(1) | code` a server sends for a method it does not know
+// (server.hpp:20-24, gpu_server.hpp answer_cpu); see include/srpc_gpu.h for
+// the table.  When the host walk saw only full-size frames the decode runs in
+// its uniform mode and reads no offsets.  Calls the peer never answers (it
+// closed the connection, or the wait timed out) get RPC_ERR_RECV_TIMEOUT and
+// zero fields; every later call on this client is then unanswered too.
+// Fixed-size Req and Resp only: string schemas throw plan_error
+// (SRPC_E_UNSUPPORTED).
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+#include <poll.h>
+#include <sys/socket.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <chrono>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "frame_walk.hpp"
+#include "gpu.hpp"
+#include "gpu_server.hpp"  // raw_plan, framed_request_prefix, framed_response_prefix
+
+namespace srpc::gpu {
+
+struct call_stats {
+    uint64_t calls = 0;
+    uint64_t ok = 0;          // full replies with code RPC_SUCCESS
+    uint64_t failed = 0;      // well-formed replies (full or bare) with another code
+    uint64_t malformed = 0;   // replies the decode flagged (SRPC_STATUS_PREFIX / _BOUNDS)
+    uint64_t unanswered = 0;  // no reply: RPC_ERR_RECV_TIMEOUT
+    uint64_t chunks = 0;          // batches of at most max_batch calls
+    uint64_t uniform_chunks = 0;  // of those, decoded without offsets (every reply full size)
+    uint64_t sent_bytes = 0;
+    uint64_t received_bytes = 0;
+    double send_seconds = 0;  // in send()
+    double recv_seconds = 0;  // in poll() and recv()
+    double gpu_seconds = 0;   // pack + D2H, H2D + decode + the codes' D2H, host-timed per chunk
+};
+
+class batch_client {
+public:
+    /// Testing hook: sees every chunk's request frames in the staging buffer
+    /// before they are sent (frames, index of the chunk's first call, calls,
+    /// bytes per frame) and may rewrite them.
+    using request_hook_t = std::function<void(uint8_t*, uint64_t, uint64_t, uint64_t)>;
+
+    /// fd: a connected stream socket (not owned).  max_batch: calls per chunk
+    /// (rounded down to a multiple of 16, the columns' alignment rule).
+    explicit batch_client(int fd, uint64_t max_batch = 1u << 20, int device = 0)
+        : _fd(fd), _max(std::max<uint64_t>(16, max_batch & ~15ull)), _dev(device) {
+        check(hipSetDevice(device));
+    }
+    batch_client(batch_client const&) = delete;
+    batch_client& operator=(batch_client const&) = delete;
+    ~batch_client() { release(); }
+
+    void set_request_hook(request_hook_t h) { _hook = std::move(h); }
+    /// Keep every reply byte received by later calls (reply_bytes()).
+    void keep_replies(bool on) { _keep = on; }
+    std::vector<uint8_t> const& reply_bytes() const { return _kept; }
+    /// How long to wait for the peer before the outstanding calls count as
+    /// unanswered; negative (the default): until it answers or closes.
+    void set_timeout_ms(int ms) { _timeout_ms = ms; }
+    call_stats const& last_stats() const { return _last; }
+
+    /// n calls of `method`: request field f of call i is d_req_cols[f][i];
+    /// the reply's fields go to d_resp_cols[f][i] and its status code to
+    /// d_codes[i] (device memory, columns 16-byte aligned).  Returns when the
+    /// outputs are complete.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    call_stats call(std::string const& method, void* const* d_req_cols, uint64_t n, void* const* d_resp_cols,
+                    uint8_t* d_codes, hipStream_t stream = nullptr) {
+        check(hipSetDevice(_dev));
+        entry& e = plans<Req, Resp>(method);
+        ensure(e.fin, e.fout);
+        call_stats st;
+        st.calls = n;
+        std::vector<const void*> rq(e.req_size.size());
+        std::vector<void*> rs(e.resp_size.size());
+        for (uint64_t lo = 0; lo < n; lo += _max) {
+            const uint64_t m = std::min(_max, n - lo);
+            st.chunks += 1;
+            for (size_t f = 0; f < rq.size(); ++f) rq[f] = static_cast<const uint8_t*>(d_req_cols[f]) + lo * e.req_size[f];
+            for (size_t f = 0; f < rs.size(); ++f) rs[f] = static_cast<uint8_t*>(d_resp_cols[f]) + lo * e.resp_size[f];
+            frame_walk w;
+            if (!_eof) {
+                auto t0 = clock::now();
+                check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _d_out, m * e.fin, stream), "srpc_gpu_pack");
+                check(hipMemcpyAsync(_h_out, _d_out, m * e.fin, hipMemcpyDeviceToHost, stream));
+                check(hipStreamSynchronize(stream));
+                st.gpu_seconds += secs(t0);
+                if (_hook) _hook(_h_out, lo, m, e.fin);
+            }
+            w = exchange(m, m * e.fin, e.fout, st);
+            auto t0 = clock::now();
+            const uint64_t nf = w.nframes;
+            if (nf) {
+                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
+                const bool uniform = w.all_full;
+                if (!uniform) check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+                st.uniform_chunks += uniform;
+                check_srpc(srpc_frames_unpack_replies(e.resp->get(), _d_in, w.walked, uniform ? nullptr : _d_offs, nf,
+                                                      rs.data(), d_codes + lo, _d_status, stream),
+                           "srpc_frames_unpack_replies");
+                check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+                check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            }
+            if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields
+                check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
+                for (size_t f = 0; f < rs.size(); ++f)
+                    check(hipMemsetAsync(static_cast<uint8_t*>(rs[f]) + nf * e.resp_size[f], 0, (m - nf) * e.resp_size[f], stream));
+                st.unanswered += m - nf;
+            }
+            check(hipStreamSynchronize(stream));
+            st.gpu_seconds += secs(t0);
+            if (nf) count(e, w, st);
+            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
+            // bytes after the chunk's last frame belong to the next chunk's replies
+            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
+            _have -= w.walked;
+        }
+        _last = st;
+        return st;
+    }
+
+    /// The same from and to host records (host_columns<T> transposes them).
+    template <SrpcMessage Req, SrpcMessage Resp>
+    std::vector<response_t<Resp>> call(std::string const& method, std::vector<Req> const& reqs) {
+        check(hipSetDevice(_dev));
+        (void)plans<Req, Resp>(method);  // string schemas are refused before anything is allocated
+        const uint64_t n = reqs.size();
+        host_columns<Req> in;
+        in.scatter(reqs);
+        host_columns<Resp> out;
+        out.n = n;
+        {
+            Resp probe{};
+            for_each_leaf<Resp>(probe, [&](const auto& v) { out.col.emplace_back(n * sizeof(v)); });
+            out.offs.resize(out.col.size());
+        }
+        device_buffers rq(in.col), rs(out.col);
+        std::vector<uint8_t> codes(n);
+        device_buffers dc(std::vector<std::vector<uint8_t>>{codes});
+        for (size_t f = 0; f < in.col.size(); ++f)
+            check(hipMemcpy(rq.p[f], in.col[f].data(), in.col[f].size(), hipMemcpyHostToDevice));
+        call<Req, Resp>(method, rq.p.data(), n, rs.p.data(), static_cast<uint8_t*>(dc.p[0]));
+        for (size_t f = 0; f < out.col.size(); ++f)
+            check(hipMemcpy(out.col[f].data(), rs.p[f], out.col[f].size(), hipMemcpyDeviceToHost));
+        check(hipMemcpy(codes.data(), dc.p[0], n, hipMemcpyDeviceToHost));
+        std::vector<Resp> vals;
+        out.gather(vals);
+        std::vector<response_t<Resp>> res(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            res[i].set_code(static_cast<rpc_status_code>(codes[i]));
+            res[i].set_value(vals[i]);
+        }
+        return res;
+    }
+
+private:
+    using clock = std::chrono::steady_clock;
+    struct entry {
+        std::unique_ptr<raw_plan> req, resp;
+        uint64_t fin = 0, fout = 0;  // request / full reply frame bytes
+        std::vector<uint64_t> req_size, resp_size;
+        std::vector<uint8_t> resp_prefix;
+    };
+    struct device_buffers {
+        std::vector<void*> p;
+        explicit device_buffers(std::vector<std::vector<uint8_t>> const& cols) {
+            for (auto const& c : cols) {
+                void* d = nullptr;
+                if (hipMalloc(&d, c.size() + 16) != hipSuccess) {
+                    free_all();
+                    throw plan_error("batch_client: hipMalloc", SRPC_E_HIP);
+                }
+                p.push_back(d);
+            }
+        }
+        device_buffers(device_buffers const&) = delete;
+        device_buffers& operator=(device_buffers const&) = delete;
+        ~device_buffers() { free_all(); }
+        void free_all() {
+            for (void* d : p) (void)hipFree(d);
+            p.clear();
+        }
+    };
+
+    static double secs(clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); }
+    static void check(hipError_t e) {
+        if (e != hipSuccess) throw plan_error(hipGetErrorString(e), SRPC_E_HIP);
+    }
+    static void check_srpc(int rc, const char* what) {
+        if (rc < 0) throw plan_error(what, rc);
+    }
+
+    template <SrpcMessage Req, SrpcMessage Resp>
+    entry& plans(std::string const& method) {
+        const std::string key = method + '\0' + Req::name + '\0' + Resp::name;
+        auto it = _plans.find(key);
+        if (it != _plans.end()) return it->second;
+        const std::vector<int32_t> kq = flat_kinds<Req>(), ks = flat_kinds<Resp>();
+        for (int32_t k : kq)
+            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string request)", SRPC_E_UNSUPPORTED);
+        for (int32_t k : ks)
+            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string response)", SRPC_E_UNSUPPORTED);
+        entry e;
+        e.resp_prefix = framed_response_prefix<Resp>(RPC_SUCCESS);
+        e.req = std::make_unique<raw_plan>(kq, framed_request_prefix<Req>(method), _dev);
+        e.resp = std::make_unique<raw_plan>(ks, e.resp_prefix, _dev);
+        e.fin = e.req->record_bytes();
+        e.fout = e.resp->record_bytes();
+        Req rq{};
+        for_each_leaf<Req>(rq, [&](const auto& v) { e.req_size.push_back(sizeof(v)); });
+        Resp rs{};
+        for_each_leaf<Resp>(rs, [&](const auto& v) { e.resp_size.push_back(sizeof(v)); });
+        return _plans.emplace(key, std::move(e)).first->second;
+    }
+
+    /// Staging for chunks of _max calls with fin-byte requests and fout-byte
+    /// replies.  The receive buffer has room for a chunk of full replies and
+    /// 4 KiB more; a peer whose replies outgrow it is treated as closed.
+    void ensure(uint64_t fin, uint64_t fout) {
+        const uint64_t out = _max * fin + 16, in = _max * fout + 4096;
+        if (out <= _out_cap && in <= _in_cap) return;
+        if (in >= (1ull << 32)) throw plan_error("batch_client: max_batch replies pass 4 GiB", SRPC_E_CAPACITY);
+        std::vector<uint8_t> carry;
+        if (_have) carry.assign(_h_in, _h_in + _have);
+        release();
+        _out_cap = std::max(out, _out_cap);
+        _in_cap = std::max(in, _in_cap);
+        check(hipMalloc(reinterpret_cast<void**>(&_d_out), _out_cap));
+        check(hipMalloc(reinterpret_cast<void**>(&_d_in), _in_cap + 16));
+        check(hipMalloc(reinterpret_cast<void**>(&_d_offs), 4 * _max));
+        check(hipMalloc(reinterpret_cast<void**>(&_d_status), sizeof(srpc_unpack_status)));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_out), _out_cap));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_in), _in_cap));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_offs), 4 * _max));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_codes), _max));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_status), sizeof(srpc_unpack_status)));
+        if (!carry.empty()) std::memcpy(_h_in, carry.data(), carry.size());
+        _have = carry.size();
+    }
+
+    void release() {
+        (void)hipFree(_d_out);
+        (void)hipFree(_d_in);
+        (void)hipFree(_d_offs);
+        (void)hipFree(_d_status);
+        (void)hipHostFree(_h_out);
+        (void)hipHostFree(_h_in);
+        (void)hipHostFree(_h_offs);
+        (void)hipHostFree(_h_codes);
+        (void)hipHostFree(_h_status);
+        _d_out = _d_in = _h_out = _h_in = _h_codes = nullptr;
+        _d_offs = _h_offs = nullptr;
+        _d_status = _h_status = nullptr;
+        _have = 0;
+    }
+
+    /// Send the chunk's `total` request bytes while receiving its m replies.
+    /// Neither direction blocks: poll waits for whichever is ready.
+    frame_walk exchange(uint64_t m, uint64_t total, uint64_t fout, call_stats& st) {
+        frame_walk w = walk_frames(_h_in, _have, m, _h_offs, fout);
+        uint64_t sent = 0;
+        bool send_dead = false;
+        while (w.nframes < m && !_eof) {
+            if (_have == _in_cap) {  // replies larger than the buffer: give the connection up
+                _eof = true;
+                break;
+            }
+            pollfd p{_fd, static_cast<short>(POLLIN | (sent < total && !send_dead ? POLLOUT : 0)), 0};
+            auto t0 = clock::now();
+            const int r = poll(&p, 1, _timeout_ms);
+            st.recv_seconds += secs(t0);
+            if (r < 0 && errno == EINTR) continue;
+            if (r <= 0) {  // an error, or nothing for _timeout_ms
+                _eof = true;
+                break;
+            }
+            if (p.revents & (POLLIN | POLLHUP | POLLERR)) {
+                t0 = clock::now();
+                const ssize_t k = recv(_fd, _h_in + _have, _in_cap - _have, MSG_DONTWAIT);
+                st.recv_seconds += secs(t0);
+                if (k > 0) {
+                    _have += static_cast<uint64_t>(k);
+                    st.received_bytes += static_cast<uint64_t>(k);
+                    w = walk_frames(_h_in, _have, m, _h_offs, fout, w);
+                } else if (k == 0 || (errno != EAGAIN && errno != EWOULDBLOCK && errno != EINTR)) {
+                    _eof = true;
+                }
+            }
+            if ((p.revents & POLLOUT) && sent < total && !send_dead) {
+                t0 = clock::now();
+                const ssize_t k = send(_fd, _h_out + sent, total - sent, MSG_DONTWAIT | MSG_NOSIGNAL);
+                st.send_seconds += secs(t0);
+                if (k > 0) {
+                    sent += static_cast<uint64_t>(k);
+                    st.sent_bytes += static_cast<uint64_t>(k);
+                } else if (k < 0 && errno != EAGAIN && errno != EWOULDBLOCK && errno != EINTR) {
+                    send_dead = true;  // the peer stopped reading; what it already answered still arrives
+                }
+            }
+        }
+        return w;
+    }
+
+    /// The chunk's counts from the codes; only a chunk the decode flagged is
+    /// looked at frame by frame (the table of include/srpc_gpu.h on the host).
+    void count(entry const& e, frame_walk const& w, call_stats& st) {
+        const uint64_t nf = w.nframes;
+        if (_h_status->flags == 0) {
+            const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
+            st.ok += ok;
+            st.failed += nf - ok;
+            return;
+        }
+        for (uint64_t i = 0; i < nf; ++i) {
+            const uint64_t o = _h_offs[i], end = i + 1 < nf ? _h_offs[i + 1] : w.walked, len = end - o;
+            const uint8_t* f = _h_in + o;
+            const bool full = len == e.fout && std::memcmp(f, e.resp_prefix.data(), 4) == 0 &&
+                              std::memcmp(f + 5, e.resp_prefix.data() + 5, e.resp_prefix.size() - 5) == 0;
+            const bool bare = len == 5 && f[4] != 0;
+            if (!(full || bare)) st.malformed += 1;
+            else if (_h_codes[i] == RPC_SUCCESS) st.ok += 1;
+            else st.failed += 1;
+        }
+    }
+
+    int _fd;
+    uint64_t _max;
+    int _dev;
+    int _timeout_ms = -1;
+    bool _eof = false;
+    bool _keep = false;
+    request_hook_t _hook;
+    std::map<std::string, entry> _plans;
+    std::vector<uint8_t> _kept;
+    call_stats _last;
+    uint64_t _out_cap = 0, _in_cap = 0, _have = 0;
+    uint8_t *_d_out = nullptr, *_d_in = nullptr, *_h_out = nullptr, *_h_in = nullptr, *_h_codes = nullptr;
+    uint32_t *_d_offs = nullptr, *_h_offs = nullptr;
+    srpc_unpack_status *_d_status = nullptr, *_h_status = nullptr;
+};
+
+}  // namespace srpc::gpu

@@ -453,6 +453,57 @@ int srpc_frames_offsets(const srpc_plan* const* req_plans, const uint32_t* resp_
                         uint64_t* d_out_off, uint64_t* d_total, void* d_scratch,
                         uint64_t scratch_bytes, void* stream);
 
+/* ---- framed reply batches (client side; added within ABI 8) -------------------
+ * The reference's generated stub answers one call at a time: send_data ->
+ * recv_data -> unpack_response<R>, which reads `u8 code | str(R::name) | body`
+ * (packer.hpp:123-137).  srpc_frames_unpack_replies decodes the reply stream of
+ * a whole batch of calls in one launch, in call order: one status code per
+ * call in d_codes[i] and the reply's fields in d_cols[f][i] (16-byte aligned
+ * columns, as for the TILE path).
+ *
+ * reply_plan is a fixed-size plan whose prefix is a framed response prefix,
+ * `BE32(payload) | u8 code | str(Resp::name)`; its code byte is ignored.  F is
+ * its record bytes, the whole frame.  Frame i is bytes [d_offs[i], end_i) of
+ * d_buf (16-byte aligned), end_i = d_offs[i+1], or buf_len for the last frame
+ * (the convention of srpc_frames_classify).  d_offs == NULL is the uniform
+ * mode: frame i is [i*F, (i+1)*F) and no offset is read; if buf_len is short
+ * of nframes frames, the frames that fit are decoded, the rest are BOUNDS
+ * frames of the table below and SRPC_ERR_BOUNDS is returned (first_bad_record
+ * = buf_len / F), as from srpc_gpu_unpack.
+ *
+ *   frame i                                     d_codes[i]          fields   status
+ *   offsets out of order, end_i > buf_len,      SRPC_REPLY_NO_CODE  zero     BOUNDS
+ *     shorter than 4 bytes, BE32 != len - 4,
+ *     or an empty payload
+ *   full: len == F and every prefix byte but    payload[0]          decoded  -
+ *     the code byte equals the plan's
+ *   bare: a payload of one nonzero byte (the    that byte           zero     -
+ *     `BE32(1) | RPC_ERR_FUNCTION_NOT_REGISTERED`
+ *     a server sends for an unknown method)
+ *   anything else with a payload                payload[0]          zero     PREFIX
+ *
+ * A full frame is decoded whatever its code, as unpack_response decodes the
+ * body after reading any code.  *d_status (may be NULL) is reset by the call;
+ * first_bad_record is the smallest flagged i.  (The reference terminates on
+ * bare and malformed frames -- buffer::increment throws inside noexcept -- so
+ * this table is the contract.)
+ * No byte outside [d_buf, d_buf + buf_len) is read.  Work is bounded by
+ * buf_len + nframes * F; the call is stream-ordered, allocates nothing, waits
+ * on nothing and can be captured.  One kernel: a workgroup stages the span of
+ * srpc_frames_replies_per_tile consecutive frames (16 * max(1, 16384 / (16 F)))
+ * into LDS with 16-byte loads, parses one frame per lane and writes the
+ * columns as 16-byte chunks; frames an oversize junk frame pushed out of the
+ * image are read on their own.
+ * Refused with nothing launched: a string plan or a prefix under 5 bytes
+ * (SRPC_E_UNSUPPORTED); a NULL reply_plan, d_cols or d_codes, or buf_len >=
+ * 4 GiB (SRPC_E_INVALID); a misaligned d_buf or column (SRPC_E_ALIGN). */
+#define SRPC_REPLY_NO_CODE 0xFF
+int srpc_frames_unpack_replies(const srpc_plan* reply_plan, const uint8_t* d_buf, uint64_t buf_len,
+                               const uint32_t* d_offs, uint64_t nframes, void* const* d_cols,
+                               uint8_t* d_codes, srpc_unpack_status* d_status, void* stream);
+/* Testing hook: frames per workgroup tile for this reply plan. */
+int srpc_frames_replies_per_tile(const srpc_plan* reply_plan, uint32_t* out);
+
 /* ---- utilities --------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
@@ -492,7 +543,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
                          uint64_t scratch_bytes, srpc_unpack_status* d_status, void* stream);
 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
- * srpc_gpu_pack / _unpack / _pack_var / _unpack_var call made on this host
+ * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
+ * srpc_frames_unpack_replies call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

@@ -32,6 +32,7 @@ SRPC_MAX_PREFIX = 1024
 SRPC_FRAMES_MAX_PLANS = 16
 SRPC_FRAME_UNKNOWN = 0xFF
 SRPC_FRAMES_MAX_STRINGS = 16
+SRPC_REPLY_NO_CODE = 0xFF
 
 SRPC_PATH_DWORD = 1
 SRPC_PATH_TILE = 2
@@ -82,6 +83,8 @@ SIGNATURES = {
     "srpc_frames_gather_var": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_scatter_var": (C.c_int, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "srpc_frames_offsets": (C.c_int, [_vp, _vp, C.c_int, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "srpc_frames_unpack_replies": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "srpc_frames_replies_per_tile": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
     "srpc_status_string": (C.c_char_p, [C.c_int]),
     "srpc_gpu_abi_version": (C.c_int, []),
 }

@@ -22,6 +22,10 @@
 // the response index srpc_gpu_pack_var writes (srpc_frames_scatter_var), and
 // the reply stream's offsets are recomputed once those sizes are known
 // (srpc_frames_offsets).
+//
+// Client side (srpc::gpu::batch_client): the reply stream of a batch of calls
+// -- full frames, bare error frames, junk -- is decoded in call order by one
+// kernel, k_unpack_replies (srpc_frames_unpack_replies), described below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -260,6 +264,268 @@ uint32_t grid_for(uint64_t work, uint64_t per) {
     return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>((work + per - 1) / per, 1u << 20)));
 }
 
+// ---------------------------------------------------------------------------
+// Client side: a reply stream of mixed frames -> columns and one code per call,
+// in call order (srpc_frames_unpack_replies).
+//
+// A workgroup takes R consecutive frames.  Their bytes are contiguous in the
+// stream, so the tile is one span starting at a 16-byte boundary: it is staged
+// into an LDS image with 16-byte loads (the bytes past the last whole chunk
+// inside buf_len bytewise; nothing past buf_len is read).  One lane per frame
+// then checks the frame against the table in srpc_gpu.h -- offsets, BE32,
+// length, and the plan's prefix (code byte masked out) eight bytes at a time
+// from aligned LDS dwords -- and leaves the frame's image position in pos[]
+// (or "fields are zero").  Every field's column is then written as 16-byte
+// chunks gathered from the image through pos[], as k_unpack_tile does with a
+// fixed stride.  A frame whose bytes lie outside the image (an oversize junk
+// frame before it used the image up, or its offset is out of order) is read
+// from global memory on its own, at most F bytes.
+// LDS: image[R*F + 32] | tmpl[P8] | mask[P8] | pos[R] | offs[R + 1] (indexed).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kReplyTileBytes = 16384;  // target image bytes per tile
+constexpr uint32_t kPosZero = 0xffffffffu;   // pos[j]: the frame's fields are zero
+constexpr uint32_t kPosGlobal = 0xfffffffeu; // pos[j]: a full frame outside the image
+constexpr int kReplyLoads = 4;               // 16-byte loads in flight per lane
+
+typedef uint32_t r_u32x4 __attribute__((ext_vector_type(4)));
+
+struct ReplyArgs {
+    uint8_t* col[kMaxFields];
+    uint32_t size[kMaxFields];
+    uint32_t off[kMaxFields];  // field offset inside the frame
+    const uint8_t* prefix;     // the plan's device prefix (zero-padded 16 bytes past its end)
+    uint32_t nfields;
+    uint32_t F;                // bytes of a full frame
+    uint32_t prefix_len;
+    uint32_t R;                // frames per tile (multiple of 16)
+};
+
+inline uint32_t reply_tile_frames(uint32_t F) { return 16 * std::max<uint32_t>(1, kReplyTileBytes / (16 * F)); }
+
+inline size_t reply_lds_bytes(uint32_t F, uint32_t prefix_len, uint32_t R, bool indexed) {
+    return static_cast<size_t>(R) * F + 32 + 2 * ((prefix_len + 7) & ~7u) + 4 * R + (indexed ? 4 * (R + 1) : 0);
+}
+
+// S <= 8 bytes at any LDS byte offset from aligned dword reads (may read up to
+// 8 bytes past the value, inside the image's padding).
+template <int S>
+__device__ __forceinline__ uint64_t lds_get(const uint8_t* lds, uint32_t at) {
+    if constexpr (S == 1) {
+        return lds[at];
+    } else if constexpr (S == 8) {
+        return lds_u64(lds, at);
+    } else {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(lds + (at & ~3u));
+        const uint32_t v = __builtin_amdgcn_alignbyte(w[1], w[0], at & 3);
+        return S == 2 ? (v & 0xffffu) : v;
+    }
+}
+
+// Field bytes [off, off + S) of the tile's frame e: from the image, from global
+// memory (a full frame outside the image), or zero.
+template <int S, bool INDEXED>
+__device__ __forceinline__ uint64_t reply_elem(const uint8_t* img, const uint32_t* pos, const uint32_t* lo,
+                                               const uint8_t* __restrict__ buf, uint32_t off, uint32_t e) {
+    const uint32_t p = pos[e];
+    uint64_t v = 0;
+    if (p < kPosGlobal) {
+        v = lds_get<S>(img, p + off);
+    } else if (INDEXED && p == kPosGlobal) {
+        const uint8_t* g = buf + lo[e] + off;
+#pragma unroll
+        for (int k = 0; k < S; ++k) v |= static_cast<uint64_t>(g[k]) << (8 * k);
+    }
+    return v;
+}
+
+template <int S, bool INDEXED>
+__device__ __forceinline__ void reply_chunk(const uint8_t* img, const uint32_t* pos, const uint32_t* lo,
+                                            const uint8_t* __restrict__ buf, uint32_t off, uint32_t c, uint32_t nr,
+                                            uint8_t* dstc) {
+    constexpr uint32_t per = 16 / S;
+    const uint32_t e0 = c * per;
+    if (e0 + per <= nr) {
+        // the chunk's positions with 8- or 16-byte LDS reads (pos + e0 is aligned
+        // to its 4 * per bytes); a branch-free gather unless a frame of the chunk
+        // lies outside the image, so the LDS reads of all elements issue together
+        uint32_t p[per];
+        if constexpr (per == 2) {
+            const uint2 t = *reinterpret_cast<const uint2*>(pos + e0);
+            p[0] = t.x;
+            p[1] = t.y;
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < per; j += 4) {
+                const uint4 t = *reinterpret_cast<const uint4*>(pos + e0 + j);
+                p[j] = t.x;
+                p[j + 1] = t.y;
+                p[j + 2] = t.z;
+                p[j + 3] = t.w;
+            }
+        }
+        bool outside = false;
+        if constexpr (INDEXED) {
+#pragma unroll
+            for (uint32_t j = 0; j < per; ++j) outside |= p[j] == kPosGlobal;
+        }
+        uint4 q;
+        uint8_t* b = reinterpret_cast<uint8_t*>(&q);
+        if (!outside) {
+#pragma unroll
+            for (uint32_t j = 0; j < per; ++j) {
+                const bool in = p[j] < kPosGlobal;
+                const uint64_t g = lds_get<S>(img, in ? p[j] + off : 0);
+                const uint64_t v = in ? g : 0;
+                __builtin_memcpy(b + j * S, &v, S);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < per; ++j) {
+                const uint64_t v = reply_elem<S, INDEXED>(img, pos, lo, buf, off, e0 + j);
+                __builtin_memcpy(b + j * S, &v, S);
+            }
+        }
+        __builtin_nontemporal_store(r_u32x4{q.x, q.y, q.z, q.w}, reinterpret_cast<r_u32x4*>(dstc) + c);
+    } else {  // the column's last, partial chunk: whole elements, bytewise
+        for (uint32_t e = e0; e < nr; ++e) {
+            const uint64_t v = reply_elem<S, INDEXED>(img, pos, lo, buf, off, e);
+#pragma unroll
+            for (int k = 0; k < S; ++k) dstc[e * S + k] = static_cast<uint8_t>(v >> (8 * k));
+        }
+    }
+}
+
+template <bool INDEXED>
+__global__ __launch_bounds__(kBlock) void k_unpack_replies(ReplyArgs a, const uint8_t* __restrict__ buf, uint64_t buf_len,
+                                                           const uint32_t* __restrict__ offs, uint64_t n,
+                                                           uint8_t* __restrict__ codes, srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const uint32_t cap = a.R * a.F + 16;  // image bytes a tile may stage (a multiple of 16)
+    const uint32_t p8 = (a.prefix_len + 7) & ~7u;
+    uint8_t* img = lds;
+    uint8_t* tmpl = lds + cap + 16;
+    uint8_t* mask = tmpl + p8;
+    uint32_t* pos = reinterpret_cast<uint32_t*>(mask + p8);
+    uint32_t* lo = pos + a.R;  // indexed mode: the tile's offsets, lo[nr] = its end
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * a.R;
+    const uint32_t nr = static_cast<uint32_t>(min<uint64_t>(a.R, n - base));
+
+    // the plan's prefix without its code byte, as template | mask
+    for (uint32_t i = threadIdx.x; i < p8; i += kBlock) {
+        const bool keep = i < a.prefix_len && i != 4;
+        tmpl[i] = keep ? a.prefix[i] : 0;
+        mask[i] = keep ? 0xff : 0;
+    }
+    uint64_t s0;       // stream offset of the image's first byte (a multiple of 16)
+    uint32_t staged;   // image bytes
+    if constexpr (INDEXED) {
+        for (uint32_t j = threadIdx.x; j <= nr; j += kBlock)
+            lo[j] = base + j < n ? offs[base + j] : static_cast<uint32_t>(buf_len);
+        __syncthreads();
+        const uint64_t o0 = lo[0], oe = lo[nr];
+        s0 = o0 & ~15ull;
+        if (o0 > buf_len) {
+            staged = 0;
+        } else {
+            const uint64_t end = oe >= o0 && oe <= buf_len ? oe : buf_len;
+            staged = static_cast<uint32_t>(min<uint64_t>(end - s0, cap));
+        }
+    } else {
+        s0 = base * a.F;
+        staged = s0 >= buf_len ? 0 : static_cast<uint32_t>(min<uint64_t>(buf_len - s0, static_cast<uint64_t>(nr) * a.F));
+    }
+
+    // 1. stream -> image
+    const uint8_t* src = buf + s0;
+    const uint32_t full = staged >> 4;
+    for (uint32_t c0 = threadIdx.x; c0 < full; c0 += kBlock * kReplyLoads) {
+        uint4 vv[kReplyLoads];
+#pragma unroll
+        for (int u = 0; u < kReplyLoads; ++u) {
+            // lanes past the span's end load its last chunk again: every slot is
+            // defined, so the batch stays in registers
+            const uint32_t c = min(c0 + u * kBlock, full - 1);
+            vv[u] = *reinterpret_cast<const uint4*>(src + 16 * c);
+        }
+#pragma unroll
+        for (int u = 0; u < kReplyLoads; ++u) {
+            const uint32_t c = c0 + u * kBlock;
+            if (c < full) *reinterpret_cast<uint4*>(img + 16 * c) = vv[u];
+        }
+    }
+    for (uint32_t i = full * 16 + threadIdx.x; i < staged; i += kBlock) img[i] = src[i];
+    __syncthreads();
+
+    // 2. one lane per frame: code, status, where its fields are
+    for (uint32_t j = threadIdx.x; j < nr; j += kBlock) {
+        uint64_t o, e;
+        if constexpr (INDEXED) {
+            o = lo[j];
+            e = lo[j + 1];
+        } else {
+            o = s0 + static_cast<uint64_t>(j) * a.F;
+            e = o + a.F;
+        }
+        uint32_t code = SRPC_REPLY_NO_CODE, p = kPosZero, flag = 0;
+        if (!(o <= e && e <= buf_len) || e - o < 5) {
+            flag = SRPC_STATUS_BOUNDS;  // out of order, past the end, no header or no payload
+        } else {
+            const uint64_t len = e - o;
+            const uint64_t need = len == a.F ? len : 5;
+            const bool in_img = o >= s0 && o - s0 + need <= staged;
+            const uint32_t q = static_cast<uint32_t>(o - s0);
+            const uint8_t* h = in_img ? img + q : buf + o;
+            const uint32_t be = be32_at(h), c0 = h[4];
+            if (be != len - 4) {
+                flag = SRPC_STATUS_BOUNDS;
+            } else {
+                code = c0;
+                if (len == a.F) {
+                    bool eq = true;
+                    if (in_img) {
+                        for (uint32_t b = 0; b < p8; b += 8)
+                            eq &= ((lds_u64(img, q + b) ^ *reinterpret_cast<const uint64_t*>(tmpl + b)) &
+                                   *reinterpret_cast<const uint64_t*>(mask + b)) == 0;
+                    } else {
+                        for (uint32_t b = 0; b < a.prefix_len; ++b) eq &= ((buf[o + b] ^ tmpl[b]) & mask[b]) == 0;
+                    }
+                    if (eq) p = in_img ? q : kPosGlobal;
+                    else flag = SRPC_STATUS_PREFIX;
+                } else if (!(len == 5 && c0 != 0)) {  // not a bare error frame either
+                    flag = SRPC_STATUS_PREFIX;
+                }
+            }
+        }
+        pos[j] = p;
+        codes[base + j] = static_cast<uint8_t>(code);
+        if (flag && st) report_bad(st, flag, base + j);
+    }
+    __syncthreads();
+
+    // 3. image -> columns
+    for (uint32_t f = 0; f < a.nfields; ++f) {
+        const uint32_t s = a.size[f];
+        uint8_t* dstc = a.col[f] + base * s;
+        const uint32_t nchunks = (nr * s + 15) >> 4;
+        for (uint32_t c = threadIdx.x; c < nchunks; c += kBlock) {
+            switch (s) {
+            case 1: reply_chunk<1, INDEXED>(img, pos, lo, buf, a.off[f], c, nr, dstc); break;
+            case 2: reply_chunk<2, INDEXED>(img, pos, lo, buf, a.off[f], c, nr, dstc); break;
+            case 4: reply_chunk<4, INDEXED>(img, pos, lo, buf, a.off[f], c, nr, dstc); break;
+            default: reply_chunk<8, INDEXED>(img, pos, lo, buf, a.off[f], c, nr, dstc); break;
+            }
+        }
+    }
+}
+
+__global__ void k_reset_status(srpc_unpack_status* st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        st->flags = 0;
+        st->reserved = 0;
+        st->first_bad_record = ~0ull;
+    }
+}
+
 }  // namespace
 }  // namespace srpc_impl
 
@@ -372,6 +638,54 @@ int srpc_frames_offsets(const srpc_plan* const* req_plans, const uint32_t* resp_
     }
     xscan(static_cast<const uint32_t*>(sizes), nframes, part, d_total, d_out_off, s);
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_replies_per_tile(const srpc_plan* reply_plan, uint32_t* out) {
+    if (!reply_plan || !out) return SRPC_E_INVALID;
+    if (reply_plan->has_string || reply_plan->prefix_len < 5) return SRPC_E_UNSUPPORTED;
+    *out = reply_tile_frames(static_cast<uint32_t>(reply_plan->stride));
+    return SRPC_OK;
+}
+
+int srpc_frames_unpack_replies(const srpc_plan* reply_plan, const uint8_t* d_buf, uint64_t buf_len,
+                               const uint32_t* d_offs, uint64_t nframes, void* const* d_cols, uint8_t* d_codes,
+                               srpc_unpack_status* d_status, void* stream) {
+    const TimedCall timed;
+    // the outputs and the length are checked before the plan is looked at
+    if (!reply_plan || !d_cols || !d_codes || buf_len >= (1ull << 32)) return SRPC_E_INVALID;
+    const srpc_plan* p = reply_plan;
+    if (p->has_string || p->prefix_len < 5) return SRPC_E_UNSUPPORTED;
+    if (nframes > 0xffffffffull) return SRPC_E_UNSUPPORTED;
+    if (nframes && !d_buf) return SRPC_E_INVALID;
+    if (!aligned(d_buf, 16)) return SRPC_E_ALIGN;
+    for (uint32_t f = 0; nframes && f < p->nfields; ++f) {
+        if (!d_cols[f]) return SRPC_E_INVALID;
+        if (!aligned(d_cols[f], 16)) return SRPC_E_ALIGN;
+    }
+    auto s = static_cast<hipStream_t>(stream);
+    if (d_status) {
+        hipLaunchKernelGGL(k_reset_status, dim3(1), dim3(64), 0, s, d_status);
+        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
+    }
+    if (!nframes) return SRPC_OK;
+    ReplyArgs a{};
+    for (uint32_t f = 0; f < p->nfields; ++f) {
+        a.col[f] = static_cast<uint8_t*>(d_cols[f]);
+        a.size[f] = p->size[f];
+        a.off[f] = p->off[f];
+    }
+    a.prefix = p->d_prefix;
+    a.nfields = p->nfields;
+    a.F = static_cast<uint32_t>(p->stride);
+    a.prefix_len = p->prefix_len;
+    a.R = reply_tile_frames(a.F);
+    const uint32_t grid = static_cast<uint32_t>((nframes + a.R - 1) / a.R);
+    const size_t lds = reply_lds_bytes(a.F, a.prefix_len, a.R, d_offs != nullptr);
+    if (d_offs) launch(k_unpack_replies<true>, dim3(grid), dim3(kBlock), lds, s, a, d_buf, buf_len, d_offs, nframes, d_codes, d_status);
+    else launch(k_unpack_replies<false>, dim3(grid), dim3(kBlock), lds, s, a, d_buf, buf_len, d_offs, nframes, d_codes, d_status);
+    if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
+    // uniform mode, a stream shorter than nframes full frames: as srpc_gpu_unpack
+    return !d_offs && buf_len / a.F < nframes ? SRPC_ERR_BOUNDS : SRPC_OK;
 }
 
 }  // extern "C"

@@ -176,6 +176,27 @@ class GpuPacker:
                                                 _dptr(status), _stream(stream)),
                      "srpc_gpu_unpack")
 
+    # -- framed reply streams (client side) ----------------------------------
+    def unpack_replies(self, buf, buf_len: int, offs, nframes: int, cols: Sequence, codes, status=None,
+                       stream=None) -> int:
+        """Decode a reply stream of mixed frames in call order (async): this
+        plan's prefix is a framed response prefix (``framed_response_prefix``).
+        ``offs``: nframes u32 device offsets of the frames, or None when every
+        frame is full size (uniform mode).  ``codes``: nframes device bytes,
+        one status code per call (SRPC_REPLY_NO_CODE where none could be read).
+        Returns SRPC_OK or SRPC_ERR_BOUNDS."""
+        arr = self._cols(cols)
+        return check(_lib.lib().srpc_frames_unpack_replies(self._h, _dptr(buf), buf_len, _dptr(offs), nframes, arr,
+                                                           _dptr(codes), _dptr(status), _stream(stream)),
+                     "srpc_frames_unpack_replies")
+
+    @property
+    def replies_per_tile(self) -> int:
+        """Frames one workgroup of unpack_replies takes (testing hook)."""
+        out = C.c_uint32()
+        check(_lib.lib().srpc_frames_replies_per_tile(self._h, C.byref(out)), "srpc_frames_replies_per_tile")
+        return out.value
+
     # -- host-terminated batches (ABI 7) ---------------------------------------
     def host_scratch_bytes(self, chunk_records: int, depth: int = 3) -> int:
         out = C.c_uint64()

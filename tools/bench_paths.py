@@ -108,6 +108,127 @@ def main():
                      "unpack_GBps": round(alg / tu / 1e9, 1), "pack_frac": round(alg / tp / 8e12, 4),
                      "unpack_frac": round(alg / tu / 8e12, 4), "parity_ok": bool(ok), **generic})
 
+    def spread(ts):
+        return {"median_us": round(statistics.median(ts) * 1e6, 2), "min_us": round(min(ts) * 1e6, 2),
+                "max_us": round(max(ts) * 1e6, 2)}
+
+    def replies_case(name, sch, n):
+        """Reply streams of n frames decoded in call order (srpc_frames_unpack_replies):
+        uniform mode, indexed mode on the same all-full stream, indexed mode with
+        1 % bare error frames.  Algorithmic bytes: frame bytes + column bytes +
+        1 code byte (+ 4 offset bytes when indexed) per frame.  Beside them,
+        srpc_gpu_unpack of the same all-success bytes, and the route the call
+        replaces on the all-full indexed stream (srpc_frames_classify + _gather +
+        srpc_gpu_unpack), timed alternately with the new call on stream events."""
+        if args.only not in name:
+            return
+        from srpc_amd import FrameClassifier, framed_response_prefix
+        pre = framed_response_prefix(sch, 0)
+        p = GpuPacker(sch, pre)
+        F = p.record_bytes
+        rng = np.random.default_rng(2)
+        cols = []
+        for k in sch.kinds:
+            dt = np.dtype(oracle.KIND_DTYPE[k])
+            c = rng.integers(0, 256, n * dt.itemsize, dtype=np.uint8).view(dt)
+            cols.append((c & 1).astype(np.uint8) if k == oracle.BOOL else c)
+        dcols = [t_u8(c) for c in cols]
+        col_bytes = sum(c.nbytes for c in cols)
+        wire = torch.empty(n * F + 16, dtype=torch.uint8, device=dev)
+        p.pack(dcols, n, wire, stream=s)
+        torch.cuda.synchronize()
+        m = 4096
+        opre = (len(pre) - 4 + sch.body_bytes).to_bytes(4, "big") + oracle.response_prefix(0, sch.name)
+        made_ok = wire[: m * F].cpu().numpy().tobytes() == oracle.pack(sch.kinds, [c[:m] for c in cols], m, opre)
+        back = [torch.empty_like(c) for c in dcols]
+        codes = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        st = torch.zeros(16, dtype=torch.uint8, device=dev)
+
+        def clear():
+            for b in back:
+                b.fill_(0xA5)
+            codes.fill_(0xA5)
+
+        def same(want_cols, want_codes):
+            torch.cuda.synchronize()
+            return (all(torch.equal(a, b) for a, b in zip(want_cols, back)) and torch.equal(codes[:n], want_codes)
+                    and not bool(st[:4].any()))
+
+        def row(mode, alg, t, ok, **extra):
+            rows.append({"case": f"{name}_{mode}", "replies": True, "frames": n, "frame_bytes": F, "alg_bytes": alg,
+                         "us": round(t * 1e6, 2), "GBps": round(alg / t / 1e9, 1), "frac": round(alg / t / 8e12, 4),
+                         "parity_ok": bool(ok), **extra})
+
+        zeros = torch.zeros(n, dtype=torch.uint8, device=dev)
+        # uniform mode, beside srpc_gpu_unpack of the same bytes
+        clear()
+        p.unpack_replies(wire, n * F, None, n, back, codes, st, stream=s)
+        ok = made_ok and same(dcols, zeros)
+        t = timeit(lambda: p.unpack_replies(wire, n * F, None, n, back, codes, st, stream=s))
+        tu = timeit(lambda: p.unpack(wire, n * F, n, back, stream=s))
+        alg_u = n * F + col_bytes
+        row("uniform", alg_u + n, t, ok, unpack_us=round(tu * 1e6, 2), unpack_alg_bytes=alg_u,
+            unpack_frac=round(alg_u / tu / 8e12, 4), time_per_byte_vs_unpack=round((t / (alg_u + n)) / (tu / alg_u), 4))
+        # indexed mode, all frames full; the route it replaces, alternately
+        offs = (torch.arange(n, dtype=torch.int64, device=dev) * F).to(torch.int32).contiguous()
+        clear()
+        p.unpack_replies(wire, n * F, offs, n, back, codes, st, stream=s)
+        ok = made_ok and same(dcols, zeros)
+        t = timeit(lambda: p.unpack_replies(wire, n * F, offs, n, back, codes, st, stream=s))
+        fc = FrameClassifier([(p, 0)])
+        sb = fc.scratch_bytes(n)
+        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        d_cls = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        d_idx = torch.empty(4 * n + 16, dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(8 * 3, dtype=torch.uint8, device=dev)
+        d_out_off = torch.empty(8 * (n + 1), dtype=torch.uint8, device=dev)
+        gathered = torch.empty(n * F + 16, dtype=torch.uint8, device=dev)
+
+        def route():
+            fc.classify(wire, n * F, offs, n, d_cls, d_idx, d_counts, d_out_off, scratch, sb, stream=s)
+            fc.gather(wire, offs, d_idx, n, F, gathered, stream=s)
+            p.unpack(gathered, n * F, n, back, stream=s)
+
+        def ev(fn):
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / 1e3
+
+        new = lambda: p.unpack_replies(wire, n * F, offs, n, back, codes, st, stream=s)  # noqa: E731
+        for _ in range(3):
+            route()
+            new()
+        t_new, t_route = [], []
+        for _ in range(args.reps):
+            t_new.append(ev(new))
+            t_route.append(ev(route))
+        row("indexed_full", alg_u + 5 * n, t, ok, ab_new=spread(t_new), ab_route=spread(t_route))
+        # indexed mode, 1 % bare `BE32(1) | code 1` frames
+        fr = wire[: n * F].cpu().numpy().reshape(n, F).copy()
+        bare = rng.random(n) < 0.01
+        fr[bare, :5] = np.array([0, 0, 0, 1, 1], np.uint8)
+        keep = np.ones((n, F), bool)
+        keep[bare, 5:] = False
+        mixed = fr[keep]
+        del fr, keep
+        lens = np.where(bare, 5, F).astype(np.int64)
+        o = np.zeros(n, np.int64)
+        np.cumsum(lens[:-1], out=o[1:])
+        d_mixed = torch.empty(mixed.size + 16, dtype=torch.uint8, device=dev)
+        d_mixed[: mixed.size].copy_(torch.from_numpy(mixed))
+        d_o = torch.from_numpy(o.astype(np.uint32).view(np.int32)).to(dev)
+        d_bare = torch.from_numpy(bare).to(dev)
+        want_cols = [torch.where(d_bare.repeat_interleave(c.numel() // n), torch.zeros_like(c), c) for c in dcols]
+        clear()
+        p.unpack_replies(d_mixed, mixed.size, d_o, n, back, codes, st, stream=s)
+        ok = made_ok and same(want_cols, d_bare.to(torch.uint8))
+        t = timeit(lambda: p.unpack_replies(d_mixed, mixed.size, d_o, n, back, codes, st, stream=s))
+        row("indexed_1pct_bare", mixed.size + col_bytes + 5 * n, t, ok)
+
     def aos_case(name, sch, n, vptr=True):
         """Records as C-aligned structs behind an 8-byte vtable slot (a C++
         std::vector<T> of srpc messages copied to the device; vptr=False: a
@@ -264,6 +385,9 @@ def main():
     fixed_case("subtract_request_63B_16M", two, N,
                srpc_amd.request_prefix("Calculator_servicer::subtract", "TwoNumbers"))
     fixed_case("two_numbers_response_23B_16M", two, N, srpc_amd.response_prefix(0, "TwoNumbers"))
+    replies_case("number_replies_23B_16M", NUMBER, N)
+    replies_case("all_kinds_replies_39B_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
+                                                        ("d", "int16"), ("e", "int32"), ("f", "int64")), N)
     aos_case("quad_aos_16M", QUAD, N)
     aos_case("quad_aos_plain_16M", QUAD, N, vptr=False)
     aos_case("all_kinds_aos_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
@@ -281,6 +405,18 @@ def main():
         with open(args.out, "w") as f:
             f.write(txt)
     for r in rows:
+        if r.get("replies"):
+            extra = ""
+            if "unpack_us" in r:
+                extra += (f'  srpc_gpu_unpack {r["unpack_us"]:9.1f} us ({r["unpack_frac"]:.3f})'
+                          f'  time/byte vs unpack {r["time_per_byte_vs_unpack"]:.3f}')
+            if "ab_new" in r:
+                extra += (f'  events: new {r["ab_new"]["median_us"]:.1f} us [{r["ab_new"]["min_us"]:.1f}, '
+                          f'{r["ab_new"]["max_us"]:.1f}]  classify+gather+unpack {r["ab_route"]["median_us"]:.1f} us '
+                          f'[{r["ab_route"]["min_us"]:.1f}, {r["ab_route"]["max_us"]:.1f}]')
+            print(f'{r["case"]:44s} replies {r["us"]:9.1f} us {r["GBps"]:7.1f} GB/s ({r["frac"]:.3f})  '
+                  f'parity={r["parity_ok"]}{extra}')
+            continue
         extra = f'  stream {r["stream_us"]:8.1f} us ({r["stream_frac"]:.3f})' if "stream_us" in r else ""
         for k in ("tiled_ok", "stream_ok"):
             if k in r and not r[k]:
