@@ -20,8 +20,16 @@
 // its uniform mode and reads no offsets.  Calls the peer never answers (it
 // closed the connection, or the wait timed out) get RPC_ERR_RECV_TIMEOUT and
 // zero fields; every later call on this client is then unanswered too.
-// Fixed-size Req and Resp only: string schemas throw plan_error
-// (SRPC_E_UNSUPPORTED).
+//
+// `call` takes fixed-size Req and Resp (string schemas throw plan_error
+// SRPC_E_UNSUPPORTED).  `call_var` takes methods whose request and/or response
+// has std::string members, with the columns of batch_server's var_batch: a
+// string request batch is packed by srpc_gpu_pack_var (prefix `str(method) |
+// str(Req::name)`) and framed by srpc_frames_frame_var; a string reply stream
+// is decoded by srpc_frames_unpack_replies_var (reply plan: the unframed `u8
+// code | str(Resp::name)`) into the client's staging, and its chars reach the
+// caller's columns only once their total is known to fit.  A side without
+// strings takes `call`'s path.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -39,6 +47,7 @@
 #include <vector>
 
 #include "frame_walk.hpp"
+#include "reply_walk.hpp"
 #include "gpu.hpp"
 #include "gpu_server.hpp"  // raw_plan, framed_request_prefix, framed_response_prefix
 
@@ -57,6 +66,14 @@ struct call_stats {
     double send_seconds = 0;  // in send()
     double recv_seconds = 0;  // in poll() and recv()
     double gpu_seconds = 0;   // pack + D2H, H2D + decode + the codes' D2H, host-timed per chunk
+};
+
+/// Sizing of call_var's staging, per call (the batch average): the send
+/// buffer holds max_batch * max_request_bytes + 4096 bytes of request frames,
+/// the receive buffer max_batch * max_reply_bytes + 4096 of reply frames.
+struct var_call_limits {
+    uint64_t max_request_bytes = 512;
+    uint64_t max_reply_bytes = 512;
 };
 
 class batch_client {
@@ -135,7 +152,7 @@ public:
             }
             check(hipStreamSynchronize(stream));
             st.gpu_seconds += secs(t0);
-            if (nf) count(e, w, st);
+            if (nf) count(e.fout, e.resp_prefix, w, st);
             if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
             // bytes after the chunk's last frame belong to the next chunk's replies
             std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
@@ -179,6 +196,216 @@ public:
         return res;
     }
 
+    /// n calls of a method whose Req and/or Resp has string fields.  The
+    /// columns follow var_batch (gpu_server.hpp): a fixed field is n values, a
+    /// string field its chars back to back plus n+1 u64 offsets
+    /// (d_req_str_offs[f] / d_resp_str_offs[f], nullptr for fixed fields).
+    /// resp_cap[f]: bytes of response column f.  The reply's string offsets
+    /// are absolute over the whole call ([0] = 0, chunk k continuing from chunk
+    /// k - 1's total).  Calls the peer never answers get RPC_ERR_RECV_TIMEOUT,
+    /// zero fields and empty strings.  Throws plan_error(SRPC_E_CAPACITY) when
+    /// a chunk's request frames outgrow the send buffer (before anything of the
+    /// chunk is sent) or when the reply chars of a chunk do not fit resp_cap[f]
+    /// (after the chunk is received; nothing past the cap is written).
+    /// The request hook sees bytes-per-frame 0 for string requests: the frames
+    /// are found by their BE32s.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    call_stats call_var(std::string const& method, void* const* d_req_cols, const uint64_t* const* d_req_str_offs,
+                        uint64_t n, void* const* d_resp_cols, uint64_t* const* d_resp_str_offs,
+                        const uint64_t* resp_cap, uint8_t* d_codes, var_call_limits lim = {},
+                        hipStream_t stream = nullptr) {
+        check(hipSetDevice(_dev));
+        var_entry& e = var_plans<Req, Resp>(method);
+        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
+        for (size_t f = 0; f < ns; ++f)
+            if (e.resp_size[f] && n * e.resp_size[f] > resp_cap[f])
+                throw plan_error("batch_client::call_var (response column)", SRPC_E_CAPACITY);
+        ensure_bytes(_max * (e.req_var ? lim.max_request_bytes : e.fin) + 4096,
+                     _max * (e.resp_var ? lim.max_reply_bytes : e.fout) + 4096);
+        ensure_var(e);
+        call_stats st;
+        st.calls = n;
+        std::vector<const void*> rq(nq);
+        std::vector<const uint64_t*> rqo(nq, nullptr);
+        std::vector<void*> rs(ns);
+        std::vector<uint64_t*> rso(ns, nullptr);
+        std::vector<uint64_t> base(ns, 0);  // chars of response field f in the chunks before this one
+        for (uint64_t lo = 0; lo < n; lo += _max) {
+            const uint64_t m = std::min(_max, n - lo);
+            st.chunks += 1;
+            uint64_t total = 0;  // the chunk's request bytes
+            if (!_eof) {
+                auto t0 = clock::now();
+                for (size_t f = 0; f < nq; ++f) {
+                    const bool str = e.req_size[f] == 0;
+                    // a string column's offsets are absolute: its chars stay where they are
+                    rq[f] = str ? d_req_cols[f] : static_cast<const uint8_t*>(d_req_cols[f]) + lo * e.req_size[f];
+                    rqo[f] = str ? d_req_str_offs[f] + lo : nullptr;
+                }
+                if (e.req_var) {
+                    check_srpc(srpc_gpu_pack_var(e.req->get(), rq.data(), rqo.data(), m, _d_wire, _out_cap, _d_rec,
+                                                 _d_status, _d_vscratch, _vscratch_cap, stream),
+                               "srpc_gpu_pack_var");
+                    check_srpc(srpc_frames_frame_var(_d_wire, _d_rec, m, _d_out, _out_cap, _d_status, stream),
+                               "srpc_frames_frame_var");
+                    check(hipMemcpyAsync(_h_ends, _d_rec + m, 8, hipMemcpyDeviceToHost, stream));
+                    check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+                    check(hipStreamSynchronize(stream));
+                    total = _h_ends[0] + 4 * m;
+                    if (total > _out_cap || _h_status->flags)
+                        throw plan_error("batch_client::call_var (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
+                } else {
+                    total = m * e.fin;
+                    check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _d_out, total, stream), "srpc_gpu_pack");
+                }
+                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
+                check(hipStreamSynchronize(stream));
+                st.gpu_seconds += secs(t0);
+                if (_hook) _hook(_h_out, lo, m, e.req_var ? 0 : e.fin);
+            }
+            const frame_walk w = exchange(m, total, e.resp_var ? 0 : e.fout, st);
+            auto t0 = clock::now();
+            const uint64_t nf = w.nframes;
+            for (size_t f = 0; f < ns; ++f) {
+                const bool str = e.resp_size[f] == 0;
+                // string fields are decoded into the client's staging first
+                rs[f] = str ? static_cast<void*>(_d_schars[e.resp_sidx[f]])
+                            : static_cast<uint8_t*>(d_resp_cols[f]) + lo * e.resp_size[f];
+                rso[f] = str ? _d_soffs[e.resp_sidx[f]] : nullptr;
+            }
+            if (nf) {
+                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
+                const bool uniform = !e.resp_var && w.all_full;
+                if (!uniform) check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+                st.uniform_chunks += uniform;
+                if (e.resp_var) {
+                    check_srpc(srpc_frames_unpack_replies_var(e.resp->get(), _d_in, w.walked, _d_offs, nf, rs.data(),
+                                                              rso.data(), d_codes + lo, _d_status, _d_vscratch,
+                                                              _vscratch_cap, stream),
+                               "srpc_frames_unpack_replies_var");
+                    for (uint32_t t = 0; t < e.resp_nstr; ++t)
+                        check(hipMemcpyAsync(_h_soffs + t * (_max + 1), _d_soffs[t], 8 * (nf + 1), hipMemcpyDeviceToHost,
+                                             stream));
+                } else {
+                    check_srpc(srpc_frames_unpack_replies(e.resp->get(), _d_in, w.walked, uniform ? nullptr : _d_offs,
+                                                          nf, rs.data(), d_codes + lo, _d_status, stream),
+                               "srpc_frames_unpack_replies");
+                }
+                check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+                check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            }
+            if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields (empty strings: below)
+                check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
+                for (size_t f = 0; f < ns; ++f)
+                    if (e.resp_size[f])
+                        check(hipMemsetAsync(static_cast<uint8_t*>(rs[f]) + nf * e.resp_size[f], 0,
+                                             (m - nf) * e.resp_size[f], stream));
+                st.unanswered += m - nf;
+            }
+            check(hipStreamSynchronize(stream));
+            // the chunk's chars, now that their totals are known: they must fit
+            // the caller's columns before a byte of them is written there
+            bool overflow = false;
+            for (size_t f = 0; f < ns; ++f) {
+                if (e.resp_size[f]) continue;
+                const uint32_t t = e.resp_sidx[f];
+                uint64_t* ho = _h_soffs + t * (_max + 1);
+                const uint64_t chars = nf ? ho[nf] : 0;
+                if (chars > resp_cap[f] || base[f] > resp_cap[f] - chars) {
+                    overflow = true;  // thrown once the chunk's bytes are accounted for
+                    continue;
+                }
+                if (chars)
+                    check(hipMemcpyAsync(static_cast<uint8_t*>(d_resp_cols[f]) + base[f], _d_schars[t], chars,
+                                         hipMemcpyDeviceToDevice, stream));
+                // absolute offsets; unanswered calls are empty strings at the chunk's end
+                if (!nf) ho[0] = 0;
+                for (uint64_t j = 0; j <= nf; ++j) ho[j] += base[f];
+                for (uint64_t j = nf + 1; j <= m; ++j) ho[j] = base[f] + chars;
+                check(hipMemcpyAsync(d_resp_str_offs[f] + lo, ho, 8 * (m + 1), hipMemcpyHostToDevice, stream));
+                base[f] += chars;
+            }
+            if (e.resp_var) check(hipStreamSynchronize(stream));
+            st.gpu_seconds += secs(t0);
+            if (nf) {
+                if (e.resp_var) count_var(e, w, st);
+                else count(e.fout, e.resp_prefix, w, st);
+            }
+            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
+            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
+            _have -= w.walked;
+            if (overflow) {
+                _last = st;
+                throw plan_error("batch_client::call_var (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
+            }
+        }
+        if (!n) {  // no chunk ran: the offsets of no calls
+            for (size_t f = 0; f < ns; ++f)
+                if (!e.resp_size[f]) check(hipMemsetAsync(d_resp_str_offs[f], 0, 8, stream));
+            check(hipStreamSynchronize(stream));
+        }
+        _last = st;
+        return st;
+    }
+
+    /// The same from and to host records (host_columns<T> transposes them,
+    /// strings included).  A response string column is given room for every
+    /// reply byte the limits allow.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    std::vector<response_t<Resp>> call_var(std::string const& method, std::vector<Req> const& reqs,
+                                           var_call_limits lim = {}) {
+        check(hipSetDevice(_dev));
+        var_entry& e = var_plans<Req, Resp>(method);
+        const uint64_t n = reqs.size();
+        host_columns<Req> in;
+        in.scatter(reqs);
+        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
+        device_allocs mem;
+        std::vector<void*> rq(nq), rs(ns);
+        std::vector<const uint64_t*> rqo(nq, nullptr);
+        std::vector<uint64_t*> rso(ns, nullptr);
+        std::vector<uint64_t> cap(ns);
+        for (size_t f = 0; f < nq; ++f) {
+            rq[f] = mem.add(in.col[f].size());
+            if (!in.col[f].empty()) check(hipMemcpy(rq[f], in.col[f].data(), in.col[f].size(), hipMemcpyHostToDevice));
+            if (e.req_size[f]) continue;
+            uint64_t* o = static_cast<uint64_t*>(mem.add(8 * (n + 1)));
+            check(hipMemcpy(o, in.offs[f].data(), 8 * (n + 1), hipMemcpyHostToDevice));
+            rqo[f] = o;
+        }
+        for (size_t f = 0; f < ns; ++f) {
+            cap[f] = e.resp_size[f] ? n * e.resp_size[f] : n * lim.max_reply_bytes + 4096;
+            rs[f] = mem.add(cap[f]);
+            if (!e.resp_size[f]) rso[f] = static_cast<uint64_t*>(mem.add(8 * (n + 1)));
+        }
+        uint8_t* d_codes = static_cast<uint8_t*>(mem.add(n));
+        call_var<Req, Resp>(method, rq.data(), rqo.data(), n, rs.data(), rso.data(), cap.data(), d_codes, lim);
+        host_columns<Resp> out;
+        out.n = n;
+        out.col.resize(ns);
+        out.offs.resize(ns);
+        for (size_t f = 0; f < ns; ++f) {
+            uint64_t bytes = n * e.resp_size[f];
+            if (!e.resp_size[f]) {
+                out.offs[f].resize(n + 1);
+                check(hipMemcpy(out.offs[f].data(), rso[f], 8 * (n + 1), hipMemcpyDeviceToHost));
+                bytes = out.offs[f][n];
+            }
+            out.col[f].resize(bytes);
+            if (bytes) check(hipMemcpy(out.col[f].data(), rs[f], bytes, hipMemcpyDeviceToHost));
+        }
+        std::vector<uint8_t> codes(n);
+        if (n) check(hipMemcpy(codes.data(), d_codes, n, hipMemcpyDeviceToHost));
+        std::vector<Resp> vals;
+        out.gather(vals);
+        std::vector<response_t<Resp>> res(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            res[i].set_code(static_cast<rpc_status_code>(codes[i]));
+            res[i].set_value(vals[i]);
+        }
+        return res;
+    }
+
 private:
     using clock = std::chrono::steady_clock;
     struct entry {
@@ -206,6 +433,35 @@ private:
             for (void* d : p) (void)hipFree(d);
             p.clear();
         }
+    };
+
+    /// Device allocations of one host-form call, freed together.
+    struct device_allocs {
+        std::vector<void*> p;
+        device_allocs() = default;
+        device_allocs(device_allocs const&) = delete;
+        device_allocs& operator=(device_allocs const&) = delete;
+        ~device_allocs() {
+            for (void* d : p) (void)hipFree(d);
+        }
+        void* add(uint64_t bytes) {
+            void* d = nullptr;
+            if (hipMalloc(&d, bytes + 16) != hipSuccess) throw plan_error("batch_client: hipMalloc", SRPC_E_HIP);
+            p.push_back(d);
+            return d;
+        }
+    };
+    /// A method of call_var: each side is a string plan (unframed prefix) or,
+    /// without strings, the framed fixed plan `call` uses.
+    struct var_entry {
+        std::unique_ptr<raw_plan> req, resp;
+        bool req_var = false, resp_var = false;
+        uint64_t fin = 0, fout = 0;                 // fixed sides: request / full reply frame bytes
+        std::vector<uint64_t> req_size, resp_size;  // leaf bytes, 0: a string
+        std::vector<uint32_t> resp_sidx;            // string leaves: which string field of Resp
+        std::vector<uint8_t> resp_leaf;             // resp_size as bytes, for walk_reply_var
+        uint32_t resp_nstr = 0;
+        std::vector<uint8_t> resp_prefix;           // framed (fixed Resp) or `code | str(Resp::name)`
     };
 
     static double secs(clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); }
@@ -239,11 +495,84 @@ private:
         return _plans.emplace(key, std::move(e)).first->second;
     }
 
+    template <SrpcMessage Req, SrpcMessage Resp>
+    var_entry& var_plans(std::string const& method) {
+        const std::string key = method + '\0' + Req::name + '\0' + Resp::name;
+        auto it = _vplans.find(key);
+        if (it != _vplans.end()) return it->second;
+        const std::vector<int32_t> kq = flat_kinds<Req>(), ks = flat_kinds<Resp>();
+        var_entry e;
+        for (int32_t k : kq) e.req_var = e.req_var || k == SRPC_KIND_STRING;
+        for (int32_t k : ks) e.resp_var = e.resp_var || k == SRPC_KIND_STRING;
+        e.resp_prefix = e.resp_var ? response_prefix<Resp>(RPC_SUCCESS) : framed_response_prefix<Resp>(RPC_SUCCESS);
+        e.req = std::make_unique<raw_plan>(kq, e.req_var ? request_prefix<Req>(method) : framed_request_prefix<Req>(method),
+                                           _dev);
+        e.resp = std::make_unique<raw_plan>(ks, e.resp_prefix, _dev);
+        e.fin = e.req->record_bytes();
+        e.fout = e.resp->record_bytes();
+        Req rq{};
+        for_each_leaf<Req>(rq, [&](const auto& v) {
+            using F = std::remove_cvref_t<decltype(v)>;
+            e.req_size.push_back(std::is_same_v<F, std::string> ? 0 : sizeof(F));
+        });
+        Resp rs{};
+        for_each_leaf<Resp>(rs, [&](const auto& v) {
+            using F = std::remove_cvref_t<decltype(v)>;
+            const bool str = std::is_same_v<F, std::string>;
+            e.resp_size.push_back(str ? 0 : sizeof(F));
+            e.resp_leaf.push_back(static_cast<uint8_t>(str ? 0 : sizeof(F)));
+            e.resp_sidx.push_back(str ? e.resp_nstr++ : 0);
+        });
+        if (e.resp_nstr > SRPC_FRAMES_MAX_STRINGS) throw plan_error("batch_client::call_var", SRPC_E_UNSUPPORTED);
+        return _vplans.emplace(key, std::move(e)).first->second;
+    }
+
+    /// call_var's own staging beside ensure_bytes': the packed records before
+    /// they are framed, the scratch of the var calls, and per response string
+    /// field the chars and offsets a chunk is decoded into.
+    void ensure_var(var_entry const& e) {
+        uint64_t need = 0, b = 0;
+        if (e.req_var) {
+            check_srpc(srpc_plan_var_scratch_bytes(e.req->get(), _max, _out_cap, &b), "srpc_plan_var_scratch_bytes");
+            need = std::max(need, b);
+        }
+        if (e.resp_var) {
+            check_srpc(srpc_frames_replies_var_scratch_bytes(e.resp->get(), _max, &b),
+                       "srpc_frames_replies_var_scratch_bytes");
+            need = std::max(need, b);
+        }
+        if (need > _vscratch_cap) {
+            (void)hipFree(_d_vscratch);
+            _d_vscratch = nullptr;
+            _vscratch_cap = 0;
+            check(hipMalloc(&_d_vscratch, need));
+            _vscratch_cap = need;
+        }
+        if (e.req_var && !_d_wire) {
+            check(hipMalloc(reinterpret_cast<void**>(&_d_wire), _out_cap + 16));
+            check(hipMalloc(reinterpret_cast<void**>(&_d_rec), 8 * (_max + 1) + 16));
+        }
+        if (!_h_ends) check(hipHostMalloc(reinterpret_cast<void**>(&_h_ends), 64));
+        if (e.resp_nstr > _d_schars.size() && _h_soffs) {
+            (void)hipHostFree(_h_soffs);
+            _h_soffs = nullptr;
+        }
+        while (_d_schars.size() < e.resp_nstr) {
+            void *c = nullptr, *o = nullptr;
+            check(hipMalloc(&c, _in_cap + 16));
+            _d_schars.push_back(static_cast<uint8_t*>(c));
+            check(hipMalloc(&o, 8 * (_max + 1) + 16));
+            _d_soffs.push_back(static_cast<uint64_t*>(o));
+        }
+        if (e.resp_nstr && !_h_soffs)
+            check(hipHostMalloc(reinterpret_cast<void**>(&_h_soffs), 8 * (_max + 1) * _d_schars.size()));
+    }
+
     /// Staging for chunks of _max calls with fin-byte requests and fout-byte
     /// replies.  The receive buffer has room for a chunk of full replies and
     /// 4 KiB more; a peer whose replies outgrow it is treated as closed.
-    void ensure(uint64_t fin, uint64_t fout) {
-        const uint64_t out = _max * fin + 16, in = _max * fout + 4096;
+    void ensure(uint64_t fin, uint64_t fout) { ensure_bytes(_max * fin + 16, _max * fout + 4096); }
+    void ensure_bytes(uint64_t out, uint64_t in) {
         if (out <= _out_cap && in <= _in_cap) return;
         if (in >= (1ull << 32)) throw plan_error("batch_client: max_batch replies pass 4 GiB", SRPC_E_CAPACITY);
         std::vector<uint8_t> carry;
@@ -265,6 +594,20 @@ private:
     }
 
     void release() {
+        // call_var's staging is sized by the same capacities
+        (void)hipFree(_d_wire);
+        (void)hipFree(_d_rec);
+        (void)hipFree(_d_vscratch);
+        (void)hipHostFree(_h_ends);
+        (void)hipHostFree(_h_soffs);
+        for (uint8_t* c : _d_schars) (void)hipFree(c);
+        for (uint64_t* o : _d_soffs) (void)hipFree(o);
+        _d_schars.clear();
+        _d_soffs.clear();
+        _d_wire = nullptr;
+        _d_rec = _h_ends = _h_soffs = nullptr;
+        _d_vscratch = nullptr;
+        _vscratch_cap = 0;
         (void)hipFree(_d_out);
         (void)hipFree(_d_in);
         (void)hipFree(_d_offs);
@@ -329,7 +672,7 @@ private:
 
     /// The chunk's counts from the codes; only a chunk the decode flagged is
     /// looked at frame by frame (the table of include/srpc_gpu.h on the host).
-    void count(entry const& e, frame_walk const& w, call_stats& st) {
+    void count(uint64_t fout, std::vector<uint8_t> const& resp_prefix, frame_walk const& w, call_stats& st) {
         const uint64_t nf = w.nframes;
         if (_h_status->flags == 0) {
             const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
@@ -340,11 +683,31 @@ private:
         for (uint64_t i = 0; i < nf; ++i) {
             const uint64_t o = _h_offs[i], end = i + 1 < nf ? _h_offs[i + 1] : w.walked, len = end - o;
             const uint8_t* f = _h_in + o;
-            const bool full = len == e.fout && std::memcmp(f, e.resp_prefix.data(), 4) == 0 &&
-                              std::memcmp(f + 5, e.resp_prefix.data() + 5, e.resp_prefix.size() - 5) == 0;
+            const bool full = len == fout && std::memcmp(f, resp_prefix.data(), 4) == 0 &&
+                              std::memcmp(f + 5, resp_prefix.data() + 5, resp_prefix.size() - 5) == 0;
             const bool bare = len == 5 && f[4] != 0;
             if (!(full || bare)) st.malformed += 1;
             else if (_h_codes[i] == RPC_SUCCESS) st.ok += 1;
+            else st.failed += 1;
+        }
+    }
+
+    /// count for a string reply stream: a flagged chunk is recounted with the
+    /// table of srpc_frames_unpack_replies_var on the host (walk_reply_var).
+    void count_var(var_entry const& e, frame_walk const& w, call_stats& st) {
+        const uint64_t nf = w.nframes;
+        if (_h_status->flags == 0) {
+            const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
+            st.ok += ok;
+            st.failed += nf - ok;
+            return;
+        }
+        for (uint64_t i = 0; i < nf; ++i) {
+            const uint64_t o = _h_offs[i], end = i + 1 < nf ? _h_offs[i + 1] : w.walked;
+            const reply_frame r = walk_reply_var(_h_in + o, end - o, e.resp_prefix.data(), e.resp_prefix.size(),
+                                                 e.resp_leaf.data(), static_cast<uint32_t>(e.resp_leaf.size()));
+            if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
+            else if (r.code == RPC_SUCCESS) st.ok += 1;
             else st.failed += 1;
         }
     }
@@ -363,6 +726,14 @@ private:
     uint8_t *_d_out = nullptr, *_d_in = nullptr, *_h_out = nullptr, *_h_in = nullptr, *_h_codes = nullptr;
     uint32_t *_d_offs = nullptr, *_h_offs = nullptr;
     srpc_unpack_status *_d_status = nullptr, *_h_status = nullptr;
+    // call_var
+    std::map<std::string, var_entry> _vplans;
+    uint8_t* _d_wire = nullptr;
+    uint64_t *_d_rec = nullptr, *_h_ends = nullptr, *_h_soffs = nullptr;
+    void* _d_vscratch = nullptr;
+    uint64_t _vscratch_cap = 0;
+    std::vector<uint8_t*> _d_schars;
+    std::vector<uint64_t*> _d_soffs;
 };
 
 }  // namespace srpc::gpu

@@ -504,6 +504,89 @@ int srpc_frames_unpack_replies(const srpc_plan* reply_plan, const uint8_t* d_buf
 /* Testing hook: frames per workgroup tile for this reply plan. */
 int srpc_frames_replies_per_tile(const srpc_plan* reply_plan, uint32_t* out);
 
+/* ---- framed reply batches with string fields (client side; added within ABI 8) --
+ * The reply stream of a batch of calls to a method whose response has
+ * std::string members (the reference's stub: unpack_response<R> over a string
+ * body, packer.hpp:123-137, 216-222), decoded in call order: one code per call
+ * in d_codes[i], fixed field f in d_cols[f][i], string field f's chars back to
+ * back in d_cols[f] with offsets d_str_offs[f][0..nframes] ([0] = 0).
+ *
+ * reply_plan is a string plan (SRPC_PATH_VAR, at most SRPC_FRAMES_MAX_STRINGS
+ * strings) whose prefix is the UNFRAMED response prefix `u8 code |
+ * str(Resp::name)`; it follows the frame's BE32 (the convention of
+ * srpc_frames_classify for string plans) and its code byte is ignored.  Frame i
+ * is bytes [d_offs[i], end_i) of d_buf (16-byte aligned), end_i = d_offs[i+1],
+ * or buf_len for the last frame.  d_offs is required: frames of varying length
+ * have no uniform mode.  Columns are 16-byte aligned; a string column has room
+ * for buf_len bytes, as for srpc_gpu_unpack_var.  d_str_offs is the host array
+ * srpc_gpu_unpack_var takes (8-byte aligned device pointers, NULL for fixed
+ * fields).
+ *
+ *   frame i                                     d_codes[i]          fixed   strings  status
+ *   offsets out of order, end_i > buf_len,      SRPC_REPLY_NO_CODE  zero    empty    BOUNDS
+ *     shorter than 4 bytes, BE32 != len - 4,
+ *     or an empty payload
+ *   full: the payload starts with the plan's    payload[0]          decoded copied   -
+ *     prefix (code byte excepted) and the walk
+ *     of its fields, each string's u64 length
+ *     read from the frame, ends exactly at end_i
+ *   bare: a payload of one nonzero byte         that byte           zero    empty    -
+ *   the prefix matches, but a field or string   payload[0]          zero    empty    BOUNDS
+ *     runs past end_i, or the walk ends before
+ *     end_i
+ *   anything else with a payload (one shorter   payload[0]          zero    empty    PREFIX
+ *     than the prefix included)
+ *
+ * "Empty" is offs[i+1] == offs[i]: later calls' chars stay packed back to back.
+ * A string length is compared as `len > end - cursor`, so 2^63 or 2^64 - 1
+ * cannot wrap.  *d_status (may be NULL) is reset by the call; first_bad_record
+ * is the smallest flagged i.  With ascending offsets (what walk_frames gives)
+ * the chars of a column total under buf_len.  Offsets out of order can make
+ * full frames overlap and their chars total more: the offsets still count every
+ * full frame, but no byte of a string column at or past buf_len is written.
+ * Properties:
+ *   - no byte outside [d_buf, d_buf + buf_len) is read;
+ *   - no byte of a column is written past its nframes elements, and none of a
+ *     string column past offs[nframes] (the last partial 16-byte chunk is
+ *     written bytewise);
+ *   - the call is stream-ordered and allocates nothing;
+ *   - it waits on nothing on the device: no look-back polling, no STALLED case;
+ *   - the number of launches (a parse pass, one scan of three launches per
+ *     string field, a copy pass, the status reset) does not depend on the data,
+ *     so the call can be captured;
+ *   - work is bounded by buf_len + nframes * (fixed bytes) on any input.
+ * A tile is srpc_frames_replies_var_tile's `frames` consecutive frames, whose
+ * span is staged into an LDS image of `image_bytes`; a frame that does not lie
+ * whole inside the image is parsed from global memory by its lane (the fixed
+ * bytes only) and its chars are copied from global memory 16 output bytes per
+ * lane by the whole workgroup.
+ * Scratch: srpc_frames_replies_var_scratch_bytes, 8-byte aligned.
+ * Refused with nothing launched: a fixed plan, a prefix under 1 byte or more
+ * than SRPC_FRAMES_MAX_STRINGS strings (SRPC_E_UNSUPPORTED); a NULL
+ * reply_plan, d_offs (with nframes > 0), d_cols, d_str_offs, d_codes or
+ * d_scratch, a NULL column or offsets pointer of a string field, or buf_len >=
+ * 4 GiB (SRPC_E_INVALID; the arguments themselves are checked before the plan
+ * is read); too little scratch (SRPC_E_CAPACITY); a misaligned d_buf, column,
+ * offsets array or scratch (SRPC_E_ALIGN). */
+int srpc_frames_replies_var_scratch_bytes(const srpc_plan* reply_plan, uint64_t nframes, uint64_t* out);
+int srpc_frames_unpack_replies_var(const srpc_plan* reply_plan, const uint8_t* d_buf, uint64_t buf_len,
+                                   const uint32_t* d_offs, uint64_t nframes, void* const* d_cols,
+                                   uint64_t* const* d_str_offs, uint8_t* d_codes,
+                                   srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                   void* stream);
+/* Testing hook: frames per workgroup tile and the tile's LDS image bytes. */
+int srpc_frames_replies_var_tile(const srpc_plan* reply_plan, uint32_t* frames, uint32_t* image_bytes);
+
+/* d_out + d_rec_offs[j] + 4 j = BE32(len_j) | record j, j < n: the records
+ * srpc_gpu_pack_var wrote (with the prefix `str(method) | str(Req::name)`: a
+ * string request batch), framed for transport.hpp's recv_data.  out_cap >=
+ * d_rec_offs[n] + 4 n is the caller's promise; a record of 4 GiB or more, or
+ * one whose frame would pass out_cap, sets SRPC_STATUS_BOUNDS in *d_status
+ * (may be NULL; not reset by this call, so it can be the pack call's) and its
+ * frame is not written. */
+int srpc_frames_frame_var(const uint8_t* d_records, const uint64_t* d_rec_offs, uint64_t n,
+                          uint8_t* d_out, uint64_t out_cap, srpc_unpack_status* d_status, void* stream);
+
 /* ---- utilities --------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
@@ -544,7 +627,7 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
- * srpc_frames_unpack_replies call made on this host
+ * srpc_frames_unpack_replies / _unpack_replies_var call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

@@ -197,6 +197,35 @@ class GpuPacker:
         check(_lib.lib().srpc_frames_replies_per_tile(self._h, C.byref(out)), "srpc_frames_replies_per_tile")
         return out.value
 
+    # -- framed reply streams with string fields (client side) ----------------
+    def replies_var_scratch_bytes(self, nframes: int) -> int:
+        """Device scratch for unpack_replies_var (8-byte aligned)."""
+        out = C.c_uint64()
+        check(_lib.lib().srpc_frames_replies_var_scratch_bytes(self._h, nframes, C.byref(out)),
+              "srpc_frames_replies_var_scratch_bytes")
+        return out.value
+
+    def unpack_replies_var(self, buf, buf_len: int, offs, nframes: int, cols: Sequence, str_offs: Sequence, codes,
+                           scratch, scratch_bytes: int, status=None, stream=None) -> None:
+        """Decode a reply stream of mixed frames of a string response in call
+        order (async): this plan's prefix is the unframed ``response_prefix``.
+        ``offs``: nframes u32 device offsets of the frames.  String field f's
+        chars go to cols[f] (room for buf_len bytes), its nframes+1 offsets to
+        str_offs[f]; ``codes``: one status code per call."""
+        check(_lib.lib().srpc_frames_unpack_replies_var(self._h, _dptr(buf), buf_len, _dptr(offs), nframes,
+                                                        self._cols(cols), self._str_offs(str_offs), _dptr(codes),
+                                                        _dptr(status), _dptr(scratch), scratch_bytes,
+                                                        _stream(stream)),
+              "srpc_frames_unpack_replies_var")
+
+    @property
+    def replies_var_tile(self) -> tuple[int, int]:
+        """(frames per workgroup tile, LDS image bytes) of unpack_replies_var (testing hook)."""
+        fr, im = C.c_uint32(), C.c_uint32()
+        check(_lib.lib().srpc_frames_replies_var_tile(self._h, C.byref(fr), C.byref(im)),
+              "srpc_frames_replies_var_tile")
+        return fr.value, im.value
+
     # -- host-terminated batches (ABI 7) ---------------------------------------
     def host_scratch_bytes(self, chunk_records: int, depth: int = 3) -> int:
         out = C.c_uint64()
@@ -379,6 +408,13 @@ def framed_response_prefix(schema: Schema, code: int = RPC_SUCCESS) -> bytes:
     return struct.pack(">I", len(pre) + schema.body_bytes) + pre
 
 
+def frame_var(records, rec_offs, n: int, out, out_cap: int, status=None, stream=None) -> None:
+    """Frame the n records ``pack_var`` wrote (``rec_offs``: its record index)
+    for the socket: ``BE32(len_j) | record j`` at out + rec_offs[j] + 4 j (async)."""
+    check(_lib.lib().srpc_frames_frame_var(_dptr(records), _dptr(rec_offs), n, _dptr(out), out_cap, _dptr(status),
+                                           _stream(stream)), "srpc_frames_frame_var")
+
+
 class FrameClassifier:
     """Buckets a batch of socket frames by method on the device
     (srpc_frames_classify / _gather / _scatter): ``methods`` is a list of
@@ -438,5 +474,5 @@ class FrameClassifier:
 
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
            "fill_splitmix_i32", "time_next_call", "framed_request_prefix", "framed_response_prefix",
-           "FrameClassifier", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
+           "FrameClassifier", "frame_var", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
            "RPC_SUCCESS", "RPC_ERR_FUNCTION_NOT_REGISTERED", "RPC_ERR_RECV_TIMEOUT"]

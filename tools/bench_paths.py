@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default="", help="substring filter on case names")
+    ap.add_argument("--replies-var-frames", type=int, default=1 << 24,
+                    help="frames of the replies_var rows (default 16M, the other reply rows' n)")
     ap.add_argument("--var-kernel", default="", help="VAR cases: comma list of pack kernels to time "
                     "(1 record tiles, 0 scan + walk; default: the plan's default)")
     ap.add_argument("--var-caps", default="", help="VAR record tiles: IMAGE:CHARS bytes (default: the plan's)")
@@ -229,6 +231,190 @@ def main():
         t = timeit(lambda: p.unpack_replies(d_mixed, mixed.size, d_o, n, back, codes, st, stream=s))
         row("indexed_1pct_bare", mixed.size + col_bytes + 5 * n, t, ok)
 
+    def replies_var_case(name, sch, n, maxlen):
+        """Reply streams of n frames of a string response decoded in call order
+        (srpc_frames_unpack_replies_var): all frames full, and with 1 % bare
+        error frames.  The stream is made on the device (pack_var + frame_var)
+        and its first 4096 frames are checked against the CPU oracle; the
+        decode of the whole stream is checked against the inputs.  Algorithmic
+        bytes: stream + fixed columns + chars + 8 (n + 1) offset bytes per
+        string field + 1 code and 4 frame-offset bytes per frame.  Beside the
+        all-full row, the route the library offered before -- srpc_frames_gather_var
+        with an identity index, then srpc_gpu_unpack_var -- timed alternately
+        with the new call on stream events, and unpack_var alone on the kernel
+        clock."""
+        if args.only not in name:
+            return
+        from srpc_amd import FrameClassifier, frame_var
+        STRING = oracle.STRING
+        kinds = sch.kinds
+        pre = oracle.response_prefix(0, sch.name)
+        p = GpuPacker.for_response(sch, 0)
+        rng = np.random.default_rng(4)
+        cols, offs = [], []
+        for k in kinds:
+            if k == STRING:
+                o = np.zeros(n + 1, np.uint64)
+                np.cumsum(rng.integers(0, maxlen + 1, n), out=o[1:])
+                cols.append(rng.integers(0, 256, max(1, int(o[-1])), dtype=np.uint8))
+                offs.append(o)
+            else:
+                dt = np.dtype(oracle.KIND_DTYPE[k])
+                cols.append(rng.integers(0, 256, n * dt.itemsize, dtype=np.uint8).view(dt))
+                offs.append(None)
+        dcols = [t_u8(c) for c in cols]
+        doffs = [None if o is None else torch.from_numpy(o.view(np.int64)).to(dev) for o in offs]
+        nstr = sum(k == STRING for k in kinds)
+        fixed = len(pre) + sum(8 if k == STRING else oracle.KIND_SIZE[k] for k in kinds)
+        chars = sum(int(o[-1]) for o in offs if o is not None)
+        total = n * fixed + chars
+        assert total + 4 * n < 1 << 32
+        wire = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        rec = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        vsb = p.var_scratch_bytes(n, total + 4 * n)
+        vscratch = torch.empty(vsb + 16, dtype=torch.uint8, device=dev)
+        st = torch.zeros(16, dtype=torch.uint8, device=dev)
+        p.pack_var(dcols, doffs, n, wire, total, rec, vscratch, vsb, st, stream=s)
+        buf_len = total + 4 * n
+        frames = torch.empty(buf_len + 16, dtype=torch.uint8, device=dev)
+        frame_var(wire, rec, n, frames, buf_len, st, stream=s)
+        torch.cuda.synchronize()
+        ar = torch.arange(n, dtype=torch.int64, device=dev)
+        f_off = rec[:n] + 4 * ar                 # frame starts
+        f_len = rec[1:] - rec[:n] + 4
+        m = 4096
+        ow = oracle.pack(kinds, [c[:m] if o is None else c for c, o in zip(cols, offs)], m, pre,
+                         [None if o is None else o[:m + 1].copy() for o in offs])
+        orec = rec[:m + 1].cpu().numpy()
+        want = b"".join(int(orec[i + 1] - orec[i]).to_bytes(4, "big") + ow[int(orec[i]):int(orec[i + 1])] for i in range(m))
+        made_ok = (not bool(st[:4].any()) and int(rec[n]) == total and len(ow) == int(orec[m])
+                   and frames[:len(want)].cpu().numpy().tobytes() == want)
+        del wire
+
+        def u32(t):
+            return t.to(torch.int32).contiguous()  # values under 2^32 keep their low 32 bits
+
+        def gather_runs(src, starts, lens):
+            """src[starts[i] : starts[i] + lens[i]] back to back, 2M runs at a time."""
+            ends = torch.cumsum(lens, 0)
+            out = torch.empty(int(ends[-1]) + 16, dtype=torch.uint8, device=dev)
+            step = 1 << 21
+            for a in range(0, n, step):
+                b = min(n, a + step)
+                l = lens[a:b]
+                o0 = int(ends[a] - lens[a])
+                tot = int(ends[b - 1]) - o0
+                if not tot:
+                    continue
+                fid = torch.repeat_interleave(torch.arange(b - a, device=dev), l)
+                within = torch.arange(tot, device=dev) - (ends[a:b] - l - o0)[fid]
+                out[o0:o0 + tot] = src[starts[a:b][fid] + within]
+            return out, ends
+
+        back = [torch.empty(buf_len + 16 if k == STRING else c.numel(), dtype=torch.uint8, device=dev)
+                for k, c in zip(kinds, dcols)]
+        boffs = [torch.empty(n + 1, dtype=torch.int64, device=dev) if k == STRING else None for k in kinds]
+        codes = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        sb = p.replies_var_scratch_bytes(n)
+        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+
+        def clear():
+            for b in back:
+                b.fill_(0xA5)
+            codes.fill_(0xA5)
+
+        def same(want_cols, want_offs, want_codes):
+            torch.cuda.synchronize()
+            ok = torch.equal(codes[:n], want_codes) and not bool(st[:4].any())
+            for k, wc, wo, b, bo in zip(kinds, want_cols, want_offs, back, boffs):
+                if k == STRING:
+                    ok = ok and torch.equal(bo, wo) and torch.equal(b[:int(wo[n])], wc[:int(wo[n])])
+                else:
+                    ok = ok and torch.equal(b, wc)
+            return bool(ok)
+
+        def row(mode, alg, t, ok, **extra):
+            rows.append({"case": f"{name}_{mode}", "replies": True, "frames": n, "frame_bytes": round(buf_len / n, 1),
+                         "alg_bytes": alg, "us": round(t * 1e6, 2), "GBps": round(alg / t / 1e9, 1),
+                         "frac": round(alg / t / 8e12, 4), "parity_ok": bool(ok), **extra})
+
+        def ev(fn):
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / 1e3
+
+        fixed_bytes = sum(c.nbytes for c, k in zip(cols, kinds) if k != STRING)
+        zeros = torch.zeros(n, dtype=torch.uint8, device=dev)
+        # all frames full
+        d_o = u32(f_off)
+        new = lambda: p.unpack_replies_var(frames, buf_len, d_o, n, back, boffs, codes, scratch, sb, st, stream=s)  # noqa: E731
+        clear()
+        new()
+        ok = made_ok and same(dcols, doffs, zeros)
+        t = timeit(new)
+        alg = buf_len + fixed_bytes + chars + 8 * (n + 1) * nstr + 5 * n
+        # the old route: payloads gathered with an identity index, then unpack_var
+        ident = u32(ar)
+        gsb = FrameClassifier([(p, 0)]).scratch_bytes(n)
+        gscratch = torch.empty(gsb, dtype=torch.uint8, device=dev)
+        gathered = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        grec = torch.empty(n + 1, dtype=torch.int64, device=dev)
+
+        def unpack_var():
+            p.unpack_var(gathered, total, n, grec, back, boffs, vscratch, vsb, st, stream=s)
+
+        def route():
+            FrameClassifier.gather_var(frames, d_o, ident, n, gathered, grec, gscratch, gsb, stream=s)
+            unpack_var()
+
+        clear()
+        route()
+        route_ok = same(dcols, doffs, codes[:n].clone())  # the route gives no codes
+        for _ in range(3):
+            route()
+            new()
+        t_new, t_route = [], []
+        for _ in range(args.reps):
+            t_new.append(ev(new))
+            t_route.append(ev(route))
+        tu = timeit(unpack_var)
+        alg_u = total + fixed_bytes + chars + 8 * (n + 1) * (nstr + 1)
+        row("full", alg, t, ok, ab_new=spread(t_new), ab_route=spread(t_route), route_parity_ok=route_ok,
+            route_name="gather_var+unpack_var",
+            unpack_var_us=round(tu * 1e6, 2), unpack_var_frac=round(alg_u / tu / 8e12, 4))
+        del gathered, grec, gscratch
+        # 1 % bare `BE32(1) | code 1` frames
+        bare = torch.from_numpy(rng.random(n) < 0.01).to(dev)
+        m_len = torch.where(bare, torch.full_like(f_len, 5), f_len)
+        mixed, m_end = gather_runs(frames, f_off, m_len)
+        m_off = m_end - m_len
+        at = m_off[bare]
+        for k, v in enumerate((0, 0, 0, 1, 1)):
+            mixed[at + k] = v
+        m_bytes = int(m_end[-1])
+        want_cols, want_offs = [], []
+        for k, c, o in zip(kinds, dcols, doffs):
+            if k == STRING:
+                l = torch.where(bare, torch.zeros_like(f_len), o[1:] - o[:n])
+                wc, we = gather_runs(c, o[:n], l)
+                want_cols.append(wc)
+                want_offs.append(torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), we]))
+            else:
+                want_cols.append(torch.where(bare.repeat_interleave(c.numel() // n), torch.zeros_like(c), c))
+                want_offs.append(None)
+        d_mo = u32(m_off)
+        new_m = lambda: p.unpack_replies_var(mixed, m_bytes, d_mo, n, back, boffs, codes, scratch, sb, st, stream=s)  # noqa: E731
+        clear()
+        new_m()
+        ok = made_ok and same(want_cols, want_offs, bare.to(torch.uint8))
+        t = timeit(new_m)
+        m_chars = sum(int(o[n]) for o in want_offs if o is not None)
+        row("1pct_bare", m_bytes + fixed_bytes + m_chars + 8 * (n + 1) * nstr + 5 * n, t, ok)
+
     def aos_case(name, sch, n, vptr=True):
         """Records as C-aligned structs behind an 8-byte vtable slot (a C++
         std::vector<T> of srpc messages copied to the device; vptr=False: a
@@ -388,6 +574,12 @@ def main():
     replies_case("number_replies_23B_16M", NUMBER, N)
     replies_case("all_kinds_replies_39B_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
                                                         ("d", "int16"), ("e", "int32"), ("f", "int64")), N)
+    NV = args.replies_var_frames
+    tag = "16M" if NV == 1 << 24 else str(NV)
+    replies_var_case(f"replies_var_text_0-64_{tag}", Schema.of("Text", ("text", "string")), NV, 64)
+    replies_var_case(f"replies_var_multiple_primitives_0-40_{tag}",
+                     Schema.of("multiple_primitives", ("arg1", "int8"), ("arg2", "char"), ("arg3", "int64"),
+                               ("arg4", "string")), NV, 40)
     aos_case("quad_aos_16M", QUAD, N)
     aos_case("quad_aos_plain_16M", QUAD, N, vptr=False)
     aos_case("all_kinds_aos_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
@@ -412,8 +604,12 @@ def main():
                           f'  time/byte vs unpack {r["time_per_byte_vs_unpack"]:.3f}')
             if "ab_new" in r:
                 extra += (f'  events: new {r["ab_new"]["median_us"]:.1f} us [{r["ab_new"]["min_us"]:.1f}, '
-                          f'{r["ab_new"]["max_us"]:.1f}]  classify+gather+unpack {r["ab_route"]["median_us"]:.1f} us '
+                          f'{r["ab_new"]["max_us"]:.1f}]  {r.get("route_name", "classify+gather+unpack")} '
+                          f'{r["ab_route"]["median_us"]:.1f} us '
                           f'[{r["ab_route"]["min_us"]:.1f}, {r["ab_route"]["max_us"]:.1f}]')
+            if "unpack_var_us" in r:
+                extra += (f'  route parity={r["route_parity_ok"]}  srpc_gpu_unpack_var alone {r["unpack_var_us"]:.1f} us '
+                          f'({r["unpack_var_frac"]:.3f})')
             print(f'{r["case"]:44s} replies {r["us"]:9.1f} us {r["GBps"]:7.1f} GB/s ({r["frac"]:.3f})  '
                   f'parity={r["parity_ok"]}{extra}')
             continue
