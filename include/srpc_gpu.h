@@ -163,7 +163,9 @@ int srpc_plan_force_path(srpc_plan* plan, int path);
 #define SRPC_TUNE_VAR_IMAGE_BYTES 8  /* VAR record tiles: LDS image bytes (8192..65536,
                                         multiple of 16); larger tiles take the walk  */
 #define SRPC_TUNE_VAR_CHARS_BYTES 10 /* VAR record tiles: LDS chars stage bytes
-                                        (0..65536, multiple of 16)                   */
+                                        (0..65536, multiple of 16).  A schema whose
+                                        image + stage + column slices pass a workgroup's
+                                        LDS packs with the scan + chunk walk          */
 #define SRPC_TUNE_REC_KERNEL 13      /* TILE path: schema-specialised kernels for the
                                         layouts that have one: 1 = in the directions
                                         where they measured faster (default), 2 = both

@@ -238,4 +238,5 @@ struct srpc_plan {
     uint32_t rt_img_cap = 0;         // record tiles: LDS image bytes, 0 = from wire_cap / n (SRPC_TUNE_VAR_IMAGE_BYTES)
     uint32_t rt_ch_cap = 0;          // record tiles: LDS chars stage bytes (SRPC_TUNE_VAR_CHARS_BYTES)
     bool rt_ch_cap_auto = true;      //   ... or what the image's span can hold
+    uint32_t lds_max = 65536;        // LDS bytes one workgroup of the device may use (a larger record-tile carve takes the walk)
 };

@@ -1179,6 +1179,10 @@ int srpc_plan_create(const srpc_schema_desc* d, int device, srpc_plan** out) {
             delete p;
             return SRPC_E_HIP;
         }
+        int lds_max = 0;
+        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess &&
+            lds_max > 0)
+            p->lds_max = static_cast<uint32_t>(lds_max);
         *out = p;
         return SRPC_OK;
     }

@@ -2481,6 +2481,10 @@ uint32_t round16(uint32_t b) { return (b + 15) & ~15u; }
 #endif
 constexpr uint64_t kRtPersistMin = SRPC_RT_PERSIST_MIN;
 constexpr uint64_t kRtTwoPerLane = 20;
+// static LDS of the record-tile pack kernels beside their dynamic carve (the
+// region table, the record starts of up to 512 records, per-field words:
+// under 6 KiB in k_pack_var_rt<2>, the largest), rounded up
+constexpr uint64_t kRtStaticLds = 8192;
 template <typename K>
 uint64_t resident_grid(K kernel, uint32_t lds, int device) {
     int per_cu = 0, cus = 0;
@@ -2622,7 +2626,23 @@ int srpc_gpu_pack_var(const srpc_plan* p, const void* const* cols, const uint64_
     // chunk walk below moves long strings at 0.38 of HBM peak, the record
     // tiles' per-tile walk fallback at 0.10, profiles/r02_var_rt_ab.log)
     const uint64_t avg = n ? wire_cap / n : 0;
-    if (p->var_kernel == 1 && (p->rt_img_cap || avg * kBlock * 17 / 16 + 64 <= kRtImageMax * 15 / 16)) {
+    bool rt_ok = p->var_kernel == 1 && (p->rt_img_cap || avg * kBlock * 17 / 16 + 64 <= kRtImageMax * 15 / 16);
+    uint32_t lds = 0;
+    const bool loop = avg >= kRtPersistMin;
+    // records under kRtTwoPerLane bytes on average: two per lane (a tile of
+    // 512 records; 0-16 B strings 114 -> 98 us, but 0-32 B 67 -> 79 us and
+    // four per lane slower on both, profiles/r02_var_rt_rpl_ab.log)
+    const uint32_t rpl = !loop && avg < kRtTwoPerLane ? 2 : 1;
+    RtArgs R{};
+    if (rt_ok && n) {
+        // the carve (image + stage + a wide schema's column slices and offsets
+        // windows) can pass what one workgroup may use when the plan fixes the
+        // image or the chars stage (SRPC_TUNE_VAR_IMAGE_BYTES / _CHARS_BYTES):
+        // such a batch takes the scan + chunk walk
+        R = rt_layout(p, avg, &lds, rpl);
+        rt_ok = static_cast<uint64_t>(lds) + kRtStaticLds <= p->lds_max;
+    }
+    if (rt_ok) {
         if (n == 0) {  // rec_offs[0] = 0
             launch(k_zero_u64, dim3(1), dim3(64), 0, s, rec_offs, 1ull);
             return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
@@ -2630,13 +2650,6 @@ int srpc_gpu_pack_var(const srpc_plan* p, const void* const* cols, const uint64_
         const uint64_t ntiles = (n + kBlock - 1) / kBlock;
         if (ntiles > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
         if (!wire) return SRPC_E_INVALID;
-        uint32_t lds = 0;
-        const bool loop = wire_cap / n >= kRtPersistMin;
-        // records under kRtTwoPerLane bytes on average: two per lane (a tile of
-        // 512 records; 0-16 B strings 114 -> 98 us, but 0-32 B 67 -> 79 us and
-        // four per lane slower on both, profiles/r02_var_rt_rpl_ab.log)
-        const uint32_t rpl = !loop && wire_cap / n < kRtTwoPerLane ? 2 : 1;
-        const RtArgs R = rt_layout(p, wire_cap / n, &lds, rpl);
         // records of >= SRPC_RT_PERSIST_MIN bytes on average: resident workgroups
         // only, each looping over its tiles with the next tile's loads in flight
         // (two strings + request envelope 228 -> 193 us, 0-64 B 134 -> 127 us);

@@ -405,18 +405,20 @@ def _dev_u64(a):
     return dev(np.ascontiguousarray(a, dtype=np.uint64))
 
 
-def gpu_pack_var(p, kinds, cols, offs, n):
-    """cols[f]: numpy column (fixed) or uint8 chars (string); offs[f]: n+1 offsets or None."""
+def gpu_pack_var(p, kinds, cols, offs, n, wire_cap=None):
+    """cols[f]: numpy column (fixed) or uint8 chars (string); offs[f]: n+1 offsets or None.
+    wire_cap: the capacity given to the call (default: the batch's bytes exactly)."""
     dcols = [dev(c) for c in cols]
     doffs = [_dev_u64(o) if o is not None else None for o in offs]
     total = int(sum(int(o[n] - o[0]) for o in offs if o is not None)) + n * (
         len(p.prefix) + sum(8 if k == oracle.STRING else oracle.KIND_SIZE[k] for k in kinds))
-    wire = empty(total + 16)
+    cap = total if wire_cap is None else wire_cap
+    wire = empty(max(total, cap) + 16)
     rec = empty(8 * (n + 1))
-    sb = p.var_scratch_bytes(n, total)
+    sb = p.var_scratch_bytes(n, cap)
     scratch = empty(sb + 16)
     st = status_buf()
-    p.pack_var(dcols, doffs, n, wire, total, rec, scratch, sb, st)
+    p.pack_var(dcols, doffs, n, wire, cap, rec, scratch, sb, st)
     rec_h = host(rec, 8 * (n + 1), np.uint64)
     return host(wire, total).tobytes(), rec_h, read_status(st)
 
