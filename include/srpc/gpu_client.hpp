@@ -30,6 +30,15 @@
 // code | str(Resp::name)`) into the client's staging, and its chars reach the
 // caller's columns only once their total is known to fit.  A side without
 // strings takes `call`'s path.
+//
+// `call_mixed` takes an ordered sequence of calls over up to 16 fixed-size
+// methods (a trace replayed against a stateful service, a pipeline whose calls
+// depend on their order): d_method[i] names call i's leg (its method, columns
+// and call count), its fields are the next element of that leg's columns.  Per
+// chunk: srpc_frames_mixed_index -> srpc_frames_pack_requests_mixed (the frames
+// batch_server buckets per method and answers in request order) -> one
+// exchange -> srpc_frames_unpack_replies_mixed, one code per call in call
+// order and each reply in its leg's columns.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -48,6 +57,7 @@
 
 #include "frame_walk.hpp"
 #include "reply_walk.hpp"
+#include "mixed_walk.hpp"
 #include "gpu.hpp"
 #include "gpu_server.hpp"  // raw_plan, framed_request_prefix, framed_response_prefix
 
@@ -74,6 +84,18 @@ struct call_stats {
 struct var_call_limits {
     uint64_t max_request_bytes = 512;
     uint64_t max_reply_bytes = 512;
+};
+
+/// One method of a mixed batch (batch_client::leg): its plans, its columns and
+/// the number of its calls in the batch.
+struct mixed_leg {
+    const srpc_plan* req = nullptr;
+    const srpc_plan* resp = nullptr;
+    uint64_t fin = 0, fout = 0;                    // request / full reply frame bytes
+    const std::vector<uint8_t>* resp_prefix = nullptr;
+    void* const* d_req_cols = nullptr;
+    void* const* d_resp_cols = nullptr;
+    uint64_t calls = 0;
 };
 
 class batch_client {
@@ -406,6 +428,143 @@ public:
         return res;
     }
 
+    /// One method of a call_mixed batch: `calls` calls of `method`, call r of
+    /// them (in batch order) taking its request fields from d_req_cols[f][r]
+    /// and leaving its reply in d_resp_cols[f][r] (device memory, columns
+    /// 16-byte aligned, `calls` elements).  The plans are call()'s, cached by
+    /// this client; a string schema throws plan_error(SRPC_E_UNSUPPORTED).
+    template <SrpcMessage Req, SrpcMessage Resp>
+    mixed_leg leg(std::string const& method, void* const* d_req_cols, void* const* d_resp_cols, uint64_t calls) {
+        check(hipSetDevice(_dev));
+        entry& e = plans<Req, Resp>(method);
+        mixed_leg l;
+        l.req = e.req->get();
+        l.resp = e.resp->get();
+        l.fin = e.fin;
+        l.fout = e.fout;
+        l.resp_prefix = &e.resp_prefix;
+        l.d_req_cols = d_req_cols;
+        l.d_resp_cols = d_resp_cols;
+        l.calls = calls;
+        return l;
+    }
+
+    /// n calls in the caller's order over at most SRPC_FRAMES_MAX_PLANS legs:
+    /// call i is the next call of legs[d_method[i]] (d_method: n device bytes);
+    /// d_codes[i] receives its status code.  The frames leave in call order,
+    /// one exchange per chunk of max_batch calls.  An id out of range, more
+    /// calls of a leg than it declares (found before anything of that chunk is
+    /// sent) or fewer (found after the last chunk) throws
+    /// plan_error(SRPC_E_INVALID).  Calls the peer never answers get
+    /// RPC_ERR_RECV_TIMEOUT and zero fields.  The request hook sees
+    /// bytes-per-frame 0: the frames differ in length.
+    call_stats call_mixed(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
+                          hipStream_t stream = nullptr) {
+        check(hipSetDevice(_dev));
+        const size_t K = legs.size();
+        if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
+            throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
+        uint64_t fin = 0, fout = 0;
+        std::vector<const srpc_plan*> rq(K), rs(K);
+        std::vector<const void* const*> rqc(K);
+        std::vector<void* const*> rsc(K);
+        std::vector<uint64_t> first(K, 0), cap(K);
+        std::vector<mixed_reply_plan> judge(K);
+        for (size_t k = 0; k < K; ++k) {
+            mixed_leg const& l = legs[k];
+            if (!l.req || !l.resp || !l.resp_prefix || !l.d_req_cols || !l.d_resp_cols)
+                throw plan_error("batch_client::call_mixed (leg)", SRPC_E_INVALID);
+            fin = std::max(fin, l.fin);
+            fout = std::max(fout, l.fout);
+            rq[k] = l.req;
+            rs[k] = l.resp;
+            rqc[k] = const_cast<const void* const*>(l.d_req_cols);
+            rsc[k] = l.d_resp_cols;
+            cap[k] = l.calls;
+            judge[k].prefix = l.resp_prefix->data();
+            judge[k].prefix_len = l.resp_prefix->size();
+            judge[k].F = l.fout;
+            judge[k].cap = l.calls;
+        }
+        ensure(fin, fout);  // staging by the largest frame of each side
+        ensure_mixed();
+        const int nk = static_cast<int>(K);
+        call_stats st;
+        st.calls = n;
+        for (uint64_t lo = 0; lo < n; lo += _max) {
+            const uint64_t m = std::min(_max, n - lo);
+            st.chunks += 1;
+            auto t0 = clock::now();
+            check_srpc(srpc_frames_mixed_index(d_method + lo, m, nk, _d_mindex, _mindex_bytes, _d_mcounts, _d_status, stream),
+                       "srpc_frames_mixed_index");
+            // the pack runs even after the peer closed: its status says whether the chunk is well formed
+            check_srpc(srpc_frames_pack_requests_mixed(rq.data(), nk, rqc.data(), first.data(), cap.data(), d_method + lo,
+                                                       _d_mindex, m, _d_out, _out_cap, _d_moffs, _d_status, stream),
+                       "srpc_frames_pack_requests_mixed");
+            check(hipMemcpyAsync(_h_mcounts, _d_mcounts, 8 * (K + 1), hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_mcounts + SRPC_FRAMES_MAX_PLANS + 1, _d_moffs + m, 4, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            check(hipStreamSynchronize(stream));
+            if (_h_status->flags || _h_mcounts[K]) {  // an id out of range, or a leg with too few calls declared
+                _last = st;
+                throw plan_error("batch_client::call_mixed (d_method does not match the legs)", SRPC_E_INVALID);
+            }
+            const uint64_t total = _eof ? 0 : *reinterpret_cast<const uint32_t*>(_h_mcounts + SRPC_FRAMES_MAX_PLANS + 1);
+            if (total) {
+                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
+                check(hipStreamSynchronize(stream));
+            }
+            st.gpu_seconds += secs(t0);
+            if (total && _hook) _hook(_h_out, lo, m, 0);
+            const frame_walk w = exchange(m, total, 0, st);
+            t0 = clock::now();
+            const uint64_t nf = w.nframes;
+            if (nf) {
+                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
+                check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+            }
+            // calls without a reply get RPC_ERR_RECV_TIMEOUT and zero fields from the decode itself
+            check_srpc(srpc_frames_unpack_replies_mixed(rs.data(), nk, _d_in, w.walked, _d_offs, nf, d_method + lo,
+                                                        _d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
+                                                        rsc.data(), first.data(), cap.data(), d_codes + lo, _d_status,
+                                                        stream),
+                       "srpc_frames_unpack_replies_mixed");
+            if (nf) check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            check(hipStreamSynchronize(stream));
+            st.gpu_seconds += secs(t0);
+            st.unanswered += m - nf;
+            if (nf && _h_status->flags == 0) {
+                const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
+                st.ok += ok;
+                st.failed += nf - ok;
+            } else if (nf) {  // a flagged chunk: the table on the host, frame by frame
+                std::vector<uint8_t> hm(m);
+                std::vector<uint32_t> rank(m);
+                std::vector<uint64_t> cnt(K + 1);
+                check(hipMemcpy(hm.data(), d_method + lo, m, hipMemcpyDeviceToHost));
+                mixed_ranks(hm.data(), m, static_cast<uint32_t>(K), rank.data(), cnt.data());
+                for (size_t k = 0; k < K; ++k) judge[k].first = first[k];
+                for (uint64_t i = 0; i < nf; ++i) {
+                    const reply_frame r = judge_reply_mixed(_h_in, w.walked, _h_offs[i], i + 1 < nf ? _h_offs[i + 1] : w.walked,
+                                                            hm[i], rank[i], judge.data(), static_cast<uint32_t>(K));
+                    if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
+                    else if (r.code == RPC_SUCCESS) st.ok += 1;
+                    else st.failed += 1;
+                }
+            }
+            for (size_t k = 0; k < K; ++k) first[k] += _h_mcounts[k];
+            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
+            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
+            _have -= w.walked;
+        }
+        _last = st;
+        for (size_t k = 0; k < K; ++k)
+            if (first[k] != legs[k].calls)
+                throw plan_error("batch_client::call_mixed (a leg declares more calls than d_method holds)", SRPC_E_INVALID);
+        return st;
+    }
+
 private:
     using clock = std::chrono::steady_clock;
     struct entry {
@@ -568,6 +727,17 @@ private:
             check(hipHostMalloc(reinterpret_cast<void**>(&_h_soffs), 8 * (_max + 1) * _d_schars.size()));
     }
 
+    /// call_mixed's own staging beside ensure's: the call index of a chunk,
+    /// its counts and its request offsets.
+    void ensure_mixed() {
+        if (_d_mindex) return;
+        check_srpc(srpc_frames_mixed_index_bytes(_max, SRPC_FRAMES_MAX_PLANS, &_mindex_bytes), "srpc_frames_mixed_index_bytes");
+        check(hipMalloc(&_d_mindex, _mindex_bytes));
+        check(hipMalloc(reinterpret_cast<void**>(&_d_mcounts), 8 * (SRPC_FRAMES_MAX_PLANS + 1)));
+        check(hipMalloc(reinterpret_cast<void**>(&_d_moffs), 4 * (_max + 1)));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_mcounts), 8 * (SRPC_FRAMES_MAX_PLANS + 2)));
+    }
+
     /// Staging for chunks of _max calls with fin-byte requests and fout-byte
     /// replies.  The receive buffer has room for a chunk of full replies and
     /// 4 KiB more; a peer whose replies outgrow it is treated as closed.
@@ -594,6 +764,13 @@ private:
     }
 
     void release() {
+        (void)hipFree(_d_mindex);
+        (void)hipFree(_d_mcounts);
+        (void)hipFree(_d_moffs);
+        (void)hipHostFree(_h_mcounts);
+        _d_mindex = nullptr;
+        _d_mcounts = _h_mcounts = nullptr;
+        _d_moffs = nullptr;
         // call_var's staging is sized by the same capacities
         (void)hipFree(_d_wire);
         (void)hipFree(_d_rec);
@@ -734,6 +911,11 @@ private:
     uint64_t _vscratch_cap = 0;
     std::vector<uint8_t*> _d_schars;
     std::vector<uint64_t*> _d_soffs;
+    // call_mixed
+    void* _d_mindex = nullptr;
+    uint64_t _mindex_bytes = 0;
+    uint64_t *_d_mcounts = nullptr, *_h_mcounts = nullptr;  // _h_mcounts[17]: the chunk's request bytes
+    uint32_t* _d_moffs = nullptr;
 };
 
 }  // namespace srpc::gpu

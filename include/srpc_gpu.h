@@ -589,6 +589,102 @@ int srpc_frames_replies_var_tile(const srpc_plan* reply_plan, uint32_t* frames, 
 int srpc_frames_frame_var(const uint8_t* d_records, const uint64_t* d_rec_offs, uint64_t n,
                           uint8_t* d_out, uint64_t out_cap, srpc_unpack_status* d_status, void* stream);
 
+/* ---- batches of calls of several methods, in call order (client side; added
+ * within ABI 8) ----------------------------------------------------------------
+ * The mirror of srpc_frames_classify: a chunk of ncalls calls of up to
+ * SRPC_FRAMES_MAX_PLANS fixed-size methods, in the caller's order, is packed
+ * into request frames in one pass and its reply stream decoded in one pass.
+ *
+ *   K = nplans, 1..SRPC_FRAMES_MAX_PLANS.  Plan k is a fixed-size plan with a
+ *     framed prefix (request: `BE32(payload) | str(method) | str(Req::name)`,
+ *     reply: `BE32(payload) | u8 code | str(Resp::name)`); F_k is its record
+ *     bytes, the whole frame.  The plans of one call have at most
+ *     SRPC_FRAMES_MIXED_MAX_FIELDS leaf fields in all (SRPC_E_UNSUPPORTED past it).
+ *   d_method[i] (u8, device) is the plan of call i; rank(i) the number of calls
+ *     j < i with d_method[j] == d_method[i].
+ *   Call i's fields are element h_first[k] + rank(i) of plan k's columns
+ *     d_cols[k][f] (host array of K host arrays of device pointers, 16-byte
+ *     aligned).  h_first[k] (host; NULL = zeros) is the number of calls of
+ *     plan k in earlier chunks of the batch, h_cap[k] (host) the elements plan
+ *     k's columns have.
+ *   A call is BAD when d_method[i] >= K or h_first[k] + rank(i) >= h_cap[k]; no
+ *     column element is read or written for a bad call.
+ *
+ * srpc_frames_mixed_index builds the chunk's call index in caller memory
+ * (d_index: opaque, 8-byte aligned, srpc_frames_mixed_index_bytes): one row of
+ * K + 1 u32 per 256 calls and one more per 16 rows -- the calls of each plan
+ * (and of ids >= K) before that row -- so 4 (K + 1) (1 + 1/16) / 256 bytes per
+ * call (0.08 B at K = 4, 0.28 B at K = 16) and no rank per call; every
+ * workgroup of the calls below finds its calls' ranks from its rows and
+ * per-plan ballots over the row's 256 method bytes.  d_counts[k] = calls of plan k, d_counts[K] = calls with an id >= K.
+ * *d_status (may be NULL) is reset, then gets SRPC_STATUS_BOUNDS with the
+ * smallest such call when one exists.  Three launches whatever the data (status
+ * reset, the histograms, one workgroup scanning the 4096-call rows); nothing
+ * waits on another workgroup.
+ *
+ * srpc_frames_mixed_ranks (testing hook, and the recount of a flagged chunk)
+ * writes rank(i) to d_rank[i], 0xFFFFFFFF for an id >= K.
+ * srpc_frames_mixed_tile: the calls one workgroup of pack / decode takes with
+ * these plans: 256, or the power of two >= 16 whose frames of max_k F_k bytes
+ * fit the 32 KiB LDS image.
+ *
+ * srpc_frames_pack_requests_mixed writes the request frames in call order:
+ * frame i is plan d_method[i]'s prefix followed by the call's fields, raw
+ * little-endian as srpc_gpu_pack writes them, at the byte offset that is the
+ * sum of the frames before it.  A bad call gets no frame (zero bytes,
+ * d_offs[i + 1] == d_offs[i], SRPC_STATUS_BOUNDS, first_bad_record the smallest
+ * such i); the other frames stay contiguous and correct.  d_offs (may be NULL)
+ * receives ncalls + 1 u32: the frame offsets and the total.  *d_status (may be
+ * NULL) is NOT reset: it can be the index call's.  out_cap < ncalls * max_k F_k
+ * is SRPC_E_CAPACITY.  No byte of d_out (16-byte aligned) at or past the total
+ * is written.  One launch.
+ *
+ * srpc_frames_unpack_replies_mixed decodes the chunk's reply stream: frame i
+ * (i < nframes <= ncalls) is bytes [d_offs[i], end_i) of d_buf, end_i =
+ * d_offs[i + 1], or buf_len for the last frame, judged by the table of
+ * srpc_frames_unpack_replies with F = F_k and plan k's prefix, k =
+ * d_method[i]: d_codes[i] as in that table, the fields (decoded for a full
+ * frame, zero otherwise) to element h_first[k] + rank(i) of plan k's columns.
+ * A bad call's frame is the table's first row (SRPC_REPLY_NO_CODE, BOUNDS) and
+ * no column element is touched for it.  Calls nframes <= i < ncalls have no
+ * frame: d_codes[i] = unanswered_code, zero fields, no status flag.  nframes ==
+ * 0 may come with d_buf == NULL; d_offs is required otherwise (frames of
+ * different plans differ in length: there is no uniform mode).
+ *   - no byte outside [d_buf, d_buf + buf_len) is read;
+ *   - no column element is written but those of the chunk's ncalls calls;
+ *   - *d_status (may be NULL) is reset; first_bad_record is the smallest
+ *     flagged i;
+ *   - the call is stream-ordered, allocates nothing, waits on nothing; its
+ *     launches (status reset, one decode) do not depend on the data;
+ *   - work is bounded by buf_len + ncalls * max_k F_k.
+ *
+ * Refused with nothing launched, in this order: a NULL required pointer,
+ * nplans outside 1..16, nframes > ncalls, buf_len >= 4 GiB or ncalls >= 2^32
+ * (SRPC_E_INVALID; checked before any plan is read); a string plan, a reply
+ * prefix under 5 or a request prefix under 4 bytes (SRPC_E_UNSUPPORTED); a
+ * misaligned d_buf, d_out, column (16), index (8) or d_offs (4) (SRPC_E_ALIGN);
+ * too small an index or out_cap (SRPC_E_CAPACITY). */
+#define SRPC_FRAMES_MIXED_MAX_FIELDS 192
+int srpc_frames_mixed_index_bytes(uint64_t ncalls, int nplans, uint64_t* out);
+int srpc_frames_mixed_index(const uint8_t* d_method, uint64_t ncalls, int nplans, void* d_index,
+                            uint64_t index_bytes, uint64_t* d_counts /* nplans + 1 */,
+                            srpc_unpack_status* d_status, void* stream);
+int srpc_frames_mixed_ranks(const void* d_index, const uint8_t* d_method, uint64_t ncalls, int nplans,
+                            uint32_t* d_rank, void* stream);
+int srpc_frames_mixed_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile);
+int srpc_frames_pack_requests_mixed(const srpc_plan* const* req_plans, int nplans,
+                                    const void* const* const* d_cols, const uint64_t* h_first,
+                                    const uint64_t* h_cap, const uint8_t* d_method, const void* d_index,
+                                    uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                    uint32_t* d_offs /* ncalls + 1, may be NULL */,
+                                    srpc_unpack_status* d_status, void* stream);
+int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                     uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                     const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                     uint8_t unanswered_code, void* const* const* d_cols,
+                                     const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                     srpc_unpack_status* d_status, void* stream);
+
 /* ---- utilities --------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
@@ -629,7 +725,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
- * srpc_frames_unpack_replies / _unpack_replies_var call made on this host
+ * srpc_frames_unpack_replies / _unpack_replies_var / srpc_frames_mixed_index /
+ * _pack_requests_mixed / _unpack_replies_mixed call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

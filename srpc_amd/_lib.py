@@ -33,6 +33,7 @@ SRPC_FRAMES_MAX_PLANS = 16
 SRPC_FRAME_UNKNOWN = 0xFF
 SRPC_FRAMES_MAX_STRINGS = 16
 SRPC_REPLY_NO_CODE = 0xFF
+SRPC_FRAMES_MIXED_MAX_FIELDS = 192
 
 SRPC_PATH_DWORD = 1
 SRPC_PATH_TILE = 2
@@ -89,6 +90,14 @@ SIGNATURES = {
     "srpc_frames_unpack_replies_var": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_replies_var_tile": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "srpc_frames_frame_var": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "srpc_frames_mixed_index_bytes": (C.c_int, [_u64, C.c_int, C.POINTER(_u64)]),
+    "srpc_frames_mixed_index": (C.c_int, [_vp, _u64, C.c_int, _vp, _u64, _vp, _vp, _vp]),
+    "srpc_frames_mixed_ranks": (C.c_int, [_vp, _vp, _u64, C.c_int, _vp, _vp]),
+    "srpc_frames_mixed_tile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32)]),
+    "srpc_frames_pack_requests_mixed": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp,
+                                                  _vp]),
+    "srpc_frames_unpack_replies_mixed": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _u64, C.c_uint8,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "srpc_status_string": (C.c_char_p, [C.c_int]),
     "srpc_gpu_abi_version": (C.c_int, []),
 }

@@ -1,0 +1,651 @@
+// mixed.hip -- batches of calls of several methods in caller-given order
+// (client side; srpc_frames_mixed_index, srpc_frames_pack_requests_mixed,
+// srpc_frames_unpack_replies_mixed of include/srpc_gpu.h).
+//
+// Call i of a chunk belongs to plan d_method[i]; its fields are element
+// first[k] + rank(i) of plan k's columns, rank(i) being the number of earlier
+// calls of the same plan.  Nothing here waits on another workgroup:
+//
+//   k_mixed_hist   a workgroup per super-row of 16 granules of 256 calls:
+//       per-plan ballots give each granule's histogram (K plans and one column
+//       for ids >= K); a granule's table row of K + 1 u32 is the calls before
+//       it inside its super-row, the super-row holds their total.
+//   k_mixed_scan   one workgroup turns the super-rows' columns into exclusive
+//       prefixes (segments of rows per thread, the segment sums scanned in LDS)
+//       and writes the chunk's counts.  The index IS that table: 4 (K + 1)
+//       (1 + 1/16) bytes per 256 calls, no rank per call.
+//   mix_ranks      (every consumer) the granule's 256 method bytes again: the
+//       rank of a call is its plan's two table entries (granule + super-row)
+//       plus the ballot counts of the lanes before it.
+//   k_mixed_pack   a workgroup per tile of T calls (T = 256, or the power of
+//       two >= 16 whose T * F_max fits the 32 KiB image; the tile's workgroup
+//       still ranks its whole granule).  The byte offset of the granule is
+//       sum_k min(table[k], room[k]) * F[k], the in-granule offsets a workgroup
+//       scan of the frame lengths.  Each lane builds its frame in the LDS image
+//       (prefix from an LDS template by lds_copy_run, fields by lds_put_small:
+//       aligned LDS accesses only); the image leaves as aligned 16-byte stores,
+//       the chunks shared with neighbouring tiles bytewise.
+//   k_mixed_unpack the same tile: the span of its frames is staged into the
+//       image with 16-byte loads, a lane per frame judges it by the table of
+//       srpc_frames_unpack_replies against its own plan's prefix and stores
+//       its fields per element.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "plan.h"
+#include "srpc_gpu.h"
+
+namespace srpc_impl {
+namespace {
+
+constexpr int kMixPlans = SRPC_FRAMES_MAX_PLANS;
+constexpr uint32_t kMixGranule = kBlock;   // calls per table row: one per lane
+constexpr uint32_t kMixWaves = kBlock / 64;
+constexpr uint32_t kMixSuper = 16;         // granules per super-row of the table
+constexpr uint32_t kMixRow = kMixPlans + 2;  // words of one LDS count row
+constexpr uint32_t kMixLds = (kMixWaves + 1) * kMixRow;  // per-wave counts, then the granule's bases
+constexpr uint32_t kMixImage = 32768;      // image bytes per tile
+constexpr int kMixFields = SRPC_FRAMES_MIXED_MAX_FIELDS;
+constexpr uint32_t kMixScanBlock = 1024;
+constexpr uint32_t kNoRank = 0xffffffffu;
+
+struct MixArgs {
+    uint8_t* col[kMixFields];        // plan k's columns: [field0[k], field0[k + 1])
+    uint16_t off[kMixFields];        // field offset inside the frame
+    uint8_t size[kMixFields];
+    const uint8_t* prefix[kMixPlans];  // device prefix (8-byte aligned, zero-padded 16 bytes past its end)
+    uint64_t first[kMixPlans];       // element of the chunk's first call of plan k
+    uint32_t room[kMixPlans];        // elements the columns have from `first` on
+    uint32_t F[kMixPlans];           // frame bytes
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];        // LDS offset of plan k's prefix template (8-byte aligned)
+    uint16_t field0[kMixPlans + 1];
+    uint32_t nplans;
+    uint32_t T;                      // calls per workgroup tile (divides kMixGranule)
+    uint32_t img;                    // LDS bytes of the image (multiple of 16)
+};
+
+struct MixLane {
+    uint32_t cls;   // plan, nplans for an id out of range, nplans + 1 for no call
+    uint32_t rank;  // calls of the same plan before this one in the chunk
+};
+
+// The ranks of granule `g`'s calls, one per lane.  table: the index (rows
+// granule rows, each the calls before it inside its super-row, then the
+// super-rows' prefixes), or nullptr for ranks inside the granule.  wcnt: LDS,
+// kMixLds words; its last row is left holding the granule's bases (the calls of
+// each plan before the granule).  The method byte and the bases are loaded
+// together, so the ranks cost one global latency.  Ends with a barrier.
+__device__ __forceinline__ MixLane mix_ranks(const uint8_t* __restrict__ method, uint64_t ncalls, uint32_t K,
+                                             const uint32_t* __restrict__ table, uint64_t rows, uint64_t g,
+                                             uint32_t* wcnt) {
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t* base = wcnt + kMixWaves * kMixRow;
+    if (threadIdx.x <= K)
+        base[threadIdx.x] = table ? table[g * (K + 1) + threadIdx.x] + table[(rows + g / kMixSuper) * (K + 1) + threadIdx.x] : 0;
+    MixLane r;
+    r.cls = i < ncalls ? min(static_cast<uint32_t>(method[i]), K) : K + 1;
+    uint32_t inw = 0;
+    for (uint32_t k = 0; k <= K; ++k) {
+        const uint64_t b = __ballot(r.cls == k);
+        if (r.cls == k) inw = __popcll(b & ((1ull << lane) - 1));
+        if (lane == 0) wcnt[w * kMixRow + k] = __popcll(b);
+    }
+    __syncthreads();
+    r.rank = kNoRank;
+    if (r.cls <= K) {
+        uint32_t v = base[r.cls] + inw;
+        for (uint32_t q = 0; q < w; ++q) v += wcnt[q * kMixRow + r.cls];
+        r.rank = v;
+    }
+    return r;
+}
+
+// A workgroup per super-row of kMixSuper granules: granule row = the calls of
+// each class before it inside the super-row, super-row = their total (scanned
+// by k_mixed_scan).
+__global__ __launch_bounds__(kBlock) void k_mixed_hist(const uint8_t* __restrict__ method, uint64_t ncalls, uint32_t K,
+                                                       uint32_t* __restrict__ table, uint64_t rows,
+                                                       srpc_unpack_status* st) {
+    __shared__ uint32_t cnt[kMixSuper * kMixWaves * kMixRow];
+    const uint64_t g0 = static_cast<uint64_t>(blockIdx.x) * kMixSuper;
+    const uint32_t ng = static_cast<uint32_t>(min<uint64_t>(kMixSuper, rows - g0));
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    // every granule's method byte first: the loads are in flight together
+    uint32_t cls[kMixSuper];
+#pragma unroll
+    for (uint32_t q = 0; q < kMixSuper; ++q) {
+        const uint64_t i = (g0 + q) * kMixGranule + threadIdx.x;
+        cls[q] = q < ng && i < ncalls ? min(static_cast<uint32_t>(method[i]), K) : K + 1;
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < kMixSuper; ++q) {
+        for (uint32_t k = 0; k <= K; ++k) {
+            const uint64_t b = __ballot(cls[q] == k);
+            if (lane == 0) cnt[(q * kMixWaves + w) * kMixRow + k] = __popcll(b);
+        }
+        if (cls[q] == K && st) report_bad(st, SRPC_STATUS_BOUNDS, (g0 + q) * kMixGranule + threadIdx.x);
+    }
+    __syncthreads();
+    if (threadIdx.x <= K) {
+        uint32_t run = 0;
+        for (uint32_t q = 0; q < ng; ++q) {
+            table[(g0 + q) * (K + 1) + threadIdx.x] = run;
+            for (uint32_t x = 0; x < kMixWaves; ++x) run += cnt[(q * kMixWaves + x) * kMixRow + threadIdx.x];
+        }
+        table[(rows + blockIdx.x) * (K + 1) + threadIdx.x] = run;
+    }
+}
+
+// One workgroup: table[r][c] (rows granules, cols K + 1) -> exclusive prefix
+// down every column, the totals to counts[0..K].
+__global__ __launch_bounds__(kMixScanBlock) void k_mixed_scan(uint32_t* __restrict__ table, uint64_t rows, uint32_t cols,
+                                                              uint64_t* __restrict__ counts) {
+    __shared__ uint32_t sums[kMixScanBlock];
+    const uint32_t nseg = kMixScanBlock / cols;
+    const uint32_t c = threadIdx.x % cols, seg = threadIdx.x / cols;
+    const uint64_t per = (rows + nseg - 1) / nseg;
+    const bool on = seg < nseg;
+    const uint64_t r0 = min<uint64_t>(static_cast<uint64_t>(seg) * per, rows), r1 = min<uint64_t>(r0 + per, rows);
+    uint32_t s = 0;
+    if (on)
+        for (uint64_t r = r0; r < r1; ++r) s += table[r * cols + c];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    if (!on) return;
+    uint32_t run = 0;
+    for (uint32_t q = 0; q < seg; ++q) run += sums[q * cols + c];
+    if (seg == nseg - 1) counts[c] = static_cast<uint64_t>(run) + s;
+    for (uint64_t r = r0; r < r1; ++r) {
+        const uint32_t v = table[r * cols + c];
+        table[r * cols + c] = run;
+        run += v;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mixed_ranks(const uint32_t* __restrict__ table, uint64_t rows,
+                                                        const uint8_t* __restrict__ method, uint64_t ncalls, uint32_t K,
+                                                        uint32_t* __restrict__ rank) {
+    __shared__ uint32_t wcnt[kMixLds];
+    const uint64_t g = blockIdx.x;
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    if (i < ncalls) rank[i] = r.cls < K ? r.rank : kNoRank;
+}
+
+// The lookups a lane makes by its own plan, in LDS: indexed from the kernel
+// arguments they would be vector loads, several of them dependent, per lane.
+struct MixLds {
+    uint8_t* col[kMixFields];
+    uint64_t first[kMixPlans];
+    uint32_t room[kMixPlans];
+    uint32_t F[kMixPlans];
+    uint16_t off[kMixFields];
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];
+    uint16_t field0[kMixPlans + 1];
+    uint8_t size[kMixFields];
+};
+
+// Filled by the whole workgroup; complete after the next barrier.
+__device__ __forceinline__ void mix_lds_fill(MixLds& d, const MixArgs& a) {
+    const uint32_t K = a.nplans, nf = a.field0[K];
+    for (uint32_t f = threadIdx.x; f < nf; f += kBlock) {
+        d.col[f] = a.col[f];
+        d.off[f] = a.off[f];
+        d.size[f] = a.size[f];
+    }
+    if (threadIdx.x <= K) d.field0[threadIdx.x] = a.field0[threadIdx.x];
+    if (threadIdx.x < K) {
+        const uint32_t k = threadIdx.x;
+        d.first[k] = a.first[k];
+        d.room[k] = a.room[k];
+        d.F[k] = a.F[k];
+        d.prefix_len[k] = a.prefix_len[k];
+        d.tmpl[k] = a.tmpl[k];
+    }
+}
+
+// The K prefixes into LDS at dst + a.tmpl[k]: a lane per byte of the template
+// region, its plan picked with uniform (scalar) argument reads, so the
+// prefixes cost one global latency whatever K is.
+__device__ __forceinline__ void mix_templates(uint8_t* dst, const MixArgs& a) {
+    const uint32_t K = a.nplans;
+    const uint32_t tb = a.tmpl[K - 1] + a.prefix_len[K - 1];
+    for (uint32_t t = threadIdx.x; t < tb; t += kBlock) {
+        uint32_t off = 0, pl = a.prefix_len[0];
+        const uint8_t* ptr = a.prefix[0];
+        for (uint32_t k = 1; k < K; ++k) {
+            const bool in = a.tmpl[k] <= t;
+            off = in ? a.tmpl[k] : off;
+            pl = in ? a.prefix_len[k] : pl;
+            ptr = in ? a.prefix[k] : ptr;
+        }
+        if (t - off < pl) dst[t] = ptr[t - off];
+    }
+}
+
+__device__ __forceinline__ uint64_t load_elem(const uint8_t* p, uint32_t s) {
+    switch (s) {
+    case 1: return *p;
+    case 2: return *reinterpret_cast<const uint16_t*>(p);
+    case 4: return *reinterpret_cast<const uint32_t*>(p);
+    default: return *reinterpret_cast<const uint64_t*>(p);
+    }
+}
+
+__device__ __forceinline__ void store_elem(uint8_t* p, uint32_t s, uint64_t v) {
+    switch (s) {
+    case 1: *p = static_cast<uint8_t>(v); break;
+    case 2: *reinterpret_cast<uint16_t*>(p) = static_cast<uint16_t>(v); break;
+    case 4: *reinterpret_cast<uint32_t*>(p) = static_cast<uint32_t>(v); break;
+    default: *reinterpret_cast<uint64_t*>(p) = v; break;
+    }
+}
+
+// LDS of k_mixed_pack: image[a.img] | templates[tmpl_bytes] | 16 pad, then
+// static wcnt, wsum and the tile's byte range.
+__global__ __launch_bounds__(kBlock) void k_mixed_pack(MixArgs a, const uint8_t* __restrict__ method,
+                                                       const uint32_t* __restrict__ table, uint64_t rows,
+                                                       uint64_t ncalls, uint8_t* __restrict__ out,
+                                                       uint32_t* __restrict__ offs, srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint32_t wsum[kMixWaves];
+    __shared__ uint32_t range[2];
+    __shared__ MixLds d;
+    if (ncalls == 0) {
+        if (offs && threadIdx.x == 0) offs[0] = 0;
+        return;
+    }
+    const uint32_t K = a.nplans;
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);  // the tile's first lane
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t* base = wcnt + kMixWaves * kMixRow;  // after mix_ranks: the calls of each plan before the granule
+
+    mix_lds_fill(d, a);
+    mix_templates(lds + a.img, a);  // the K prefixes as LDS templates
+
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
+    const bool present = r.cls <= K;
+    const bool good = r.cls < K && r.rank < d.room[r.cls];
+    const uint32_t F = good ? d.F[r.cls] : 0;
+
+    // bytes of the frames before this granule, and an exclusive scan inside it
+    uint64_t gbase = 0;
+    for (uint32_t k = 0; k < K; ++k) gbase += static_cast<uint64_t>(min(base[k], a.room[k])) * a.F[k];
+    uint32_t inc = F;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t at = inc - F;
+    for (uint32_t q = 0; q < w; ++q) at += wsum[q];
+
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T;
+    if (threadIdx.x == j0) range[0] = at;
+    if (threadIdx.x == j0 + a.T - 1) range[1] = at + F;
+    __syncthreads();
+    const uint64_t lo = gbase + range[0], hi = gbase + range[1];  // the tile's bytes of the stream
+    const uint64_t A = lo & ~15ull;                                // the image's first byte
+
+    if (mine && present) {
+        const uint64_t o = gbase + at;
+        if (offs) {
+            offs[i] = static_cast<uint32_t>(o);
+            if (i + 1 == ncalls) offs[ncalls] = static_cast<uint32_t>(o + F);
+        }
+        if (!good) {
+            if (st) report_bad(st, SRPC_STATUS_BOUNDS, i);
+        } else {
+            const uint32_t k = r.cls;
+            const uint32_t p = static_cast<uint32_t>(o - A);  // < T * F_max + 16 <= a.img
+            const uint64_t e = d.first[k] + r.rank;
+            const uint32_t f0 = d.field0[k], f1 = d.field0[k + 1];
+            // the first fields' loads are issued together, before the prefix is copied
+            constexpr uint32_t kAhead = 2;
+            uint64_t v[kAhead];
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u) {
+                const uint32_t f = min(f0 + u, f1 - 1);
+                v[u] = load_elem(d.col[f] + e * d.size[f], d.size[f]);
+            }
+            lds_copy_run(lds, p, a.img + d.tmpl[k], d.prefix_len[k]);
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u)
+                if (f0 + u < f1) lds_put_small(lds, p + d.off[f0 + u], v[u], d.size[f0 + u]);
+            for (uint32_t f = f0 + kAhead; f < f1; ++f) {
+                const uint32_t s = d.size[f];
+                lds_put_small(lds, p + d.off[f], load_elem(d.col[f] + e * s, s), s);
+            }
+        }
+    }
+    __syncthreads();
+
+    // image -> stream: whole 16-byte chunks inside [lo, hi) as one store, the rest bytewise
+    const uint32_t nch = static_cast<uint32_t>((hi - A + 15) >> 4);
+    for (uint32_t c = threadIdx.x; c < nch; c += kBlock) {
+        const uint64_t b0 = A + 16ull * c;
+        if (b0 >= lo && b0 + 16 <= hi) {
+            *reinterpret_cast<uint4*>(out + b0) = *reinterpret_cast<const uint4*>(lds + 16 * c);
+        } else {
+            for (uint32_t b = 0; b < 16; ++b)
+                if (b0 + b >= lo && b0 + b < hi) out[b0 + b] = lds[16 * c + b];
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t mix_be32(const uint8_t* b) {
+    return (static_cast<uint32_t>(b[0]) << 24) | (static_cast<uint32_t>(b[1]) << 16) | (static_cast<uint32_t>(b[2]) << 8) |
+           static_cast<uint32_t>(b[3]);
+}
+
+// LDS of k_mixed_unpack: image[a.img + 32] | lo[T + 1] (8-byte padded) | the K
+// prefixes (8-byte aligned each), then static wcnt and the lookups.
+__global__ __launch_bounds__(kBlock) void k_mixed_unpack(MixArgs a, const uint8_t* __restrict__ method,
+                                                         const uint32_t* __restrict__ table, uint64_t rows,
+                                                         uint64_t ncalls, const uint8_t* __restrict__ buf,
+                                                         uint64_t buf_len,
+                                                         const uint32_t* __restrict__ offs, uint64_t nframes,
+                                                         uint32_t unanswered, uint8_t* __restrict__ codes,
+                                                         srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ MixLds d;
+    uint8_t* img = lds;
+    uint32_t* lo = reinterpret_cast<uint32_t*>(lds + a.img + 32);
+    const uint8_t* tmpl = lds + a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
+    const uint32_t K = a.nplans;
+    mix_lds_fill(d, a);
+    mix_templates(lds + a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u), a);
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    // frames of this tile
+    const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(a.T, nframes - c0)) : 0;
+    for (uint32_t j = threadIdx.x; j <= a.T; j += kBlock) lo[j] = c0 + j < nframes ? offs[c0 + j] : static_cast<uint32_t>(buf_len);
+
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);  // barrier: lo[] is complete
+    const bool good = r.cls < K && r.rank < d.room[r.cls];
+
+    // 1. the span of the tile's frames -> image, from a 16-byte boundary
+    const uint32_t cap = a.img;
+    uint64_t s0 = 0;
+    uint32_t staged = 0;
+    if (nr) {
+        const uint64_t o0 = lo[0], oe = lo[nr];
+        s0 = o0 & ~15ull;
+        if (o0 <= buf_len) {
+            const uint64_t end = oe >= o0 && oe <= buf_len ? oe : buf_len;
+            staged = static_cast<uint32_t>(min<uint64_t>(end - s0, cap));
+        }
+    }
+    const uint8_t* src = buf + s0;
+    const uint32_t full = staged >> 4;
+    constexpr int kLoads = 4;  // 16-byte loads in flight per lane
+    for (uint32_t cb = threadIdx.x; cb < full; cb += kBlock * kLoads) {
+        uint4 vv[kLoads];
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u) vv[u] = *reinterpret_cast<const uint4*>(src + 16 * min(cb + u * kBlock, full - 1));
+#pragma unroll
+        for (int u = 0; u < kLoads; ++u)
+            if (cb + u * kBlock < full) *reinterpret_cast<uint4*>(img + 16 * (cb + u * kBlock)) = vv[u];
+    }
+    for (uint32_t b = full * 16 + threadIdx.x; b < staged; b += kBlock) img[b] = src[b];
+    __syncthreads();
+
+    // 2. a lane per call: judge its frame, store its code and fields
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T && i < ncalls;
+    if (!mine) return;
+    const uint32_t j = threadIdx.x - j0;
+    uint32_t code = SRPC_REPLY_NO_CODE, flag = 0, q = 0;
+    bool decoded = false, in_img = false;
+    uint64_t o = 0;
+    if (j >= nr) {
+        code = unanswered;  // no frame: no flag
+    } else if (!good) {
+        flag = SRPC_STATUS_BOUNDS;  // no plan, or no element to decode into
+    } else {
+        const uint32_t k = r.cls;
+        const uint64_t e = lo[j + 1];
+        o = lo[j];
+        if (!(o <= e && e <= buf_len) || e - o < 5) {
+            flag = SRPC_STATUS_BOUNDS;
+        } else {
+            const uint64_t len = e - o;
+            const uint64_t need = len == d.F[k] ? len : 5;
+            in_img = o >= s0 && o - s0 + need <= staged;
+            q = static_cast<uint32_t>(o - s0);
+            const uint8_t* h = in_img ? img + q : buf + o;
+            const uint32_t be = mix_be32(h), cb = h[4];
+            if (be != len - 4) {
+                flag = SRPC_STATUS_BOUNDS;
+            } else {
+                code = cb;
+                if (len == d.F[k]) {
+                    const uint32_t pl = d.prefix_len[k];
+                    const uint8_t* pre = tmpl + d.tmpl[k];
+                    bool eq = true;
+                    if (in_img) {
+                        for (uint32_t b = 0; b < pl; b += 8) {
+                            uint64_t m = pl - b >= 8 ? ~0ull : (1ull << (8 * (pl - b))) - 1;
+                            if (b == 0) m &= ~(0xffull << 32);  // the code byte
+                            eq &= ((lds_u64(img, q + b) ^ *reinterpret_cast<const uint64_t*>(pre + b)) & m) == 0;
+                        }
+                    } else {
+                        for (uint32_t b = 0; b < pl; ++b) eq &= b == 4 || buf[o + b] == pre[b];
+                    }
+                    if (eq) decoded = true;
+                    else flag = SRPC_STATUS_PREFIX;
+                } else if (!(len == 5 && cb != 0)) {
+                    flag = SRPC_STATUS_PREFIX;
+                }
+            }
+        }
+    }
+    codes[i] = static_cast<uint8_t>(code);
+    if (flag && st) report_bad(st, flag, i);
+    if (!good) return;  // no column element is touched for a bad call
+    const uint32_t k = r.cls;
+    const uint64_t e = d.first[k] + r.rank;
+    for (uint32_t f = d.field0[k]; f < d.field0[k + 1]; ++f) {
+        const uint32_t s = d.size[f];
+        uint64_t v = 0;
+        if (decoded) {
+            if (in_img) {
+                v = s == 1 ? img[q + d.off[f]] : lds_u64(img, q + d.off[f]);
+            } else {
+                const uint8_t* gp = buf + o + d.off[f];
+                for (uint32_t b = 0; b < s; ++b) v |= static_cast<uint64_t>(gp[b]) << (8 * b);
+            }
+        }
+        store_elem(d.col[f] + e * s, s, v);
+    }
+}
+
+__global__ void k_mixed_reset_status(srpc_unpack_status* st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        st->flags = 0;
+        st->reserved = 0;
+        st->first_bad_record = ~0ull;
+    }
+}
+
+inline uint64_t mix_rows(uint64_t ncalls) { return (ncalls + kMixGranule - 1) / kMixGranule; }
+inline uint64_t mix_super_rows(uint64_t rows) { return (rows + kMixSuper - 1) / kMixSuper; }
+inline uint64_t mix_index_bytes(uint64_t ncalls, int nplans) {
+    const uint64_t rows = mix_rows(ncalls);
+    return std::max<uint64_t>(8, ((rows + mix_super_rows(rows)) * (nplans + 1) * 4 + 7) & ~7ull);
+}
+
+inline uint32_t mix_tile(uint32_t fmax) {
+    uint32_t t = kMixGranule;
+    while (t > 16 && t * fmax > kMixImage) t >>= 1;
+    return t;
+}
+
+// The plans of one side: fixed-size, a prefix of at least min_prefix bytes.
+int mix_plans_ok(const srpc_plan* const* plans, int nplans, uint32_t min_prefix, uint32_t* fmax) {
+    uint32_t fields = 0, m = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        if (!p) return SRPC_E_INVALID;
+        if (p->has_string || p->prefix_len < min_prefix) return SRPC_E_UNSUPPORTED;
+        fields += p->nfields;
+        m = std::max<uint32_t>(m, static_cast<uint32_t>(p->stride));
+    }
+    if (fields > static_cast<uint32_t>(kMixFields)) return SRPC_E_UNSUPPORTED;
+    *fmax = m;
+    return SRPC_OK;
+}
+
+// Columns, rooms and layouts into the kernel's arguments.
+int mix_args(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols, const uint64_t* h_first,
+             const uint64_t* h_cap, uint32_t fmax, MixArgs* a, uint32_t* tmpl_bytes) {
+    uint32_t nf = 0, tb = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        const uint64_t first = h_first ? h_first[k] : 0;
+        const uint64_t room = h_cap[k] > first ? h_cap[k] - first : 0;
+        if (!d_cols[k]) return SRPC_E_INVALID;
+        a->field0[k] = static_cast<uint16_t>(nf);
+        for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
+            const void* c = d_cols[k][f];
+            if (room && !c) return SRPC_E_INVALID;
+            if (!aligned(c, 16)) return SRPC_E_ALIGN;
+            a->col[nf] = static_cast<uint8_t*>(const_cast<void*>(c));
+            a->off[nf] = static_cast<uint16_t>(p->off[f]);
+            a->size[nf] = static_cast<uint8_t>(p->size[f]);
+        }
+        a->prefix[k] = p->d_prefix;
+        a->first[k] = first;
+        a->room[k] = static_cast<uint32_t>(std::min<uint64_t>(room, 0xffffffffull));
+        a->F[k] = static_cast<uint32_t>(p->stride);
+        a->prefix_len[k] = static_cast<uint16_t>(p->prefix_len);
+        a->tmpl[k] = static_cast<uint16_t>(tb);
+        tb += (p->prefix_len + 7) & ~7u;  // 8-byte aligned: the decode compares eight bytes at a time
+    }
+    a->field0[nplans] = static_cast<uint16_t>(nf);
+    a->nplans = static_cast<uint32_t>(nplans);
+    a->T = mix_tile(fmax);
+    a->img = (a->T * fmax + 16 + 15) & ~15u;
+    *tmpl_bytes = tb;
+    return SRPC_OK;
+}
+
+}  // namespace
+}  // namespace srpc_impl
+
+using namespace srpc_impl;
+
+extern "C" {
+
+int srpc_frames_mixed_index_bytes(uint64_t ncalls, int nplans, uint64_t* out) {
+    if (!out || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32)) return SRPC_E_INVALID;
+    *out = mix_index_bytes(ncalls, nplans);
+    return SRPC_OK;
+}
+
+int srpc_frames_mixed_index(const uint8_t* d_method, uint64_t ncalls, int nplans, void* d_index, uint64_t index_bytes,
+                            uint64_t* d_counts, srpc_unpack_status* d_status, void* stream) {
+    const TimedCall timed;
+    if (!d_index || !d_counts || (ncalls && !d_method) || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32))
+        return SRPC_E_INVALID;
+    if (!aligned(d_index, 8) || !aligned(d_counts, 8)) return SRPC_E_ALIGN;
+    if (index_bytes < mix_index_bytes(ncalls, nplans)) return SRPC_E_CAPACITY;
+    auto s = static_cast<hipStream_t>(stream);
+    auto* table = static_cast<uint32_t*>(d_index);
+    const uint64_t rows = mix_rows(ncalls);
+    if (d_status) hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    if (rows)
+        launch(k_mixed_hist, dim3(static_cast<uint32_t>(mix_super_rows(rows))), dim3(kBlock), 0, s, d_method, ncalls,
+               static_cast<uint32_t>(nplans), table, rows, d_status);
+    launch(k_mixed_scan, dim3(1), dim3(kMixScanBlock), 0, s, table + rows * (nplans + 1), mix_super_rows(rows),
+           static_cast<uint32_t>(nplans + 1), d_counts);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_mixed_ranks(const void* d_index, const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* d_rank,
+                            void* stream) {
+    if (!d_index || (ncalls && (!d_method || !d_rank)) || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32))
+        return SRPC_E_INVALID;
+    if (!aligned(d_index, 8) || !aligned(d_rank, 4)) return SRPC_E_ALIGN;
+    if (!ncalls) return SRPC_OK;
+    hipLaunchKernelGGL(k_mixed_ranks, dim3(static_cast<uint32_t>(mix_rows(ncalls))), dim3(kBlock), 0,
+                       static_cast<hipStream_t>(stream), static_cast<const uint32_t*>(d_index), mix_rows(ncalls), d_method,
+                       ncalls, static_cast<uint32_t>(nplans), d_rank);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_mixed_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile) {
+    if (!plans || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(plans, nplans, 4, &fmax)) return rc;
+    *calls_per_tile = mix_tile(fmax);
+    return SRPC_OK;
+}
+
+int srpc_frames_pack_requests_mixed(const srpc_plan* const* req_plans, int nplans, const void* const* const* d_cols,
+                                    const uint64_t* h_first, const uint64_t* h_cap, const uint8_t* d_method,
+                                    const void* d_index, uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                    uint32_t* d_offs, srpc_unpack_status* d_status, void* stream) {
+    const TimedCall timed;
+    // the arguments themselves are checked before any plan is read
+    if (!req_plans || !d_cols || !h_cap || !d_index || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32) ||
+        (ncalls && (!d_method || !d_out)))
+        return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(req_plans, nplans, 4, &fmax)) return rc;
+    if (!aligned(d_out, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4)) return SRPC_E_ALIGN;
+    MixArgs a{};
+    uint32_t tb = 0;
+    if (int rc = mix_args(req_plans, nplans, d_cols, h_first, h_cap, fmax, &a, &tb)) return rc;
+    if (out_cap < ncalls * fmax) return SRPC_E_CAPACITY;
+    if (d_offs && ncalls * fmax >= (1ull << 32)) return SRPC_E_INVALID;  // u32 offsets
+    const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, (ncalls + a.T - 1) / a.T));
+    launch(k_mixed_pack, dim3(grid), dim3(kBlock), a.img + tb + 16, static_cast<hipStream_t>(stream), a, d_method,
+           static_cast<const uint32_t*>(d_index), mix_rows(ncalls), ncalls, d_out, d_offs, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                     uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes, const uint8_t* d_method,
+                                     const void* d_index, uint64_t ncalls, uint8_t unanswered_code,
+                                     void* const* const* d_cols, const uint64_t* h_first, const uint64_t* h_cap,
+                                     uint8_t* d_codes, srpc_unpack_status* d_status, void* stream) {
+    const TimedCall timed;
+    if (!reply_plans || !d_cols || !h_cap || !d_index || !d_codes || nplans <= 0 || nplans > kMixPlans ||
+        nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) || (ncalls && !d_method) ||
+        (nframes && (!d_buf || !d_offs)))
+        return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4)) return SRPC_E_ALIGN;
+    MixArgs a{};
+    uint32_t tb = 0;
+    if (int rc = mix_args(reply_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols), h_first, h_cap, fmax,
+                          &a, &tb))
+        return rc;
+    auto s = static_cast<hipStream_t>(stream);
+    if (d_status) {
+        hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
+        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
+    }
+    if (!ncalls) return SRPC_OK;
+    const uint32_t grid = static_cast<uint32_t>((ncalls + a.T - 1) / a.T);
+    launch(k_mixed_unpack, dim3(grid), dim3(kBlock), a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u) + tb, s, a, d_method,
+           static_cast<const uint32_t*>(d_index), mix_rows(ncalls), ncalls, d_buf, buf_len, d_offs, nframes,
+           static_cast<uint32_t>(unanswered_code), d_codes, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+}  // extern "C"

@@ -472,7 +472,65 @@ class FrameClassifier:
                                              _stream(stream)), "srpc_frames_offsets")
 
 
+class MixedFrames:
+    """A batch of calls of several fixed-size methods in call order
+    (srpc_frames_mixed_index / _pack_requests_mixed / _unpack_replies_mixed):
+    ``plans`` are GpuPackers with framed prefixes, request plans for ``pack``,
+    reply plans for ``unpack``.  Every call returns the C status (negative:
+    refused, nothing launched)."""
+
+    def __init__(self, plans: Sequence["GpuPacker"]):
+        self.plans = list(plans)
+        self.k = len(self.plans)
+        self._plans = (C.c_void_p * self.k)(*[p._h.value for p in self.plans])
+
+    @staticmethod
+    def index_bytes(ncalls: int, nplans: int) -> int:
+        out = C.c_uint64()
+        check(_lib.lib().srpc_frames_mixed_index_bytes(ncalls, nplans, C.byref(out)), "srpc_frames_mixed_index_bytes")
+        return out.value
+
+    @staticmethod
+    def index(method, ncalls: int, nplans: int, index, index_bytes: int, counts, status=None, stream=None) -> int:
+        return _lib.lib().srpc_frames_mixed_index(_dptr(method), ncalls, nplans, _dptr(index), index_bytes,
+                                                  _dptr(counts), _dptr(status), _stream(stream))
+
+    @staticmethod
+    def ranks(index, method, ncalls: int, nplans: int, rank, stream=None) -> int:
+        return _lib.lib().srpc_frames_mixed_ranks(_dptr(index), _dptr(method), ncalls, nplans, _dptr(rank),
+                                                  _stream(stream))
+
+    @property
+    def tile(self) -> int:
+        out = C.c_uint32()
+        check(_lib.lib().srpc_frames_mixed_tile(self._plans, self.k, C.byref(out)), "srpc_frames_mixed_tile")
+        return out.value
+
+    def _args(self, cols, first, cap):
+        self._keep = [(C.c_void_p * len(c))(*[_dptr(x) for x in c]) for c in cols]
+        arr = (C.c_void_p * self.k)(*[C.cast(a, C.c_void_p).value for a in self._keep])
+        h_first = None if first is None else (C.c_uint64 * self.k)(*[int(x) for x in first])
+        h_cap = (C.c_uint64 * self.k)(*[int(x) for x in cap])
+        return arr, h_first, h_cap
+
+    def pack(self, cols, first, cap, method, index, ncalls: int, out, out_cap: int, offs=None, status=None,
+             stream=None) -> int:
+        """cols[k]: plan k's request columns; first / cap: per plan (first may be None)."""
+        arr, h_first, h_cap = self._args(cols, first, cap)
+        return _lib.lib().srpc_frames_pack_requests_mixed(self._plans, self.k, arr, h_first, h_cap, _dptr(method),
+                                                          _dptr(index), ncalls, _dptr(out), out_cap, _dptr(offs),
+                                                          _dptr(status), _stream(stream))
+
+    def unpack(self, buf, buf_len: int, offs, nframes: int, method, index, ncalls: int, unanswered: int, cols, first,
+               cap, codes, status=None, stream=None) -> int:
+        arr, h_first, h_cap = self._args(cols, first, cap)
+        return _lib.lib().srpc_frames_unpack_replies_mixed(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                           nframes, _dptr(method), _dptr(index), ncalls, unanswered,
+                                                           arr, h_first, h_cap, _dptr(codes), _dptr(status),
+                                                           _stream(stream))
+
+
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
            "fill_splitmix_i32", "time_next_call", "framed_request_prefix", "framed_response_prefix",
-           "FrameClassifier", "frame_var", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
+           "FrameClassifier", "frame_var", "MixedFrames", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
            "RPC_SUCCESS", "RPC_ERR_FUNCTION_NOT_REGISTERED", "RPC_ERR_RECV_TIMEOUT"]

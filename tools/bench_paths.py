@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--only", default="", help="substring filter on case names")
     ap.add_argument("--replies-var-frames", type=int, default=1 << 24,
                     help="frames of the replies_var rows (default 16M, the other reply rows' n)")
+    ap.add_argument("--mixed-calls", type=int, default=1 << 24, help="calls of the mixed rows (default 16M)")
     ap.add_argument("--var-kernel", default="", help="VAR cases: comma list of pack kernels to time "
                     "(1 record tiles, 0 scan + walk; default: the plan's default)")
     ap.add_argument("--var-caps", default="", help="VAR record tiles: IMAGE:CHARS bytes (default: the plan's)")
@@ -415,6 +416,155 @@ def main():
         m_chars = sum(int(o[n]) for o in want_offs if o is not None)
         row("1pct_bare", m_bytes + fixed_bytes + m_chars + 8 * (n + 1) * nstr + 5 * n, t, ok)
 
+    def mixed_case(name, methods, n):
+        """n calls over the methods [(method, request schema, reply schema)] in a
+        uniformly random order (srpc_frames_mixed_index, _pack_requests_mixed,
+        _unpack_replies_mixed).  The request frames' first 4096 are checked
+        against the CPU oracle (each plan's calls packed in rank order, the rows
+        interleaved by the method vector); the reply stream is made by the same
+        pack over the reply plans, checked the same way, and its decode against
+        the inputs.  Algorithmic bytes: frames + fields + 1 method byte per
+        call, + 1 code byte and 4 offset bytes per call on the reply side; the
+        index reads the method bytes and writes its table.  Beside them, timed
+        alternately on stream events, the single-plan calls over the same data:
+        one srpc_gpu_pack and one indexed srpc_frames_unpack_replies per method
+        on per-method streams (no call order, one exchange per method)."""
+        if args.only not in name:
+            return
+        from srpc_amd import MixedFrames, framed_request_prefix, framed_response_prefix
+        K = len(methods)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(5)
+
+        def dcols_of(sch):
+            out = []
+            for k in sch.kinds:
+                c = torch.randint(0, 256, (n * oracle.KIND_SIZE[k],), dtype=torch.uint8, device=dev, generator=gen)
+                out.append(c & 1 if k == oracle.BOOL else c)
+            return out
+
+        d_method = torch.randint(0, K, (n,), dtype=torch.uint8, device=dev, generator=gen)
+        counts = torch.bincount(d_method.to(torch.int64), minlength=K).cpu().numpy()
+        req = [GpuPacker(rq, framed_request_prefix(rq, m)) for m, rq, _ in methods]
+        rep = [GpuPacker(rs, framed_response_prefix(rs, 0)) for _, _, rs in methods]
+        qcols = [dcols_of(rq) for _, rq, _ in methods]
+        scols = [dcols_of(rs) for _, _, rs in methods]
+        mq, ms = MixedFrames(req), MixedFrames(rep)
+        cap = [n] * K
+        nb = MixedFrames.index_bytes(n, K)
+        d_index = torch.empty(nb, dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(8 * (K + 1), dtype=torch.uint8, device=dev)
+        st = torch.zeros(16, dtype=torch.uint8, device=dev)
+
+        def index():
+            assert MixedFrames.index(d_method, n, K, d_index, nb, d_counts, st, stream=s) == 0
+
+        def first_frames(plans, cols, out, offs, m=4096):
+            """out's first m frames against the oracle's, interleaved on the host."""
+            hm = d_method[:m].cpu().numpy()
+            want = []
+            seen = [0] * K
+            rows = []
+            for p, cs in zip(plans, cols):
+                hc = [c[: m * oracle.KIND_SIZE[k]].cpu().numpy().view(oracle.KIND_DTYPE[k]) for c, k in zip(cs, p.schema.kinds)]
+                w = oracle.pack(p.schema.kinds, hc, m, p.prefix)
+                rows.append(np.frombuffer(w, np.uint8).reshape(m, p.record_bytes))
+            for i in range(m):
+                want.append(rows[hm[i]][seen[hm[i]]].tobytes())
+                seen[hm[i]] += 1
+            want = b"".join(want)
+            ho = offs[: m + 1].cpu().numpy().view(np.uint32)
+            lens = np.array([plans[k].record_bytes for k in hm])
+            return (out[: len(want)].cpu().numpy().tobytes() == want
+                    and np.array_equal(ho, np.concatenate([[0], np.cumsum(lens)]).astype(np.uint32)))
+
+        def side(mf, plans, cols):
+            fmax = max(p.record_bytes for p in plans)
+            out = torch.empty(n * fmax + 16, dtype=torch.uint8, device=dev)
+            offs = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            fn = lambda: mf.pack(cols, None, cap, d_method, d_index, n, out, n * fmax, offs, st, stream=s)  # noqa: E731
+            assert fn() == 0
+            torch.cuda.synchronize()
+            total = int(offs[n].item()) & 0xffffffff
+            fields = sum(int(c) * p.schema.body_bytes for c, p in zip(counts, plans))
+            return out, offs, total, fields, fn
+
+        def ev(fn):
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / 1e3
+
+        def alternate(new, route):
+            for _ in range(3):
+                route()
+                new()
+            t_new, t_route = [], []
+            for _ in range(args.reps):
+                t_new.append(ev(new))
+                t_route.append(ev(route))
+            return {"ab_new": spread(t_new), "ab_route": spread(t_route)}
+
+        def row(mode, alg, t, ok, **extra):
+            rows.append({"case": f"{name}_{mode}", "mixed": True, "calls": n, "plans": K, "alg_bytes": alg,
+                         "us": round(t * 1e6, 2), "GBps": round(alg / t / 1e9, 1), "frac": round(alg / t / 8e12, 4),
+                         "parity_ok": bool(ok), **extra})
+
+        index()
+        torch.cuda.synchronize()
+        ok = np.array_equal(d_counts.cpu().numpy().view(np.uint64)[:K], counts.astype(np.uint64)) and not bool(st[:4].any())
+        row("index", n + nb, timeit(index), ok, index_bytes=nb)
+        # requests
+        out, offs, total, fields, pack = side(mq, req, qcols)
+        ok = first_frames(req, qcols, out, offs) and not bool(st[:4].any())
+        wires = [torch.empty(int(c) * p.record_bytes + 16, dtype=torch.uint8, device=dev) for c, p in zip(counts, req)]
+
+        def route_pack():
+            for p, cs, c, w in zip(req, qcols, counts, wires):
+                p.pack(cs, int(c), w, stream=s)
+
+        row("pack", total + fields + n, timeit(pack), ok, frame_bytes=round(total / n, 1),
+            **alternate(lambda: (index(), pack()), route_pack), route_name=f"{K} x srpc_gpu_pack", new_name="index+pack")
+        del out, wires
+        # replies: the stream, then its decode
+        rbuf, roffs, rtotal, rfields, _ = side(ms, rep, scols)
+        made_ok = first_frames(rep, scols, rbuf, roffs)
+        back = [[torch.empty_like(c) for c in cs] for cs in scols]
+        codes = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        for b in back:
+            for c in b:
+                c.fill_(0xA5)
+        codes.fill_(0xA5)
+
+        def decode():
+            assert ms.unpack(rbuf, rtotal, roffs, n, d_method, d_index, n, 13, back, None, cap, codes, st, stream=s) == 0
+
+        decode()
+        torch.cuda.synchronize()
+        ok = made_ok and not bool(st[:4].any()) and not bool(codes[:n].any())
+        for k, p in enumerate(rep):
+            for a, b, kind in zip(scols[k], back[k], p.schema.kinds):
+                used = int(counts[k]) * oracle.KIND_SIZE[kind]
+                ok = ok and torch.equal(a[:used], b[:used])
+        streams = []
+        for p, cs, c in zip(rep, scols, counts):
+            w = torch.empty(int(c) * p.record_bytes + 16, dtype=torch.uint8, device=dev)
+            p.pack(cs, int(c), w, stream=s)
+            o = (torch.arange(int(c), dtype=torch.int64, device=dev) * p.record_bytes).to(torch.int32).contiguous()
+            streams.append((w, o))
+        rcodes = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+
+        def route_decode():
+            for p, b, c, (w, o) in zip(rep, back, counts, streams):
+                p.unpack_replies(w, int(c) * p.record_bytes, o, int(c), b, rcodes, st, stream=s)
+
+        row("decode", rtotal + rfields + 6 * n, timeit(decode), ok, frame_bytes=round(rtotal / n, 1),
+            **alternate(decode, route_decode), route_name=f"{K} x srpc_frames_unpack_replies (indexed)",
+            new_name="decode")
+
     def aos_case(name, sch, n, vptr=True):
         """Records as C-aligned structs behind an 8-byte vtable slot (a C++
         std::vector<T> of srpc messages copied to the device; vptr=False: a
@@ -580,6 +730,12 @@ def main():
     replies_var_case(f"replies_var_multiple_primitives_0-40_{tag}",
                      Schema.of("multiple_primitives", ("arg1", "int8"), ("arg2", "char"), ("arg3", "int64"),
                                ("arg4", "string")), NV, 40)
+    NM = args.mixed_calls
+    mtag = "16M" if NM == 1 << 24 else str(NM)
+    svc = "Calculator_servicer::"
+    mixed_case(f"mixed_k1_square_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER)], NM)
+    mixed_case(f"mixed_k4_calculator_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER), (svc + "add", two, NUMBER),
+                                               (svc + "subtract", two, NUMBER), (svc + "multiply", two, NUMBER)], NM)
     aos_case("quad_aos_16M", QUAD, N)
     aos_case("quad_aos_plain_16M", QUAD, N, vptr=False)
     aos_case("all_kinds_aos_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
@@ -597,6 +753,15 @@ def main():
         with open(args.out, "w") as f:
             f.write(txt)
     for r in rows:
+        if r.get("mixed"):
+            extra = ""
+            if "ab_new" in r:
+                extra = (f'  events: {r["new_name"]} {r["ab_new"]["median_us"]:.1f} us [{r["ab_new"]["min_us"]:.1f}, '
+                         f'{r["ab_new"]["max_us"]:.1f}]  {r["route_name"]} {r["ab_route"]["median_us"]:.1f} us '
+                         f'[{r["ab_route"]["min_us"]:.1f}, {r["ab_route"]["max_us"]:.1f}]')
+            print(f'{r["case"]:36s} mixed {r["us"]:9.1f} us {r["GBps"]:7.1f} GB/s ({r["frac"]:.3f})  '
+                  f'parity={r["parity_ok"]}{extra}')
+            continue
         if r.get("replies"):
             extra = ""
             if "unpack_us" in r:
