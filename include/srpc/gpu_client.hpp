@@ -38,7 +38,14 @@
 // chunk: srpc_frames_mixed_index -> srpc_frames_pack_requests_mixed (the frames
 // batch_server buckets per method and answers in request order) -> one
 // exchange -> srpc_frames_unpack_replies_mixed, one code per call in call
-// order and each reply in its leg's columns.
+// order and each reply in its leg's columns.  With a string-bodied leg
+// (`leg_var`, call_var's column form) a chunk takes the same steps through
+// srpc_frames_pack_requests_mixed_var and srpc_frames_unpack_replies_mixed_var:
+// the traffic batch_server buckets with register_var_method beside the fixed
+// methods, still in call order and one exchange per chunk.  Reply strings go
+// straight to the leg's columns with offsets absolute over the whole call; a
+// column's capacity is never passed, and an overflow throws SRPC_E_CAPACITY
+// once the chunk is accounted for.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -96,6 +103,12 @@ struct mixed_leg {
     void* const* d_req_cols = nullptr;
     void* const* d_resp_cols = nullptr;
     uint64_t calls = 0;
+    // string-bodied legs (batch_client::leg_var); leg<> leaves these as they are
+    bool req_var = false, resp_var = false;
+    const uint64_t* const* d_req_str_offs = nullptr;   // per request leaf, NULL for fixed leaves
+    uint64_t* const* d_resp_str_offs = nullptr;        // per reply leaf, calls + 1 entries each
+    const uint64_t* resp_cap = nullptr;                // per reply leaf: the bytes a string column has
+    const std::vector<uint8_t>* resp_leaf = nullptr;   // reply leaf bytes, 0: a string
 };
 
 class batch_client {
@@ -449,6 +462,37 @@ public:
         return l;
     }
 
+    /// A leg whose request and/or response has std::string members, in
+    /// call_var's column form: a string leaf's column holds the leg's chars back
+    /// to back in call order, its offsets array `calls` + 1 u64 absolute over the
+    /// leg (request: read; reply: written, entry 0 included).  resp_cap[f] is
+    /// read for string leaves of the reply: the bytes column f has.  The plans
+    /// are call_var's.  Such legs need the call_mixed overload taking
+    /// var_call_limits (the other forwards to it with the default limits).
+    template <SrpcMessage Req, SrpcMessage Resp>
+    mixed_leg leg_var(std::string const& method, void* const* d_req_cols, const uint64_t* const* d_req_str_offs,
+                      void* const* d_resp_cols, uint64_t* const* d_resp_str_offs, const uint64_t* resp_cap,
+                      uint64_t calls) {
+        check(hipSetDevice(_dev));
+        var_entry& e = var_plans<Req, Resp>(method);
+        mixed_leg l;
+        l.req = e.req->get();
+        l.resp = e.resp->get();
+        l.fin = e.req_var ? 0 : e.fin;
+        l.fout = e.resp_var ? 0 : e.fout;
+        l.resp_prefix = &e.resp_prefix;
+        l.d_req_cols = d_req_cols;
+        l.d_resp_cols = d_resp_cols;
+        l.calls = calls;
+        l.req_var = e.req_var;
+        l.resp_var = e.resp_var;
+        l.d_req_str_offs = d_req_str_offs;
+        l.d_resp_str_offs = d_resp_str_offs;
+        l.resp_cap = resp_cap;
+        l.resp_leaf = &e.resp_leaf;
+        return l;
+    }
+
     /// n calls in the caller's order over at most SRPC_FRAMES_MAX_PLANS legs:
     /// call i is the next call of legs[d_method[i]] (d_method: n device bytes);
     /// d_codes[i] receives its status code.  The frames leave in call order,
@@ -464,6 +508,8 @@ public:
         const size_t K = legs.size();
         if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
             throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
+        for (mixed_leg const& l : legs)
+            if (l.req_var || l.resp_var) return call_mixed(legs, d_method, n, d_codes, var_call_limits{}, stream);
         uint64_t fin = 0, fout = 0;
         std::vector<const srpc_plan*> rq(K), rs(K);
         std::vector<const void* const*> rqc(K);
@@ -557,6 +603,173 @@ public:
             if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
             std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
             _have -= w.walked;
+        }
+        _last = st;
+        for (size_t k = 0; k < K; ++k)
+            if (first[k] != legs[k].calls)
+                throw plan_error("batch_client::call_mixed (a leg declares more calls than d_method holds)", SRPC_E_INVALID);
+        return st;
+    }
+
+    /// call_mixed over legs of which some are string-bodied (leg_var); without
+    /// one it is the call above.  `lim` sizes the staging as for call_var (a
+    /// fixed leg's frames count with their own size).  Beyond the call above:
+    /// plan_error(SRPC_E_CAPACITY) before anything of a chunk is sent when its
+    /// request frames outgrow the send buffer, and after a chunk is received and
+    /// accounted for when the chars of some reply column pass its resp_cap
+    /// (nothing at or past the capacity was written); SRPC_E_INVALID also for a
+    /// request string whose offsets decrease.  Unanswered calls get
+    /// RPC_ERR_RECV_TIMEOUT, zero fields and empty strings.  Reply offsets are
+    /// absolute over the whole call; the host makes no pass over them.
+    call_stats call_mixed(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
+                          var_call_limits lim, hipStream_t stream = nullptr) {
+        check(hipSetDevice(_dev));
+        const size_t K = legs.size();
+        if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
+            throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
+        bool any_var = false;
+        for (mixed_leg const& l : legs) any_var = any_var || l.req_var || l.resp_var;
+        if (!any_var) return call_mixed(legs, d_method, n, d_codes, stream);
+        uint64_t fin = lim.max_request_bytes, fout = lim.max_reply_bytes;
+        std::vector<const srpc_plan*> rq(K), rs(K);
+        std::vector<const void* const*> rqc(K);
+        std::vector<void* const*> rsc(K);
+        std::vector<const uint64_t* const*> rqo(K, nullptr);
+        std::vector<uint64_t* const*> rso(K, nullptr);
+        std::vector<std::vector<uint64_t>> scap(K);
+        std::vector<const uint64_t*> scapp(K, nullptr);
+        std::vector<uint64_t> first(K, 0), cap(K), slot_cap;
+        std::vector<mixed_reply_plan> judge(K);
+        for (size_t k = 0; k < K; ++k) {
+            mixed_leg const& l = legs[k];
+            if (!l.req || !l.resp || !l.resp_prefix || !l.d_req_cols || !l.d_resp_cols ||
+                (l.req_var && !l.d_req_str_offs) || (l.resp_var && (!l.d_resp_str_offs || !l.resp_cap || !l.resp_leaf)))
+                throw plan_error("batch_client::call_mixed (leg)", SRPC_E_INVALID);
+            fin = std::max(fin, l.fin);
+            fout = std::max(fout, l.fout);
+            rq[k] = l.req;
+            rs[k] = l.resp;
+            rqc[k] = const_cast<const void* const*>(l.d_req_cols);
+            rsc[k] = l.d_resp_cols;
+            rqo[k] = l.req_var ? l.d_req_str_offs : nullptr;
+            cap[k] = l.calls;
+            judge[k].prefix = l.resp_prefix->data();
+            judge[k].prefix_len = l.resp_prefix->size();
+            judge[k].F = l.fout;
+            judge[k].cap = l.calls;
+            if (l.resp_var) {
+                rso[k] = l.d_resp_str_offs;
+                judge[k].var = true;
+                judge[k].leaf = l.resp_leaf->data();
+                judge[k].nleaves = static_cast<uint32_t>(l.resp_leaf->size());
+                scap[k].resize(l.resp_leaf->size(), 0);
+                for (size_t f = 0; f < l.resp_leaf->size(); ++f)
+                    if ((*l.resp_leaf)[f] == 0) {
+                        scap[k][f] = l.resp_cap[f];
+                        slot_cap.push_back(l.resp_cap[f]);
+                    }
+                scapp[k] = scap[k].data();
+            }
+        }
+        ensure_bytes(_max * fin + 4096, _max * fout + 4096);
+        ensure_mixed();
+        const int nk = static_cast<int>(K);
+        ensure_mixed_var(rq.data(), rs.data(), nk);
+        const uint64_t out_cap = std::min<uint64_t>(_out_cap, (1ull << 32) - 1);
+        const size_t nslots = slot_cap.size();
+        call_stats st;
+        st.calls = n;
+        for (uint64_t lo = 0; lo < n; lo += _max) {
+            const uint64_t m = std::min(_max, n - lo);
+            st.chunks += 1;
+            auto t0 = clock::now();
+            check_srpc(srpc_frames_mixed_index(d_method + lo, m, nk, _d_mindex, _mindex_bytes, _d_mcounts, _d_status, stream),
+                       "srpc_frames_mixed_index");
+            // the pack runs even after the peer closed: its status says whether the chunk is well formed
+            check_srpc(srpc_frames_pack_requests_mixed_var(rq.data(), nk, rqc.data(), rqo.data(), first.data(), cap.data(),
+                                                           d_method + lo, _d_mindex, m, _d_out, out_cap, _d_moffs, _d_mv,
+                                                           _d_status, _d_vscratch, _vscratch_cap, stream),
+                       "srpc_frames_pack_requests_mixed_var");
+            check(hipMemcpyAsync(_h_mcounts, _d_mcounts, 8 * (K + 1), hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_mv, _d_mv, 8, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            check(hipStreamSynchronize(stream));
+            bool fits = _h_mcounts[K] == 0;  // no id out of range, no leg with too few calls declared
+            for (size_t k = 0; k < K; ++k) fits = fits && _h_mcounts[k] <= cap[k] - std::min(cap[k], first[k]);
+            if (!fits) {
+                _last = st;
+                throw plan_error("batch_client::call_mixed (d_method does not match the legs)", SRPC_E_INVALID);
+            }
+            if (_h_mv[0] > out_cap) {
+                _last = st;
+                throw plan_error("batch_client::call_mixed (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
+            }
+            if (_h_status->flags) {
+                _last = st;
+                throw plan_error("batch_client::call_mixed (a request string's offsets decrease)", SRPC_E_INVALID);
+            }
+            const uint64_t total = _eof ? 0 : _h_mv[0];
+            if (total) {
+                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
+                check(hipStreamSynchronize(stream));
+            }
+            st.gpu_seconds += secs(t0);
+            if (total && _hook) _hook(_h_out, lo, m, 0);
+            const frame_walk w = exchange(m, total, 0, st);
+            t0 = clock::now();
+            const uint64_t nf = w.nframes;
+            if (nf) {
+                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
+                check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+            }
+            // calls without a reply get RPC_ERR_RECV_TIMEOUT, zero fields and empty strings from the decode itself
+            check_srpc(srpc_frames_unpack_replies_mixed_var(rs.data(), nk, _d_in, w.walked, _d_offs, nf, d_method + lo,
+                                                            _d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
+                                                            rsc.data(), rso.data(), scapp.data(), first.data(), cap.data(),
+                                                            d_codes + lo, _d_mv + 1, _d_status, _d_vscratch, _vscratch_cap,
+                                                            stream),
+                       "srpc_frames_unpack_replies_mixed_var");
+            if (nf) check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+            if (nslots) check(hipMemcpyAsync(_h_mv + 1, _d_mv + 1, 8 * nslots, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            check(hipStreamSynchronize(stream));
+            st.gpu_seconds += secs(t0);
+            st.unanswered += m - nf;
+            if (nf && _h_status->flags == 0) {
+                const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
+                st.ok += ok;
+                st.failed += nf - ok;
+            } else if (nf) {  // a flagged chunk: the tables on the host, frame by frame
+                std::vector<uint8_t> hm(m);
+                std::vector<uint32_t> rank(m);
+                std::vector<uint64_t> cnt(K + 1);
+                check(hipMemcpy(hm.data(), d_method + lo, m, hipMemcpyDeviceToHost));
+                mixed_ranks(hm.data(), m, static_cast<uint32_t>(K), rank.data(), cnt.data());
+                for (size_t k = 0; k < K; ++k) judge[k].first = first[k];
+                for (uint64_t i = 0; i < nf; ++i) {
+                    const reply_frame r = judge_reply_mixed_var(_h_in, w.walked, _h_offs[i],
+                                                                i + 1 < nf ? _h_offs[i + 1] : w.walked, hm[i], rank[i],
+                                                                judge.data(), static_cast<uint32_t>(K));
+                    if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
+                    else if (r.code == RPC_SUCCESS) st.ok += 1;
+                    else st.failed += 1;
+                }
+            }
+            for (size_t k = 0; k < K; ++k) first[k] += _h_mcounts[k];
+            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
+            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
+            _have -= w.walked;
+            for (size_t s = 0; s < nslots; ++s)
+                if (_h_mv[1 + s] > slot_cap[s]) {
+                    _last = st;
+                    throw plan_error("batch_client::call_mixed (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
+                }
+        }
+        if (!n) {  // no chunk ran: the offsets of no calls
+            for (size_t k = 0; k < K; ++k)
+                for (size_t f = 0; legs[k].resp_var && f < legs[k].resp_leaf->size(); ++f)
+                    if ((*legs[k].resp_leaf)[f] == 0) check(hipMemsetAsync(legs[k].d_resp_str_offs[f], 0, 8, stream));
+            check(hipStreamSynchronize(stream));
         }
         _last = st;
         for (size_t k = 0; k < K; ++k)
@@ -738,6 +951,27 @@ private:
         check(hipHostMalloc(reinterpret_cast<void**>(&_h_mcounts), 8 * (SRPC_FRAMES_MAX_PLANS + 2)));
     }
 
+    /// The string form's staging beside ensure_mixed's: the scratch of both
+    /// calls and, device and pinned, the chunk's request bytes followed by the
+    /// end offset of every reply string slot.
+    void ensure_mixed_var(const srpc_plan* const* rq, const srpc_plan* const* rs, int nk) {
+        uint64_t a = 0, b = 0;
+        check_srpc(srpc_frames_mixed_var_scratch_bytes(rq, nk, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
+        check_srpc(srpc_frames_mixed_var_scratch_bytes(rs, nk, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
+        const uint64_t need = std::max(a, b);
+        if (need > _vscratch_cap) {
+            (void)hipFree(_d_vscratch);
+            _d_vscratch = nullptr;
+            _vscratch_cap = 0;
+            check(hipMalloc(&_d_vscratch, need));
+            _vscratch_cap = need;
+        }
+        if (!_d_mv) {
+            check(hipMalloc(reinterpret_cast<void**>(&_d_mv), 8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS)));
+            check(hipHostMalloc(reinterpret_cast<void**>(&_h_mv), 8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS)));
+        }
+    }
+
     /// Staging for chunks of _max calls with fin-byte requests and fout-byte
     /// replies.  The receive buffer has room for a chunk of full replies and
     /// 4 KiB more; a peer whose replies outgrow it is treated as closed.
@@ -764,6 +998,9 @@ private:
     }
 
     void release() {
+        (void)hipFree(_d_mv);
+        (void)hipHostFree(_h_mv);
+        _d_mv = _h_mv = nullptr;
         (void)hipFree(_d_mindex);
         (void)hipFree(_d_mcounts);
         (void)hipFree(_d_moffs);
@@ -916,6 +1153,7 @@ private:
     uint64_t _mindex_bytes = 0;
     uint64_t *_d_mcounts = nullptr, *_h_mcounts = nullptr;  // _h_mcounts[17]: the chunk's request bytes
     uint32_t* _d_moffs = nullptr;
+    uint64_t *_d_mv = nullptr, *_h_mv = nullptr;  // [0]: the chunk's request bytes, [1 + s]: reply string slot s's end
 };
 
 }  // namespace srpc::gpu

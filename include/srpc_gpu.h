@@ -685,6 +685,114 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
                                      const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
                                      srpc_unpack_status* d_status, void* stream);
 
+/* ---- batches of calls of several methods with string bodies, in call order
+ * (client side; added within ABI 8) ----------------------------------------------
+ * The calls above with string plans allowed beside the fixed-size ones: the
+ * client-side mirror of srpc_frames_classify over register_var_method traffic.
+ * K, d_method, rank(i), h_first[k], h_cap[k], BAD calls and the index are those
+ * of the section above; the index srpc_frames_mixed_index built is used as is.
+ * The srpc_frames_*_mixed calls above keep refusing string plans.
+ *
+ * Plan k is one of two kinds, and both may appear in one batch:
+ *   - a fixed-size plan with a framed prefix, exactly as the *_mixed calls take;
+ *   - a string plan (SRPC_PATH_VAR, at most SRPC_FRAMES_MAX_STRINGS strings)
+ *     with the UNFRAMED prefix -- request: `str(method) | str(Req::name)`, reply:
+ *     `u8 code | str(Resp::name)`, its code byte ignored -- the convention of
+ *     srpc_frames_classify and srpc_frames_unpack_replies_var.  Its frame is
+ *     `BE32(len) | prefix | fields`, each string as `u64 length | chars`.
+ * All plans together have at most SRPC_FRAMES_MIXED_MAX_FIELDS leaves; buf_len
+ * and out_cap are under 4 GiB, ncalls under 2^32.
+ * d_cols is as above.  d_str_offs is a host array of K host arrays, one entry
+ * per leaf (NULL for fixed leaves; the array of a fixed plan may be NULL): each a
+ * device pointer to h_cap[k] + 1 u64, absolute over the leg -- element e's
+ * string is bytes [offs[e], offs[e + 1]) of its column, which holds the leg's
+ * chars back to back in element order.
+ * Scratch: srpc_frames_mixed_var_scratch_bytes(plans of that call, ncalls),
+ * 8-byte aligned, monotone in ncalls; its contents need not be kept or cleared
+ * between calls.  srpc_frames_mixed_var_tile (testing hook): the calls one
+ * workgroup of pack / decode takes with these plans (256, or the power of two >=
+ * 16 whose frames without their chars fit the image) and the bytes of its LDS
+ * image window.
+ *
+ * srpc_frames_pack_requests_mixed_var: frame i is plan d_method[i]'s frame of
+ * element h_first[k] + rank(i); the frames lie back to back in call order, each
+ * byte-identical to `BE32 | pack_request` of the scalar packer (packer.hpp:77-82,
+ * 193-198).  A call is also BAD when a pair of its strings' offsets decreases;
+ * for a BAD call no chars are read, no frame is written (zero bytes) and BOUNDS
+ * is set.  Offsets are computed in 64 bits (one frame's length saturates at
+ * 4 GiB, which no out_cap admits): *d_total (device, 8-byte aligned) receives
+ * the untruncated total, d_offs[j] = min(offset_j, out_cap) for j <= ncalls.
+ * When the total exceeds out_cap, BOUNDS is set with first_bad_record the first
+ * call whose frame ends past out_cap; the frames ending at or before out_cap are
+ * complete and no byte at or past out_cap is written.  No byte at or past the
+ * total is written.  *d_status (may be NULL) is NOT reset: it can be the index
+ * call's.
+ *
+ * srpc_frames_unpack_replies_mixed_var: frame i (i < nframes) is judged by the
+ * table of srpc_frames_unpack_replies_var when plan d_method[i] is a string
+ * plan, by that of srpc_frames_unpack_replies when it is fixed.  d_codes[i] is as
+ * in the table; fixed fields go to element h_first[k] + rank(i), decoded for a
+ * full frame and zero otherwise; string fields are copied for a full frame and
+ * empty otherwise.  String offsets are absolute over the leg: the call writes
+ * entry 0 = 0 when h_first[k] == 0, otherwise it continues from entry
+ * h_first[k], which the previous chunk's call wrote, and it writes entries
+ * h_first[k] + 1 .. h_first[k] + count_k.  d_ends[s] (device, one u64 per string
+ * slot; slots are numbered over the plans and then their string leaves, in
+ * order) receives the end offset of slot s, so the host sees every total in one
+ * copy.  h_str_cap[k][f] (host array of K host arrays, read for string leaves;
+ * the array of a fixed plan may be NULL) is the bytes string column f of plan k
+ * has: no char is written at or past it, while the offsets still count every
+ * full frame, so an overflow shows as d_ends[s] > capacity.  Calls nframes <= i
+ * < ncalls get unanswered_code, zero fields, empty strings and no flag.  A BAD
+ * call's frame is the table's first row and no column or offsets element is
+ * touched for it.  *d_status (may be NULL) is reset; first_bad_record is the
+ * smallest flagged i.  nframes == 0 may come with d_buf == NULL.
+ *
+ * Both calls:
+ *   - touch no byte outside [d_buf, d_buf + buf_len) or d_out[0, out_cap);
+ *   - write the last partial 16-byte chunk of any output bytewise;
+ *   - are stream-ordered and allocate nothing;
+ *   - wait on no other workgroup: there is no look-back spin;
+ *   - make a number of launches that depends on neither the data nor K (pack:
+ *     the plans' description into scratch, sizes, one scan, pack; decode: status
+ *     reset, the description, parse, one segmented scan of all string slots in
+ *     three launches, copy);
+ *   - do work bounded by the bytes plus ncalls * the largest fixed part, on any
+ *     input.  A frame that does not lie whole inside its tile's image window is
+ *     written (read) from global memory: head and fixed part by its lane, chars
+ *     by the whole workgroup, as every other frame's chars are.
+ *
+ * Refused with nothing launched, in this order: a NULL required pointer (plans,
+ * d_cols, d_str_offs, h_cap, d_index, d_scratch; pack: d_offs, d_total, and
+ * d_method, d_out with calls; decode: h_str_cap, d_codes, d_ends, d_method with
+ * calls, d_buf and d_offs with frames), nplans outside 1..16, nframes > ncalls,
+ * buf_len or out_cap >= 4 GiB, ncalls >= 2^32 (SRPC_E_INVALID; checked before
+ * any plan is read); a fixed plan with a prefix under 4 bytes (request) or 5
+ * (reply), a string plan with a prefix under 1 byte or more than
+ * SRPC_FRAMES_MAX_STRINGS strings, more than SRPC_FRAMES_MIXED_MAX_FIELDS leaves
+ * (SRPC_E_UNSUPPORTED); a misaligned d_buf, d_out or column (16), offsets array,
+ * index, d_total, d_ends or scratch (8), d_offs (4) (SRPC_E_ALIGN); too little
+ * scratch (SRPC_E_CAPACITY). */
+int srpc_frames_mixed_var_scratch_bytes(const srpc_plan* const* plans, int nplans, uint64_t ncalls, uint64_t* out);
+int srpc_frames_mixed_var_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile,
+                               uint32_t* image_bytes);
+int srpc_frames_pack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans,
+                                        const void* const* const* d_cols,
+                                        const uint64_t* const* const* d_str_offs, const uint64_t* h_first,
+                                        const uint64_t* h_cap, const uint8_t* d_method, const void* d_index,
+                                        uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                        uint32_t* d_offs /* ncalls + 1 */, uint64_t* d_total,
+                                        srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                        void* stream);
+int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                         uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                         const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                         uint8_t unanswered_code, void* const* const* d_cols,
+                                         uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap,
+                                         const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                         uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
+                                         uint64_t scratch_bytes, void* stream);
+
 /* ---- utilities --------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
@@ -726,7 +834,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
  * srpc_frames_unpack_replies / _unpack_replies_var / srpc_frames_mixed_index /
- * _pack_requests_mixed / _unpack_replies_mixed call made on this host
+ * _pack_requests_mixed / _unpack_replies_mixed / _pack_requests_mixed_var /
+ * _unpack_replies_mixed_var call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

@@ -98,6 +98,12 @@ SIGNATURES = {
                                                   _vp]),
     "srpc_frames_unpack_replies_mixed": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _u64, C.c_uint8,
                                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "srpc_frames_mixed_var_scratch_bytes": (C.c_int, [_vp, C.c_int, _u64, C.POINTER(_u64)]),
+    "srpc_frames_mixed_var_tile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "srpc_frames_pack_requests_mixed_var": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,
+                                                      _vp, _vp, _vp, _u64, _vp]),
+    "srpc_frames_unpack_replies_mixed_var": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _u64, C.c_uint8,
+                                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_status_string": (C.c_char_p, [C.c_int]),
     "srpc_gpu_abi_version": (C.c_int, []),
 }

@@ -1,0 +1,846 @@
+// mixed_var.hip -- batches of calls of several methods in caller-given order
+// whose plans may have string fields (client side;
+// srpc_frames_pack_requests_mixed_var, srpc_frames_unpack_replies_mixed_var of
+// include/srpc_gpu.h).  The call index and mix_ranks are those of mixed.hip
+// (mixed_common.h).  Nothing here waits on another workgroup.
+//
+// Both calls first put their description of the plans (MvDesc: columns, offsets
+// arrays, layouts, 5.8 KiB -- more than kernel arguments hold) into scratch with
+// a fixed number of k_mv_upload launches; every later kernel reads it there.
+//
+// Pack:
+//   k_mv_sizes   a workgroup per granule of 256 calls: mix_ranks, each lane's
+//       frame length from its leg's offsets (u64, a frame saturates at 4 GiB),
+//       the granule's total to scratch.
+//   k_mv_scan    one workgroup: exclusive scan of the granule totals; the total
+//       to *d_total and min(total, out_cap) to d_offs[ncalls].
+//   k_mv_pack    a workgroup per tile of T calls.  Frames that lie whole inside
+//       the image window (kMixImage bytes from the 16-byte boundary at or under
+//       the tile's first byte) are built in LDS: BE32, prefix and fixed fields by
+//       the frame's lane (lds_copy_run, lds_put_small), the chars by the whole
+//       workgroup, round t moving every frame's t-th string, 8 bytes of the
+//       round's chars per lane and step, so no lane's work grows with one
+//       string.  The image leaves as aligned 16-byte stores, the chunks shared
+//       with neighbouring tiles bytewise.  A frame outside the window goes to
+//       global memory directly, by the same code with another destination.
+// Decode:
+//   k_mv_parse   the tile's span staged into LDS, a lane per frame: the table
+//       of srpc_gpu.h by the call's own plan, codes, fixed fields, each string's
+//       length into its offsets entry and its chars' stream offset to scratch.
+//   k_mv_slot_*  one segmented scan over all string slots (blockIdx.y = slot):
+//       reduce, partials (which adds the carry of the chunk before and writes
+//       d_ends), apply.  Three launches whatever K.
+//   k_mv_copy    a workgroup per granule: the chars, again in rounds by the
+//       whole workgroup; nothing at or past a column's capacity is written.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+
+#include "mixed_common.h"
+#include "plan.h"
+#include "srpc_gpu.h"
+
+namespace srpc_impl {
+namespace {
+
+constexpr int kMvStr = SRPC_FRAMES_MAX_STRINGS;
+constexpr uint64_t kMvSat = 1ull << 32;        // a frame length saturates here: past any out_cap
+constexpr uint32_t kMvScanBlock = 1024;
+constexpr uint32_t kMvSlotItems = 8;
+constexpr uint32_t kMvSlotBlock = kBlock * kMvSlotItems;  // offsets entries per workgroup of the slot scan
+constexpr uint64_t kMvInImage = 1ull << 63;    // run destination: an image offset
+
+struct alignas(16) MvDesc {
+    uint8_t* col[kMixFields];         // plan k's leaves: [field0[k], field0[k + 1])
+    uint64_t* soffs[kMixFields];      // a string leaf's offsets, else nullptr
+    uint64_t scap[kMixFields];        // decode: bytes a string column has
+    uint8_t size[kMixFields];         // 0: a string
+    uint8_t leaf_plan[kMixFields];
+    uint8_t slot_leaf[kMixFields];    // string slot -> leaf
+    uint8_t str_leaf[kMixPlans * kMvStr];  // plan k's t-th string -> leaf
+    const uint8_t* prefix[kMixPlans];
+    uint64_t first[kMixPlans];
+    uint32_t room[kMixPlans];
+    uint32_t F[kMixPlans];            // fixed plan: frame bytes; string plan: the frame without its chars
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];         // LDS offset of plan k's prefix template
+    uint16_t field0[kMixPlans + 1];
+    uint8_t var[kMixPlans];
+    uint8_t nstr[kMixPlans];
+    uint32_t nplans;
+    uint32_t nslots;
+    uint32_t maxstr;                  // max_k nstr[k]
+    uint32_t T;                       // calls per tile (divides kMixGranule)
+    uint32_t tmpl_bytes;
+};
+static_assert(sizeof(MvDesc) % 16 == 0, "uploaded in 16-byte words");
+
+constexpr uint32_t kMvChunk = 2048;
+constexpr uint32_t kMvChunks = (sizeof(MvDesc) + kMvChunk - 1) / kMvChunk;
+struct MvChunk {
+    uint4 w[kMvChunk / 16];
+};
+
+__global__ void k_mv_upload(MvChunk c, uint4* dst, uint32_t words) {
+    for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) dst[i] = c.w[i];
+}
+
+__global__ void k_mv_reset_status(srpc_unpack_status* st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        st->flags = 0;
+        st->reserved = 0;
+        st->first_bad_record = ~0ull;
+    }
+}
+
+// Exclusive scan of one u64 per lane over the workgroup; *total = the sum.
+// wsum: LDS, kMixWaves entries.  Ends with a barrier (wsum can be reused).
+__device__ __forceinline__ uint64_t mv_block_scan(uint64_t x, uint64_t* wsum, uint64_t* total) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint64_t inc = x;
+    for (uint32_t s = 1; s < 64; s <<= 1) {
+        const uint64_t t = __shfl_up(inc, s, 64);
+        if (lane >= s) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint64_t at = inc - x, all = 0;
+    for (uint32_t q = 0; q < kMixWaves; ++q) {
+        if (q < w) at += wsum[q];
+        all += wsum[q];
+    }
+    __syncthreads();
+    *total = all;
+    return at;
+}
+
+struct MvFrame {
+    uint64_t len;  // frame bytes, 0 for a bad call
+    uint64_t e;    // element of the plan's columns
+    bool good;
+};
+
+// The request frame of a call: its element and its length from the leg's
+// string offsets.  A decreasing pair makes the call bad; no char is read here.
+__device__ __forceinline__ MvFrame mv_frame(const MvDesc* __restrict__ d, const MixLane& r) {
+    MvFrame fr{0, 0, false};
+    if (r.cls >= d->nplans || r.rank >= d->room[r.cls]) return fr;
+    const uint32_t k = r.cls;
+    fr.e = d->first[k] + r.rank;
+    fr.good = true;
+    uint64_t len = d->F[k];
+    for (uint32_t t = 0; t < d->nstr[k]; ++t) {
+        const uint32_t f = d->str_leaf[k * kMvStr + t];
+        const uint64_t a = d->soffs[f][fr.e], b = d->soffs[f][fr.e + 1];
+        if (b < a) fr.good = false;
+        else len = b - a > kMvSat - len ? kMvSat : len + (b - a);
+    }
+    fr.len = fr.good ? len : 0;
+    return fr;
+}
+
+__global__ __launch_bounds__(kBlock) void k_mv_sizes(const MvDesc* __restrict__ d, const uint8_t* __restrict__ method,
+                                                     const uint32_t* __restrict__ table, uint64_t rows, uint64_t ncalls,
+                                                     uint64_t* __restrict__ gsum) {
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint64_t wsum[kMixWaves];
+    const uint64_t g = blockIdx.x;
+    const MixLane r = mix_ranks(method, ncalls, d->nplans, table, rows, g, wcnt);
+    const MvFrame fr = mv_frame(d, r);
+    uint64_t total;
+    mv_block_scan(fr.len, wsum, &total);
+    if (threadIdx.x == 0) gsum[g] = total;
+}
+
+// One workgroup: gsum[0..rows) -> exclusive prefixes, gsum[rows] = the total.
+__global__ __launch_bounds__(kMvScanBlock) void k_mv_scan(uint64_t* __restrict__ gsum, uint64_t rows, uint64_t ncalls,
+                                                          uint64_t out_cap, uint32_t* __restrict__ offs,
+                                                          uint64_t* __restrict__ d_total) {
+    __shared__ uint64_t sums[kMvScanBlock];
+    const uint64_t per = (rows + kMvScanBlock - 1) / kMvScanBlock;
+    const uint64_t r0 = min<uint64_t>(threadIdx.x * per, rows), r1 = min<uint64_t>(r0 + per, rows);
+    uint64_t s = 0;
+    for (uint64_t r = r0; r < r1; ++r) s += gsum[r];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    uint64_t run = 0;
+    for (uint32_t q = 0; q < threadIdx.x; ++q) run += sums[q];
+    if (threadIdx.x == kMvScanBlock - 1) {
+        const uint64_t total = run + s;
+        gsum[rows] = total;
+        *d_total = total;
+        offs[ncalls] = static_cast<uint32_t>(min(total, out_cap));
+    }
+    for (uint64_t r = r0; r < r1; ++r) {
+        const uint64_t v = gsum[r];
+        gsum[r] = run;
+        run += v;
+    }
+}
+
+// The K prefixes into LDS at dst + d->tmpl[k].
+__device__ __forceinline__ void mv_templates(uint8_t* dst, const MvDesc* __restrict__ d) {
+    for (uint32_t k = 0; k < d->nplans; ++k) {
+        const uint8_t* src = d->prefix[k];
+        for (uint32_t b = threadIdx.x; b < d->prefix_len[k]; b += kBlock) dst[d->tmpl[k] + b] = src[b];
+    }
+}
+
+// The k <= 8 low bytes of v to frame byte `pos`: into the image, or bytewise to
+// global memory.
+__device__ __forceinline__ void mv_put(bool inimg, uint8_t* lds, uint32_t q, uint8_t* __restrict__ out, uint64_t o,
+                                       uint32_t pos, uint64_t v, uint32_t k) {
+    if (inimg) {
+        lds_put_small(lds, q + pos, v, k);
+    } else {
+        for (uint32_t b = 0; b < k; ++b) out[o + pos + b] = static_cast<uint8_t>(v >> (8 * b));
+    }
+}
+
+// The round's runs (one per lane: rel[j] = exclusive scan of their lengths,
+// rel[kBlock] = total) copied by the whole workgroup, 8 bytes of the run space
+// per lane and step.  dst[j] is a global address, or kMvInImage | image offset.
+__device__ __forceinline__ void mv_copy_runs(const uint64_t* rel, const uint8_t* const* src, const uint64_t* dst,
+                                             uint8_t* lds) {
+    const uint64_t total = rel[kBlock];
+    const uint64_t np = (total + 7) >> 3;
+    for (uint64_t p = threadIdx.x; p < np; p += kBlock) {
+        uint64_t r = p << 3;
+        const uint64_t rend = min(r + 8, total);
+        uint32_t lo_j = 0, hi_j = kBlock;  // the last j with rel[j] <= r
+        while (hi_j - lo_j > 1) {
+            const uint32_t m = (lo_j + hi_j) >> 1;
+            if (rel[m] <= r) lo_j = m;
+            else hi_j = m;
+        }
+        uint32_t j = lo_j;
+        for (; r < rend; ++r) {
+            while (rel[j + 1] <= r) ++j;  // empty runs; r < total keeps j < kBlock
+            const uint64_t x = r - rel[j];
+            const uint8_t v = src[j][x];
+            const uint64_t t = dst[j];
+            if (t & kMvInImage) lds[static_cast<uint32_t>(t) + static_cast<uint32_t>(x)] = v;
+            else reinterpret_cast<uint8_t*>(t)[x] = v;
+        }
+    }
+}
+
+// LDS of k_mv_pack: image[kMixImage + 16] | templates[tmpl_bytes] | 16 pad.
+__global__ __launch_bounds__(kBlock) void k_mv_pack(const MvDesc* __restrict__ d, const uint8_t* __restrict__ method,
+                                                    const uint32_t* __restrict__ table, uint64_t rows, uint64_t ncalls,
+                                                    const uint64_t* __restrict__ gsum, uint8_t* __restrict__ out,
+                                                    uint64_t out_cap, uint32_t* __restrict__ offs,
+                                                    srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint64_t wsum[kMixWaves];
+    __shared__ uint64_t tile_lo;
+    __shared__ unsigned long long himg;
+    __shared__ uint64_t rel[kBlock + 1];
+    __shared__ const uint8_t* rsrc[kBlock];
+    __shared__ uint64_t rdst[kBlock];
+    const uint32_t K = d->nplans, T = d->T;
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t tm = kMixImage + 16;  // the templates' LDS offset
+
+    mv_templates(lds + tm, d);
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
+    const bool present = r.cls <= K;
+    const MvFrame fr = mv_frame(d, r);
+    uint64_t gtotal;
+    const uint64_t o = gsum[g] + mv_block_scan(fr.len, wsum, &gtotal);
+
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + T;
+    if (threadIdx.x == j0) tile_lo = o;
+    __syncthreads();
+    const uint64_t lo = tile_lo;  // the tile's first byte of the stream
+    const uint64_t A = lo & ~15ull;  // the image's first byte
+    const bool whole = mine && fr.good && o + fr.len <= out_cap;
+    const bool inimg = whole && o + fr.len - A <= kMixImage;
+    if (threadIdx.x == j0) himg = lo;
+    __syncthreads();
+    if (inimg) atomicMax(&himg, static_cast<unsigned long long>(o + fr.len));
+
+    if (mine && present) {
+        offs[i] = static_cast<uint32_t>(min(o, out_cap));
+        if (!whole && st) report_bad(st, SRPC_STATUS_BOUNDS, i);
+    }
+
+    // the lane's part of its frame: BE32, prefix, fixed fields, string lengths
+    const uint32_t k = whole ? r.cls : 0;
+    const uint32_t q = static_cast<uint32_t>(o - A);  // used when inimg
+    uint32_t f = 0, f1 = 0;
+    uint64_t pos = 0;  // bytes of the frame so far
+    if (whole) {
+        const uint32_t pl = d->prefix_len[k];
+        if (d->var[k]) {
+            const uint32_t be = static_cast<uint32_t>(fr.len - 4);
+            mv_put(inimg, lds, q, out, o, 0, __builtin_bswap32(be), 4);
+            pos = 4;
+        }
+        if (inimg) {
+            lds_copy_run(lds, q + static_cast<uint32_t>(pos), tm + d->tmpl[k], pl);
+        } else {
+            for (uint32_t b = 0; b < pl; ++b) out[o + pos + b] = lds[tm + d->tmpl[k] + b];
+        }
+        pos += pl;
+        f = d->field0[k];
+        f1 = d->field0[k + 1];
+    }
+    const uint32_t rounds = d->maxstr;
+    for (uint32_t t = 0; t <= rounds; ++t) {
+        // up to the lane's next string (after the last round: to the frame's end)
+        uint64_t rl = 0, rd = 0;
+        const uint8_t* rs = nullptr;
+        while (f < f1) {
+            const uint32_t s = d->size[f];
+            if (s) {
+                mv_put(inimg, lds, q, out, o, static_cast<uint32_t>(pos), load_elem(d->col[f] + fr.e * s, s), s);
+                pos += s;
+                ++f;
+            } else {
+                const uint64_t a = d->soffs[f][fr.e], b = d->soffs[f][fr.e + 1];
+                mv_put(inimg, lds, q, out, o, static_cast<uint32_t>(pos), b - a, 8);
+                pos += 8;
+                rl = b - a;
+                rs = d->col[f] + a;
+                rd = inimg ? (kMvInImage | (q + pos)) : reinterpret_cast<uint64_t>(out + o + pos);
+                pos += rl;
+                ++f;
+                break;
+            }
+        }
+        if (t == rounds) break;  // uniform: no string is left
+        uint64_t total;
+        const uint64_t at = mv_block_scan(rl, wsum, &total);
+        rel[threadIdx.x] = at;
+        if (threadIdx.x == 0) rel[kBlock] = total;
+        rsrc[threadIdx.x] = rs;
+        rdst[threadIdx.x] = rd;
+        __syncthreads();
+        mv_copy_runs(rel, rsrc, rdst, lds);
+        __syncthreads();
+    }
+    __syncthreads();
+
+    // image -> stream: whole 16-byte chunks inside [lo, hi) as one store, the rest bytewise
+    const uint64_t hi = himg;
+    const uint32_t nch = static_cast<uint32_t>((hi - A + 15) >> 4);
+    for (uint32_t c = threadIdx.x; c < nch; c += kBlock) {
+        const uint64_t b0 = A + 16ull * c;
+        if (b0 >= lo && b0 + 16 <= hi) {
+            *reinterpret_cast<uint4*>(out + b0) = *reinterpret_cast<const uint4*>(lds + 16 * c);
+        } else {
+            for (uint32_t b = 0; b < 16; ++b)
+                if (b0 + b >= lo && b0 + b < hi) out[b0 + b] = lds[16 * c + b];
+        }
+    }
+}
+
+// u64 of the k <= 8 bytes at p (LDS or global: a generic pointer), little-endian.
+__device__ __forceinline__ uint64_t mv_get(const uint8_t* p, uint32_t k) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < k; ++b) v |= static_cast<uint64_t>(p[b]) << (8 * b);
+    return v;
+}
+
+// LDS of k_mv_parse: image[kMixImage + 16] | templates[tmpl_bytes], then static
+// wcnt and the tile's offsets.
+__global__ __launch_bounds__(kBlock) void k_mv_parse(const MvDesc* __restrict__ d, const uint8_t* __restrict__ method,
+                                                     const uint32_t* __restrict__ table, uint64_t rows, uint64_t ncalls,
+                                                     const uint8_t* __restrict__ buf, uint64_t buf_len,
+                                                     const uint32_t* __restrict__ offs, uint64_t nframes,
+                                                     uint32_t unanswered, uint8_t* __restrict__ codes,
+                                                     uint32_t* __restrict__ srcs, uint32_t* __restrict__ counts,
+                                                     srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint32_t lo[kBlock + 1];
+    uint8_t* img = lds;
+    const uint8_t* tmpl = lds + kMixImage + 16;
+    const uint32_t K = d->nplans, T = d->T;
+    mv_templates(lds + kMixImage + 16, d);
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(T, nframes - c0)) : 0;
+    for (uint32_t j = threadIdx.x; j <= T; j += kBlock) lo[j] = c0 + j < nframes ? offs[c0 + j] : static_cast<uint32_t>(buf_len);
+
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);  // barrier: lo[] is complete
+    const bool good = r.cls < K && r.rank < d->room[r.cls];
+    // the chunk's calls per plan, for the slot scan: the last tile's granule is the last one
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < K) {
+        uint32_t v = wcnt[kMixWaves * kMixRow + threadIdx.x];
+        for (uint32_t w = 0; w < kMixWaves; ++w) v += wcnt[w * kMixRow + threadIdx.x];
+        counts[threadIdx.x] = v;
+    }
+
+    // 1. the span of the tile's frames -> image, from a 16-byte boundary
+    uint64_t s0 = 0;
+    uint32_t staged = 0;
+    if (nr) {
+        const uint64_t o0 = lo[0], oe = lo[nr];
+        s0 = o0 & ~15ull;
+        if (o0 <= buf_len) {
+            const uint64_t end = oe >= o0 && oe <= buf_len ? oe : buf_len;
+            staged = static_cast<uint32_t>(min<uint64_t>(end - s0, kMixImage));
+        }
+    }
+    const uint8_t* src = buf + s0;
+    const uint32_t full16 = staged >> 4;
+    for (uint32_t cb = threadIdx.x; cb < full16; cb += kBlock)
+        *reinterpret_cast<uint4*>(img + 16 * cb) = *reinterpret_cast<const uint4*>(src + 16 * cb);
+    for (uint32_t b = full16 * 16 + threadIdx.x; b < staged; b += kBlock) img[b] = src[b];
+    __syncthreads();
+
+    // 2. a lane per call: judge its frame, store its code, fields and string lengths
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + T && i < ncalls;
+    if (!mine) return;
+    const uint32_t j = threadIdx.x - j0;
+    uint32_t code = SRPC_REPLY_NO_CODE, flag = 0;
+    bool full = false;
+    uint64_t o = 0;
+    const uint8_t* p = nullptr;  // the frame: in the image when it lies whole inside it, else in global memory
+    uint32_t body = 0;           // a full frame's first field
+    if (j >= nr) {
+        code = unanswered;  // no frame: no flag
+    } else if (!good) {
+        flag = SRPC_STATUS_BOUNDS;  // no plan, or no element to decode into
+    } else {
+        const uint32_t k = r.cls;
+        const uint64_t e = lo[j + 1];
+        o = lo[j];
+        if (!(o <= e && e <= buf_len) || e - o < 5) {
+            flag = SRPC_STATUS_BOUNDS;
+        } else {
+            const uint64_t len = e - o;
+            p = o >= s0 && e - s0 <= staged ? img + (o - s0) : buf + o;
+            const uint32_t cb = p[4];
+            if (mix_be32(p) != len - 4) {
+                flag = SRPC_STATUS_BOUNDS;
+            } else {
+                code = cb;
+                const uint32_t pl = d->prefix_len[k];
+                const uint8_t* pre = tmpl + d->tmpl[k];
+                if (len == 5 && cb != 0) {
+                    // a bare error frame
+                } else if (!d->var[k]) {
+                    bool eq = len == d->F[k];
+                    if (eq)
+                        for (uint32_t b = 0; b < pl; ++b) eq &= b == 4 || p[b] == pre[b];
+                    if (eq) {
+                        full = true;
+                        body = pl;
+                    } else {
+                        flag = SRPC_STATUS_PREFIX;
+                    }
+                } else {
+                    bool eq = len - 4 >= pl;
+                    if (eq)
+                        for (uint32_t b = 1; b < pl; ++b) eq &= p[4 + b] == pre[b];
+                    if (!eq) {
+                        flag = SRPC_STATUS_PREFIX;
+                    } else {
+                        // the walk of the fields ends exactly at the frame's end
+                        uint64_t c = 4 + pl;
+                        bool ok = true;
+                        for (uint32_t f = d->field0[k]; ok && f < d->field0[k + 1]; ++f) {
+                            const uint32_t s = d->size[f];
+                            if (s) {
+                                ok = s <= len - c;
+                                c += s;
+                            } else if (8 > len - c) {
+                                ok = false;
+                            } else {
+                                const uint64_t sl = mv_get(p + c, 8);
+                                c += 8;
+                                ok = sl <= len - c;  // 2^63 or 2^64 - 1 cannot wrap
+                                if (ok) c += sl;
+                            }
+                        }
+                        if (ok && c == len) {
+                            full = true;
+                            body = 4 + pl;
+                        } else {
+                            flag = SRPC_STATUS_BOUNDS;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    codes[i] = static_cast<uint8_t>(code);
+    if (flag && st) report_bad(st, flag, i);
+    if (!good) return;  // no column or offsets element is touched for a bad call
+    const uint32_t k = r.cls;
+    const uint64_t e = d->first[k] + r.rank;
+    uint64_t c = body;
+    uint32_t t = 0;
+    for (uint32_t f = d->field0[k]; f < d->field0[k + 1]; ++f) {
+        const uint32_t s = d->size[f];
+        if (s) {
+            store_elem(d->col[f] + e * s, s, full ? mv_get(p + c, s) : 0);
+            c += s;
+        } else {
+            const uint64_t sl = full ? mv_get(p + c, 8) : 0;
+            c += 8;
+            d->soffs[f][e + 1] = sl;  // its length: the slot scan turns lengths into offsets
+            srcs[t * ncalls + i] = static_cast<uint32_t>(o + c);
+            c += sl;
+            ++t;
+        }
+    }
+}
+
+struct MvSlot {
+    uint64_t* arr;   // the slot's offsets array
+    uint64_t first;  // entries first + 1 .. first + n hold this chunk's lengths
+    uint64_t n;
+};
+
+__device__ __forceinline__ MvSlot mv_slot(const MvDesc* __restrict__ d, const uint32_t* __restrict__ counts,
+                                          uint64_t ncalls, uint32_t s) {
+    const uint32_t f = d->slot_leaf[s], k = d->leaf_plan[f];
+    MvSlot x;
+    x.arr = d->soffs[f];
+    x.first = d->first[k];
+    x.n = ncalls ? min(counts[k], d->room[k]) : 0;
+    return x;
+}
+
+__global__ __launch_bounds__(kBlock) void k_mv_slot_reduce(const MvDesc* __restrict__ d,
+                                                           const uint32_t* __restrict__ counts, uint64_t ncalls,
+                                                           uint64_t* __restrict__ partial, uint32_t nb) {
+    __shared__ uint64_t wsum[kMixWaves];
+    const MvSlot x = mv_slot(d, counts, ncalls, blockIdx.y);
+    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * kMvSlotBlock;
+    uint64_t s = 0;
+    for (uint32_t u = 0; u < kMvSlotItems; ++u) {
+        const uint64_t idx = b0 + u * kBlock + threadIdx.x;
+        if (idx < x.n) s += x.arr[x.first + 1 + idx];
+    }
+    uint64_t total;
+    mv_block_scan(s, wsum, &total);
+    if (threadIdx.x == 0) partial[static_cast<uint64_t>(blockIdx.y) * nb + blockIdx.x] = total;
+}
+
+// A workgroup per slot: its partials -> exclusive prefixes, starting from the
+// offset the chunk before ended at; the slot's end to ends[s].
+__global__ __launch_bounds__(kBlock) void k_mv_slot_partials(const MvDesc* __restrict__ d,
+                                                             const uint32_t* __restrict__ counts, uint64_t ncalls,
+                                                             uint64_t* __restrict__ partial, uint32_t nb,
+                                                             uint64_t* __restrict__ ends) {
+    __shared__ uint64_t wsum[kMixWaves];
+    const MvSlot x = mv_slot(d, counts, ncalls, blockIdx.x);
+    uint64_t* pp = partial + static_cast<uint64_t>(blockIdx.x) * nb;
+    uint64_t carry = x.first ? x.arr[x.first] : 0;
+    for (uint32_t b0 = 0; b0 < nb; b0 += kBlock) {
+        const uint32_t b = b0 + threadIdx.x;
+        const uint64_t v = b < nb ? pp[b] : 0;
+        uint64_t total;
+        const uint64_t at = mv_block_scan(v, wsum, &total);
+        if (b < nb) pp[b] = carry + at;
+        carry += total;
+    }
+    if (threadIdx.x == 0) {
+        ends[blockIdx.x] = carry;
+        if (!x.first) x.arr[0] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mv_slot_apply(const MvDesc* __restrict__ d,
+                                                          const uint32_t* __restrict__ counts, uint64_t ncalls,
+                                                          const uint64_t* __restrict__ partial, uint32_t nb) {
+    __shared__ uint64_t wsum[kMixWaves];
+    const MvSlot x = mv_slot(d, counts, ncalls, blockIdx.y);
+    const uint64_t b0 = static_cast<uint64_t>(blockIdx.x) * kMvSlotBlock + static_cast<uint64_t>(threadIdx.x) * kMvSlotItems;
+    if (static_cast<uint64_t>(blockIdx.x) * kMvSlotBlock >= x.n) return;  // the whole workgroup
+    uint64_t v[kMvSlotItems], s = 0;
+    for (uint32_t u = 0; u < kMvSlotItems; ++u) {
+        v[u] = b0 + u < x.n ? x.arr[x.first + 1 + b0 + u] : 0;
+        s += v[u];
+    }
+    uint64_t total;
+    uint64_t run = partial[static_cast<uint64_t>(blockIdx.y) * nb + blockIdx.x] + mv_block_scan(s, wsum, &total);
+    for (uint32_t u = 0; u < kMvSlotItems; ++u) {
+        run += v[u];
+        if (b0 + u < x.n) x.arr[x.first + 1 + b0 + u] = run;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_mv_copy(const MvDesc* __restrict__ d, const uint8_t* __restrict__ method,
+                                                    const uint32_t* __restrict__ table, uint64_t rows, uint64_t ncalls,
+                                                    const uint8_t* __restrict__ buf, const uint32_t* __restrict__ srcs) {
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint64_t wsum[kMixWaves];
+    __shared__ uint64_t rel[kBlock + 1];
+    __shared__ const uint8_t* rsrc[kBlock];
+    __shared__ uint64_t rdst[kBlock];
+    const uint32_t K = d->nplans;
+    const uint64_t g = blockIdx.x;
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
+    const bool good = r.cls < K && r.rank < d->room[r.cls];
+    const uint32_t k = good ? r.cls : 0;
+    const uint64_t e = good ? d->first[k] + r.rank : 0;
+    const uint32_t ns = good ? d->nstr[k] : 0;
+    for (uint32_t t = 0; t < d->maxstr; ++t) {
+        uint64_t rl = 0, rd = 0;
+        const uint8_t* rs = nullptr;
+        if (t < ns) {
+            const uint32_t f = d->str_leaf[k * kMvStr + t];
+            const uint64_t a = d->soffs[f][e], b = d->soffs[f][e + 1];
+            const uint64_t room = a < d->scap[f] ? d->scap[f] - a : 0;  // nothing at or past the column's capacity
+            rl = min(b - a, room);
+            rs = buf + srcs[t * ncalls + i];
+            rd = reinterpret_cast<uint64_t>(d->col[f] + a);
+        }
+        uint64_t total;
+        const uint64_t at = mv_block_scan(rl, wsum, &total);
+        rel[threadIdx.x] = at;
+        if (threadIdx.x == 0) rel[kBlock] = total;
+        rsrc[threadIdx.x] = rs;
+        rdst[threadIdx.x] = rd;
+        __syncthreads();
+        mv_copy_runs(rel, rsrc, rdst, nullptr);
+        __syncthreads();
+    }
+}
+
+// ---- host side ----
+
+inline uint32_t mv_tile(uint32_t fmax) {
+    uint32_t t = kMixGranule;
+    while (t > 16 && t * fmax > kMixImage) t >>= 1;
+    return t;
+}
+
+// The plans of one side into d's layout part.  min_fixed_prefix: 4 (request) or
+// 5 (reply).
+int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefix, MvDesc* d) {
+    uint32_t nf = 0, tb = 0, fmax = 0, ns = 0, maxstr = 0;
+    for (int k = 0; k < nplans; ++k)
+        if (!plans[k]) return SRPC_E_INVALID;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        if (p->has_string ? (p->prefix_len < 1 || p->nstrings > static_cast<uint32_t>(kMvStr))
+                          : p->prefix_len < min_fixed_prefix)
+            return SRPC_E_UNSUPPORTED;
+        nf += p->nfields;
+    }
+    if (nf > static_cast<uint32_t>(kMixFields)) return SRPC_E_UNSUPPORTED;
+    nf = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        d->field0[k] = static_cast<uint16_t>(nf);
+        uint32_t t = 0;
+        for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
+            d->size[nf] = static_cast<uint8_t>(p->size[f]);
+            d->leaf_plan[nf] = static_cast<uint8_t>(k);
+            if (p->size[f] == 0) {
+                d->slot_leaf[ns++] = static_cast<uint8_t>(nf);
+                d->str_leaf[k * kMvStr + t++] = static_cast<uint8_t>(nf);
+            }
+        }
+        d->prefix[k] = p->d_prefix;
+        d->var[k] = p->has_string;
+        d->nstr[k] = static_cast<uint8_t>(t);
+        d->F[k] = p->has_string ? 4 + p->fixed_bytes : static_cast<uint32_t>(p->stride);
+        d->prefix_len[k] = static_cast<uint16_t>(p->prefix_len);
+        d->tmpl[k] = static_cast<uint16_t>(tb);
+        tb += (p->prefix_len + 7) & ~7u;
+        fmax = std::max(fmax, d->F[k]);
+        maxstr = std::max(maxstr, t);
+    }
+    d->field0[nplans] = static_cast<uint16_t>(nf);
+    d->nplans = static_cast<uint32_t>(nplans);
+    d->nslots = ns;
+    d->maxstr = maxstr;
+    d->T = mv_tile(fmax);
+    d->tmpl_bytes = tb;
+    return SRPC_OK;
+}
+
+// Columns, offsets arrays and rooms.
+int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
+            const uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap, const uint64_t* h_first,
+            const uint64_t* h_cap, MvDesc* d) {
+    uint32_t nf = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        // a first past the capacity leaves no element, as first == capacity does: every call of
+        // the plan is BAD, and the slot scan's carry stays inside the cap + 1 offsets entries
+        const uint64_t first = std::min(h_first ? h_first[k] : 0, h_cap[k]);
+        const uint64_t room = h_cap[k] - first;
+        if (!d_cols[k] || (p->has_string && (!d_str_offs[k] || (h_str_cap && !h_str_cap[k])))) return SRPC_E_INVALID;
+        for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
+            const void* c = d_cols[k][f];
+            const bool str = p->size[f] == 0;
+            const uint64_t* so = str ? d_str_offs[k][f] : nullptr;
+            if (str && !so) return SRPC_E_INVALID;
+            if (room && !c && !str) return SRPC_E_INVALID;
+            if (!aligned(c, 16) || !aligned(so, 8)) return SRPC_E_ALIGN;
+            d->col[nf] = static_cast<uint8_t*>(const_cast<void*>(c));
+            d->soffs[nf] = const_cast<uint64_t*>(so);
+            d->scap[nf] = str && h_str_cap ? h_str_cap[k][f] : 0;
+        }
+        d->first[k] = first;
+        d->room[k] = static_cast<uint32_t>(std::min<uint64_t>(room, 0xffffffffull));
+    }
+    return SRPC_OK;
+}
+
+// Scratch: desc | gsum[rows + 1] | counts[kMixPlans] | partial[nslots * nb] | srcs[maxstr * ncalls]
+struct MvScratch {
+    uint64_t gsum, counts, partial, srcs, bytes;
+    uint32_t nb;
+};
+
+inline MvScratch mv_scratch(const MvDesc& d, uint64_t ncalls) {
+    MvScratch s;
+    s.nb = static_cast<uint32_t>(std::max<uint64_t>(1, (ncalls + kMvSlotBlock - 1) / kMvSlotBlock));
+    uint64_t at = kMvChunks * kMvChunk;
+    s.gsum = at;
+    at += 8 * (mix_rows(ncalls) + 1);
+    s.counts = at;
+    at += 4 * kMixPlans;
+    s.partial = at;
+    at += 8ull * d.nslots * s.nb;
+    s.srcs = at;
+    at += (4ull * d.maxstr * ncalls + 7) & ~7ull;
+    s.bytes = at;
+    return s;
+}
+
+inline size_t mv_lds(const MvDesc& d) { return kMixImage + 16 + d.tmpl_bytes + 16; }
+
+int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) {
+    for (uint32_t c = 0; c < kMvChunks; ++c) {
+        MvChunk ch;
+        const size_t at = static_cast<size_t>(c) * kMvChunk;
+        const size_t nbytes = std::min<size_t>(kMvChunk, sizeof(MvDesc) - at);
+        std::memset(&ch, 0, sizeof ch);
+        std::memcpy(&ch, reinterpret_cast<const uint8_t*>(&d) + at, nbytes);
+        launch(k_mv_upload, dim3(1), dim3(128), 0, s, ch, reinterpret_cast<uint4*>(static_cast<uint8_t*>(d_scratch) + at),
+               static_cast<uint32_t>(nbytes / 16));
+    }
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+}  // namespace
+}  // namespace srpc_impl
+
+using namespace srpc_impl;
+
+extern "C" {
+
+int srpc_frames_mixed_var_scratch_bytes(const srpc_plan* const* plans, int nplans, uint64_t ncalls, uint64_t* out) {
+    if (!plans || !out || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32)) return SRPC_E_INVALID;
+    MvDesc d{};
+    if (int rc = mv_plans(plans, nplans, 4, &d)) return rc;
+    *out = mv_scratch(d, ncalls).bytes;
+    return SRPC_OK;
+}
+
+int srpc_frames_mixed_var_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile,
+                               uint32_t* image_bytes) {
+    if (!plans || !calls_per_tile || !image_bytes || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    MvDesc d{};
+    if (int rc = mv_plans(plans, nplans, 4, &d)) return rc;
+    *calls_per_tile = d.T;
+    *image_bytes = kMixImage;
+    return SRPC_OK;
+}
+
+int srpc_frames_pack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans, const void* const* const* d_cols,
+                                        const uint64_t* const* const* d_str_offs, const uint64_t* h_first,
+                                        const uint64_t* h_cap, const uint8_t* d_method, const void* d_index,
+                                        uint64_t ncalls, uint8_t* d_out, uint64_t out_cap, uint32_t* d_offs,
+                                        uint64_t* d_total, srpc_unpack_status* d_status, void* d_scratch,
+                                        uint64_t scratch_bytes, void* stream) {
+    const TimedCall timed;
+    // the arguments themselves are checked before any plan is read
+    if (!req_plans || !d_cols || !d_str_offs || !h_cap || !d_index || !d_offs || !d_total || !d_scratch || nplans <= 0 ||
+        nplans > kMixPlans || ncalls >= (1ull << 32) || out_cap >= (1ull << 32) || (ncalls && (!d_method || !d_out)))
+        return SRPC_E_INVALID;
+    static thread_local MvDesc d;
+    d = MvDesc{};
+    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
+    if (!aligned(d_out, 16) || !aligned(d_index, 8) || !aligned(d_scratch, 8) || !aligned(d_total, 8) ||
+        !aligned(d_offs, 4))
+        return SRPC_E_ALIGN;
+    if (int rc = mv_cols(req_plans, nplans, d_cols, d_str_offs, nullptr, h_first, h_cap, &d)) return rc;
+    const MvScratch sc = mv_scratch(d, ncalls);
+    if (scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
+    auto s = static_cast<hipStream_t>(stream);
+    auto* base = static_cast<uint8_t*>(d_scratch);
+    const auto* dd = reinterpret_cast<const MvDesc*>(base);
+    auto* gsum = reinterpret_cast<uint64_t*>(base + sc.gsum);
+    const auto* table = static_cast<const uint32_t*>(d_index);
+    const uint64_t rows = mix_rows(ncalls);
+    if (int rc = mv_upload(d, d_scratch, s)) return rc;
+    if (rows)
+        launch(k_mv_sizes, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, dd, d_method, table, rows, ncalls, gsum);
+    launch(k_mv_scan, dim3(1), dim3(kMvScanBlock), 0, s, gsum, rows, ncalls, out_cap, d_offs, d_total);
+    if (ncalls)
+        launch(k_mv_pack, dim3(static_cast<uint32_t>((ncalls + d.T - 1) / d.T)), dim3(kBlock), mv_lds(d), s, dd, d_method,
+               table, rows, ncalls, gsum, d_out, out_cap, d_offs, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                         uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                         const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                         uint8_t unanswered_code, void* const* const* d_cols,
+                                         uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap,
+                                         const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                         uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
+                                         uint64_t scratch_bytes, void* stream) {
+    const TimedCall timed;
+    if (!reply_plans || !d_cols || !d_str_offs || !h_str_cap || !h_cap || !d_index || !d_codes || !d_ends || !d_scratch ||
+        nplans <= 0 || nplans > kMixPlans || nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) ||
+        (ncalls && !d_method) || (nframes && (!d_buf || !d_offs)))
+        return SRPC_E_INVALID;
+    static thread_local MvDesc d;
+    d = MvDesc{};
+    if (int rc = mv_plans(reply_plans, nplans, 5, &d)) return rc;
+    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_scratch, 8) || !aligned(d_ends, 8) ||
+        !aligned(d_offs, 4))
+        return SRPC_E_ALIGN;
+    if (int rc = mv_cols(reply_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
+                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d))
+        return rc;
+    const MvScratch sc = mv_scratch(d, ncalls);
+    if (scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
+    auto s = static_cast<hipStream_t>(stream);
+    auto* base = static_cast<uint8_t*>(d_scratch);
+    const auto* dd = reinterpret_cast<const MvDesc*>(base);
+    auto* counts = reinterpret_cast<uint32_t*>(base + sc.counts);
+    auto* partial = reinterpret_cast<uint64_t*>(base + sc.partial);
+    auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
+    const auto* table = static_cast<const uint32_t*>(d_index);
+    const uint64_t rows = mix_rows(ncalls);
+    if (d_status) hipLaunchKernelGGL(k_mv_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    if (int rc = mv_upload(d, d_scratch, s)) return rc;
+    if (ncalls)
+        launch(k_mv_parse, dim3(static_cast<uint32_t>((ncalls + d.T - 1) / d.T)), dim3(kBlock), mv_lds(d), s, dd, d_method,
+               table, rows, ncalls, d_buf, buf_len, d_offs, nframes, static_cast<uint32_t>(unanswered_code), d_codes, srcs,
+               counts, d_status);
+    if (d.nslots) {
+        launch(k_mv_slot_reduce, dim3(sc.nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb);
+        launch(k_mv_slot_partials, dim3(d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb, d_ends);
+        launch(k_mv_slot_apply, dim3(sc.nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb);
+        if (ncalls)
+            launch(k_mv_copy, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, dd, d_method, table, rows, ncalls,
+                   d_buf, srcs);
+    }
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+}  // extern "C"

@@ -530,7 +530,71 @@ class MixedFrames:
                                                            _stream(stream))
 
 
+class MixedVarFrames:
+    """A batch of calls of several methods in call order, string-bodied ones
+    included (srpc_frames_pack_requests_mixed_var / _unpack_replies_mixed_var;
+    the index is ``MixedFrames.index``).  ``plans``: GpuPackers -- a fixed-size
+    one with a framed prefix, a string one with the unframed prefix
+    (``request_prefix`` / ``response_prefix``).  ``cols[k]`` are plan k's
+    columns, ``str_offs[k]`` its per-leaf offsets arrays (None for fixed leaves;
+    None for a fixed plan).  Every call returns the C status (negative: refused,
+    nothing launched)."""
+
+    def __init__(self, plans: Sequence["GpuPacker"]):
+        self.plans = list(plans)
+        self.k = len(self.plans)
+        self._plans = (C.c_void_p * self.k)(*[p._h.value for p in self.plans])
+
+    def scratch_bytes(self, ncalls: int) -> int:
+        out = C.c_uint64()
+        check(_lib.lib().srpc_frames_mixed_var_scratch_bytes(self._plans, self.k, ncalls, C.byref(out)),
+              "srpc_frames_mixed_var_scratch_bytes")
+        return out.value
+
+    @property
+    def tile(self) -> tuple[int, int]:
+        """(calls per workgroup tile, bytes of its LDS image window)."""
+        t, img = C.c_uint32(), C.c_uint32()
+        check(_lib.lib().srpc_frames_mixed_var_tile(self._plans, self.k, C.byref(t), C.byref(img)),
+              "srpc_frames_mixed_var_tile")
+        return t.value, img.value
+
+    def _table(self, rows, conv, ctype):
+        keep = [None if r is None else (ctype * len(r))(*[conv(x) for x in r]) for r in rows]
+        arr = (C.c_void_p * self.k)(*[None if a is None else C.cast(a, C.c_void_p).value for a in keep])
+        return arr, keep
+
+    def _args(self, cols, str_offs, first, cap):
+        c_arr, k1 = self._table(cols, _dptr, C.c_void_p)
+        s_arr, k2 = self._table(str_offs, lambda x: None if x is None else _dptr(x), C.c_void_p)
+        self._keep = (k1, k2)
+        h_first = None if first is None else (C.c_uint64 * self.k)(*[int(x) for x in first])
+        h_cap = (C.c_uint64 * self.k)(*[int(x) for x in cap])
+        return c_arr, s_arr, h_first, h_cap
+
+    def pack(self, cols, str_offs, first, cap, method, index, ncalls: int, out, out_cap: int, offs, total, status,
+             scratch, scratch_bytes: int, stream=None) -> int:
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        return _lib.lib().srpc_frames_pack_requests_mixed_var(self._plans, self.k, c_arr, s_arr, h_first, h_cap,
+                                                              _dptr(method), _dptr(index), ncalls, _dptr(out), out_cap,
+                                                              _dptr(offs), _dptr(total), _dptr(status), _dptr(scratch),
+                                                              scratch_bytes, _stream(stream))
+
+    def unpack(self, buf, buf_len: int, offs, nframes: int, method, index, ncalls: int, unanswered: int, cols,
+               str_offs, str_cap, first, cap, codes, ends, status, scratch, scratch_bytes: int, stream=None) -> int:
+        """str_cap[k]: per leaf, the bytes a string column has (ignored for fixed
+        leaves; None for a fixed plan)."""
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        cap_arr, k3 = self._table(str_cap, lambda x: 0 if x is None else int(x), C.c_uint64)
+        self._keep += (k3,)
+        return _lib.lib().srpc_frames_unpack_replies_mixed_var(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                               nframes, _dptr(method), _dptr(index), ncalls, unanswered,
+                                                               c_arr, s_arr, cap_arr, h_first, h_cap, _dptr(codes),
+                                                               _dptr(ends), _dptr(status), _dptr(scratch),
+                                                               scratch_bytes, _stream(stream))
+
+
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
            "fill_splitmix_i32", "time_next_call", "framed_request_prefix", "framed_response_prefix",
-           "FrameClassifier", "frame_var", "MixedFrames", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
+           "FrameClassifier", "frame_var", "MixedFrames", "MixedVarFrames", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
            "RPC_SUCCESS", "RPC_ERR_FUNCTION_NOT_REGISTERED", "RPC_ERR_RECV_TIMEOUT"]
