@@ -208,7 +208,10 @@ int srpc_gpu_unpack(const srpc_plan* plan, const uint8_t* d_wire, uint64_t wire_
  * as raw bytes: record r's leaf field f is at d_records + r * record_stride +
  * field_offsets[f] (host array, nfields entries, T::fields order, nested
  * messages flattened), naturally aligned (offset, stride and base multiples of
- * the field size: SRPC_E_ALIGN otherwise).  Wire bytes are those of
+ * the field size: SRPC_E_ALIGN otherwise); no two fields may share a byte of
+ * the struct (SRPC_E_INVALID: each leaf has its own bytes in a C++ object).
+ * Any stride up to 2^32 - 1 is taken: a struct too wide for a tile of 16 in a
+ * workgroup's LDS moves field by field.  Wire bytes are those of
  * srpc_gpu_pack / srpc_gpu_unpack.  unpack_aos writes only the leaf fields'
  * bytes of each struct; every other byte (padding, a vtable pointer) keeps
  * what d_records held.  srpc::gpu::batch_packer<T>::pack_records /

@@ -810,16 +810,28 @@ __global__ __launch_bounds__(kBlock) void k_unpack_aos_staged(AosArgs a, const u
 
 // Staged-kernel tiling: R (a multiple of 16) records whose two images fill
 // about kAosTileBytes of LDS; returns the LDS bytes, sets a->R / a->simg.
+// R stops at 16, so the bytes grow with the struct stride from there (16
+// records of 1536 bytes and up): the callers compare them with the device's
+// per-workgroup LDS and take the per-field kernels, whose LDS holds wire
+// records only, when the tile does not fit.
 constexpr uint32_t kAosTileBytes = 24 * 1024;  // (12 / 16 KiB measured slower: profiles/r04_aos_lay_ab.log)
-uint32_t staged_tiling(AosArgs* a) {
-    const uint32_t per = a->ident ? a->wstride : a->wstride + a->rstride;
-    uint32_t R = std::max<uint32_t>(16, (kAosTileBytes / per) & ~15u);
+uint64_t staged_tiling(AosArgs* a) {
+    const uint64_t per = a->ident ? a->wstride : static_cast<uint64_t>(a->wstride) + a->rstride;
+    const uint32_t R = std::max<uint32_t>(16, static_cast<uint32_t>(kAosTileBytes / per) & ~15u);
     a->R = R;
     const uint32_t wimg = (R * a->wstride + 15) & ~15u;
     a->simg = a->ident ? 0 : wimg;
-    const uint32_t end = a->ident ? wimg : wimg + ((R * a->rstride + 15) & ~15u);
-    a->fill_at = end + (a->prefix_len ? 2 * a->L : 0);
-    return a->fill_at + (a->fill ? kAosFillMax : 0);
+    const uint64_t end = a->ident ? wimg : wimg + ((static_cast<uint64_t>(R) * a->rstride + 15) & ~15ull);
+    const uint64_t fill_at = end + (a->prefix_len ? 2 * a->L : 0);
+    a->fill_at = static_cast<uint32_t>(std::min<uint64_t>(fill_at, UINT32_MAX));  // (a tile that large never launches)
+    return fill_at + (a->fill ? kAosFillMax : 0);
+}
+
+// The staged tile of this layout fits a workgroup's LDS on the plan's device.
+bool staged_fits(const srpc_plan* p, AosArgs* a, uint32_t* lds) {
+    const uint64_t need = staged_tiling(a);
+    *lds = static_cast<uint32_t>(std::min<uint64_t>(need, UINT32_MAX));
+    return need <= p->lds_max;
 }
 
 __global__ void k_aos_status(srpc_unpack_status* st, uint32_t flags, uint64_t first_bad) {
@@ -841,6 +853,13 @@ int aos_args(const srpc_plan* p, const void* recs, uint64_t stride, const uint32
         a->size[f] = sz;
         a->woff[f] = p->off[f];
     }
+    // no two fields share a byte: cover's sum below and the staged unpack
+    // (which skips reading a struct tile the fields cover) rest on it
+    uint64_t iv[kMaxFields];  // (offset << 8) | size, sorted by offset
+    for (uint32_t f = 0; f < p->nfields; ++f) iv[f] = (static_cast<uint64_t>(offs[f]) << 8) | p->size[f];
+    std::sort(iv, iv + p->nfields);
+    for (uint32_t f = 1; f < p->nfields; ++f)
+        if ((iv[f - 1] >> 8) + (iv[f - 1] & 0xff) > (iv[f] >> 8)) return SRPC_E_INVALID;
     a->period = p->d_period;
     a->nfields = p->nfields;
     a->wstride = static_cast<uint32_t>(p->stride);
@@ -853,8 +872,8 @@ int aos_args(const srpc_plan* p, const void* recs, uint64_t stride, const uint32
         a->ident = a->ident && offs[f] == p->off[f];
         covered += p->size[f];
     }
-    // fields do not overlap (each has its own bytes in a C++ struct), so they
-    // cover the struct when their sizes add up to its stride
+    // fields do not overlap (checked above), so they cover the struct when
+    // their sizes add up to its stride
     a->cover = covered == stride;
     // the body as one run of the struct: every field at the same shift from its wire offset
     a->boff = -1;
@@ -916,8 +935,8 @@ int srpc_gpu_pack_aos(const srpc_plan* p, const void* d_records, uint64_t record
     if (!g_aos_unstaged && !g_aos_nolay &&
         launch_aos_lay(a, true, static_cast<const uint8_t*>(d_records), d_wire, n, static_cast<hipStream_t>(stream)))
         return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
-    if (aligned(d_records, 16) && !g_aos_unstaged) {
-        const uint32_t lds = staged_tiling(&a);
+    uint32_t lds = 0;
+    if (aligned(d_records, 16) && !g_aos_unstaged && staged_fits(p, &a, &lds)) {
         const uint64_t tiles = (n + a.R - 1) / a.R;
         if (tiles > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
         launch(k_pack_aos_staged, dim3(static_cast<uint32_t>(tiles)), dim3(kBlock), lds, static_cast<hipStream_t>(stream),
@@ -967,8 +986,8 @@ static int unpack_aos(const srpc_plan* p, const uint8_t* d_wire, uint64_t wire_l
     if (n_fit && !g_aos_unstaged && !g_aos_nolay && umode &&
         launch_aos_lay(a, false, d_wire, static_cast<uint8_t*>(d_records), n_fit, s, umode))
         return hipGetLastError() == hipSuccess ? ret : SRPC_E_HIP;
-    if (n_fit && aligned(d_records, 16) && !g_aos_unstaged) {
-        const uint32_t lds = staged_tiling(&a);
+    uint32_t lds = 0;
+    if (n_fit && aligned(d_records, 16) && !g_aos_unstaged && staged_fits(p, &a, &lds)) {
         const uint64_t tiles = (n_fit + a.R - 1) / a.R;
         if (tiles > 0x7fffffffull) return SRPC_E_UNSUPPORTED;
         launch(k_unpack_aos_staged, dim3(static_cast<uint32_t>(tiles)), dim3(kBlock), lds, s, a, d_wire,

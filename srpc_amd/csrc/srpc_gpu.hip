@@ -1112,6 +1112,14 @@ void set_rec(srpc_plan* p, int mode) {
     p->rec_unpack = p->rec_id >= 0 && (mode == 2 || rec_default(p->rec_id, false));
 }
 
+// LDS bytes a workgroup of the plan's device may use (the default stays when
+// the runtime does not say).
+void query_lds_max(srpc_plan* p) {
+    int lds_max = 0;
+    if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, p->device) == hipSuccess && lds_max > 0)
+        p->lds_max = static_cast<uint32_t>(lds_max);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1179,10 +1187,7 @@ int srpc_plan_create(const srpc_schema_desc* d, int device, srpc_plan** out) {
             delete p;
             return SRPC_E_HIP;
         }
-        int lds_max = 0;
-        if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess &&
-            lds_max > 0)
-            p->lds_max = static_cast<uint32_t>(lds_max);
+        query_lds_max(p);
         *out = p;
         return SRPC_OK;
     }
@@ -1199,6 +1204,7 @@ int srpc_plan_create(const srpc_schema_desc* d, int device, srpc_plan** out) {
         delete p;
         return SRPC_E_HIP;
     }
+    query_lds_max(p);  // aos.hip: the staged tile of a wide struct against it
     if (p->dword_ok) p->dv = default_dword_variant(static_cast<uint32_t>(o / 4));
     // TILE unpack image: 32 KiB, within 3 % of the best of 4-32 KiB for every
     // record width swept on MI355X (profiles/r01_sweep_tile.log).

@@ -99,14 +99,34 @@ static int run(srpc::gpu::batch_packer<T>& bp, size_t n, Fill fill, Eq eq, Emit 
     CHECK(bp.pack_records(drecs, n, dw, want.size()) == SRPC_OK);
     HIPCHECK(hipMemcpy(got.data(), dw, got.size(), hipMemcpyDeviceToHost));
     CHECK(got == want);
+    // the bytes of a T its leaf fields own (leaf_offsets + the fields' sizes);
+    // every other one -- the vtable pointer, a nested message's, padding --
+    // must come back as it went
+    std::vector<bool> leaf(sizeof(T), false);
+    {
+        const std::vector<uint32_t> offs = srpc::gpu::leaf_offsets<T>();
+        T probe{};
+        size_t f = 0;
+        srpc::gpu::for_each_leaf<T>(probe, [&](const auto& v) {
+            for (size_t b = 0; b < sizeof(v); ++b) leaf[offs[f] + b] = true;
+            ++f;
+        });
+        CHECK(f == offs.size());
+    }
     std::vector<T> out2(n);  // default objects: their vtable pointers travel to the device and back
-    HIPCHECK(hipMemcpy(drecs, out2.data(), n * sizeof(T), hipMemcpyHostToDevice));
+    std::vector<uint8_t> before(n * sizeof(T)), after(n * sizeof(T));
+    std::memcpy(before.data(), static_cast<const void*>(out2.data()), before.size());
+    HIPCHECK(hipMemcpy(drecs, before.data(), n * sizeof(T), hipMemcpyHostToDevice));
     CHECK(bp.unpack_records(dw, want.size(), n, drecs, st) == SRPC_OK);
-    HIPCHECK(hipMemcpy(static_cast<void*>(out2.data()), drecs, n * sizeof(T), hipMemcpyDeviceToHost));
+    HIPCHECK(hipMemcpy(after.data(), drecs, n * sizeof(T), hipMemcpyDeviceToHost));
+    std::memcpy(static_cast<void*>(out2.data()), after.data(), after.size());
     HIPCHECK(hipMemcpy(&hs, st, sizeof(hs), hipMemcpyDeviceToHost));
     CHECK(hs.flags == 0);
     same = true;
     for (size_t i = 0; same && i < n; ++i) same = eq(out2[i], recs[i]);
+    CHECK(same);
+    same = true;
+    for (size_t i = 0; same && i < before.size(); ++i) same = leaf[i % sizeof(T)] || after[i] == before[i];
     CHECK(same);
     // into fresh objects: the device array holds garbage, every non-field
     // byte (the vtable pointer) comes from a T{} (unpack_records_fresh)
@@ -121,6 +141,13 @@ static int run(srpc::gpu::batch_packer<T>& bp, size_t n, Fill fill, Eq eq, Emit 
             same = eq(out3[i], recs[i]) &&
                    (!std::is_polymorphic_v<T> || std::memcmp(static_cast<const void*>(&out3[i]),
                                                              static_cast<const void*>(&proto), sizeof(void*)) == 0);
+        CHECK(same);
+        // byte-wise: whatever no leaf field owns is proto's (the inner
+        // message's vtable pointer and the padding included)
+        HIPCHECK(hipMemcpy(after.data(), drecs, n * sizeof(T), hipMemcpyDeviceToHost));
+        const auto* pb = reinterpret_cast<const uint8_t*>(&proto);
+        same = true;
+        for (size_t i = 0; same && i < after.size(); ++i) same = leaf[i % sizeof(T)] || after[i] == pb[i % sizeof(T)];
         CHECK(same);
     }
     // host-terminated (ABI 7): pinned host columns -> host wire and back,
