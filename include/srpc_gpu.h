@@ -306,8 +306,21 @@ int srpc_gpu_unpack_var_tiled(const srpc_plan* plan, const uint8_t* d_wire, uint
  * string past the end) is reported in *d_status as the first bad record
  * (PREFIX or BOUNDS), as orc_unpack / the reference would meet it; its start
  * is d_rec_offs[i] and every later entry is wire_len (those records are
- * BOUNDS too).  Scratch: srpc_plan_var_stream_scratch_bytes (256-byte
- * aligned). */
+ * BOUNDS too).  Nothing of record i is decoded: every record before it is
+ * exact, d_str_offs[f][i] counts the chars of records 0..i-1 and
+ * d_str_offs[f][i+1..n] == d_str_offs[f][i] for every string field f (the
+ * later records hold no chars).  A schema with more than four string fields
+ * is decoded by srpc_gpu_unpack_var over the index built here and follows
+ * the same rule: that decode is given records i..n-1 as empty, and its
+ * status is replaced by the stream's (so a prefix mismatch in record i
+ * decodes none of its fields, unlike a direct srpc_gpu_unpack_var call).
+ * No byte at or past d_wire + wire_len influences any output.
+ * Alignment: d_wire may have ANY alignment (the result is the same bytes
+ * wherever the wire starts); d_rec_offs and every d_str_offs[f] 8 bytes, a
+ * fixed column its field size, a chars column 16 bytes (SRPC_E_ALIGN before
+ * any launch, nothing written).
+ * Scratch: srpc_plan_var_stream_scratch_bytes (256-byte aligned); the result
+ * does not depend on what the scratch held. */
 int srpc_plan_var_stream_scratch_bytes(const srpc_plan* plan, uint64_t n, uint64_t wire_len,
                                        uint64_t* out);
 int srpc_gpu_unpack_var_stream(const srpc_plan* plan, const uint8_t* d_wire, uint64_t wire_len,

@@ -122,6 +122,8 @@ constexpr uint32_t kCtlTot = 4;      // ... str_offs value per string ordinal (k
 constexpr uint32_t kCtlRepair = 8;   // the first scan met a position no table holds: repair, scan again
 constexpr uint32_t kCtlOver = 9;     // blocks whose exit slots overflowed (diagnostics)
 constexpr uint32_t kCtlDone = 10;    // k_sx_groups workgroups done, per pass (2 words): the last runs the scan
+constexpr uint32_t kCtlX = 12;       // ... record T's start (the indexed decode's tail, k_sx_index_tail)
+constexpr uint32_t kCtlFlags = 13;   // ... the status flags of a call that stopped at record T
 constexpr uint32_t kCtlWords = 16;
 
 // stop bits: bit 0 = the chain stopped, bits 1-2 = why (SRPC_STATUS_PREFIX / _BOUNDS)
@@ -2326,11 +2328,14 @@ __device__ void sx_top(const SxArgs& a, const uint8_t* __restrict__ w, const SxS
             S.ctl[kCtlTot + si] = v;
         }
     if (T < n) {
+        const uint32_t kind = (s.stop & 1) ? (s.stop >> 1) & 3 : 0;
+        const uint32_t flags = (kind ? kind : SRPC_STATUS_BOUNDS) | (T + 1 < n ? SRPC_STATUS_BOUNDS : 0);
         S.ctl[kCtlT] = T;
+        S.ctl[kCtlX] = s.x;
+        S.ctl[kCtlFlags] = flags;
         S.ctl[kCtlTailOn] = 1;
         if (kDecode && st) {
-            const uint32_t kind = (s.stop & 1) ? (s.stop >> 1) & 3 : 0;
-            st->flags = (kind ? kind : SRPC_STATUS_BOUNDS) | (T + 1 < n ? SRPC_STATUS_BOUNDS : 0);
+            st->flags = flags;
             st->first_bad_record = T;
         }
     }
@@ -2500,8 +2505,12 @@ __global__ __launch_bounds__(kBlock, 8) void k_sx_decode(SxArgs a, const uint8_t
     if (S.ctl[kCtlTailOn]) {
         const uint64_t T = S.ctl[kCtlT];
         const uint64_t gs = static_cast<uint64_t>(gridDim.x) * kBlock;
+        // (index only, for the indexed decode that follows: records T .. n - 1
+        // empty, so that it reads nothing of the bad record; k_sx_index_tail
+        // writes W afterwards)
+        const uint64_t tail = kDecode ? W : S.ctl[kCtlX];
         for (uint64_t r = T + 1 + b * kBlock + tid; r <= n; r += gs) {
-            a.rec_offs[r] = W;
+            a.rec_offs[r] = tail;
             if (kDecode)
                 for (uint32_t f = 0; f < a.nfields; ++f)
                     if (!a.size[f]) a.soff[f][r] = S.ctl[kCtlTot + a.sord[f]];
@@ -2834,6 +2843,23 @@ __global__ __launch_bounds__(kBlock, 8) void k_sx_decode(SxArgs a, const uint8_t
     SXP(13);
 }
 
+// After the indexed decode of a schema with more string fields than a state
+// carries (srpc_gpu_unpack_var over the index just built): when the stream
+// stopped at record T < n, the index's tail and the status as the stream
+// decode itself leaves them.  The indexed decode saw records T .. n - 1 as
+// empty (BOUNDS: no field, no chars, str_offs[f][T + 1 .. n] = str_offs[f][T]).
+__global__ __launch_bounds__(kBlock) void k_sx_index_tail(const uint64_t* __restrict__ ctl, uint64_t* rec_offs,
+                                                          uint64_t n, uint64_t W, srpc_unpack_status* st) {
+    if (!ctl[kCtlTailOn]) return;
+    const uint64_t T = ctl[kCtlT];
+    const uint64_t gs = static_cast<uint64_t>(gridDim.x) * kBlock;
+    for (uint64_t r = T + 1 + static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; r <= n; r += gs) rec_offs[r] = W;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && st) {
+        st->flags = static_cast<uint32_t>(ctl[kCtlFlags]);
+        st->first_bad_record = T;
+    }
+}
+
 __global__ void k_zero_ctl(uint64_t* ctl) {
     if (threadIdx.x < kCtlWords) ctl[threadIdx.x] = 0;
 }
@@ -2942,7 +2968,9 @@ int srpc_gpu_unpack_var_stream(const srpc_plan* p, const uint8_t* wire, uint64_t
     if (int rc = srpc_plan_var_stream_scratch_bytes(p, n, wire_len, &need)) return rc;
     if (scratch_bytes < need) return SRPC_E_CAPACITY;
     const bool decode = sx_decodes(p);
-    for (uint32_t f = 0; f < p->nfields && decode; ++f) {
+    // (also for the schemas handed on to the indexed decode: it would refuse
+    // them only after the index kernels had written d_rec_offs)
+    for (uint32_t f = 0; f < p->nfields; ++f) {
         if (!cols[f]) return SRPC_E_INVALID;
         if (p->size[f] && !aligned(cols[f], p->size[f])) return SRPC_E_ALIGN;
         if (p->size[f] == 0 && (!str_offs[f] || !aligned(str_offs[f], 8) || !aligned(cols[f], 16))) return SRPC_E_ALIGN;
@@ -3008,8 +3036,13 @@ int srpc_gpu_unpack_var_stream(const srpc_plan* p, const uint8_t* wire, uint64_t
     else if (nc == 2) launch_sx<2, true>(a, wire, S, st, s);
     else launch_sx<3, true>(a, wire, S, st, s);
     if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    if (!decode)  // more string fields than a state carries: the indexed decode over the index just built
-        return srpc_gpu_unpack_var(p, wire, wire_len, n, rec_offs, cols, str_offs, st, scratch, var, stream);
+    if (!decode) {  // more string fields than a state carries: the indexed decode over the index just built
+        if (int rc = srpc_gpu_unpack_var(p, wire, wire_len, n, rec_offs, cols, str_offs, st, scratch, var, stream))
+            return rc;
+        const uint32_t g = static_cast<uint32_t>(std::min<uint64_t>((n + kBlock) / kBlock, 1024));
+        hipLaunchKernelGGL(k_sx_index_tail, dim3(g), dim3(kBlock), 0, s, S.ctl, rec_offs, n, wire_len, st);
+        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
+    }
     return SRPC_OK;
 }
 

@@ -350,7 +350,10 @@ class GpuPacker:
     def unpack_var_stream(self, wire, wire_len: int, n: int, rec_offs, cols: Sequence, str_offs: Sequence,
                           scratch, scratch_bytes: int, status=None, stream=None) -> None:
         """Unpack n records from a concatenated stream with no index (the
-        reference's shared-cursor decode); writes rec_offs[0..n] (async)."""
+        reference's shared-cursor decode); writes rec_offs[0..n] (async).
+        The wire needs no alignment.  When record e is the first the cursor
+        cannot read, nothing of it is decoded: rec_offs[e+1..n] == wire_len
+        and str_offs[f][e+1..n] == str_offs[f][e] (srpc_gpu.h)."""
         check(_lib.lib().srpc_gpu_unpack_var_stream(self._h, _dptr(wire), wire_len, n, _dptr(rec_offs),
                                                     self._cols(cols), self._str_offs(str_offs),
                                                     _dptr(status), _dptr(scratch), scratch_bytes,
