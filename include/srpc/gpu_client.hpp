@@ -28,8 +28,10 @@
 // str(Req::name)`) and framed by srpc_frames_frame_var; a string reply stream
 // is decoded by srpc_frames_unpack_replies_var (reply plan: the unframed `u8
 // code | str(Resp::name)`) into the client's staging, and its chars reach the
-// caller's columns only once their total is known to fit.  A side without
-// strings takes `call`'s path.
+// caller's columns only once their total is known to fit.  Both run one chunk
+// loop (run_calls): each side branches on whether it has strings, and `call` is
+// the case where neither has.  A method's plans are built once (one entry, one
+// cache) whichever form uses it.
 //
 // `call_mixed` takes an ordered sequence of calls over up to 16 fixed-size
 // methods (a trace replayed against a stateful service, a pipeline whose calls
@@ -45,7 +47,16 @@
 // methods, still in call order and one exchange per chunk.  Reply strings go
 // straight to the leg's columns with offsets absolute over the whole call; a
 // column's capacity is never passed, and an overflow throws SRPC_E_CAPACITY
-// once the chunk is accounted for.
+// once the chunk is accounted for.  Both overloads are one chunk loop too: the
+// pack call (and where the chunk's request bytes are read), the decode call and
+// the string capacities are its only branches on `any_var`.
+//
+// Every loop counts a chunk's replies by one rule (tally_replies,
+// reply_walk.hpp): from the codes when the decode flagged nothing, otherwise
+// frame by frame on the host with the judge of its table (judge_reply_fixed,
+// walk_reply_var, judge_reply_mixed), and ends a chunk the same way
+// (end_chunk).  The staging is owning buffers: a grow releases all of it, and
+// each form re-creates what it needs.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -126,7 +137,6 @@ public:
     }
     batch_client(batch_client const&) = delete;
     batch_client& operator=(batch_client const&) = delete;
-    ~batch_client() { release(); }
 
     void set_request_hook(request_hook_t h) { _hook = std::move(h); }
     /// Keep every reply byte received by later calls (reply_bytes()).
@@ -147,88 +157,15 @@ public:
         check(hipSetDevice(_dev));
         entry& e = plans<Req, Resp>(method);
         ensure(e.fin, e.fout);
-        call_stats st;
-        st.calls = n;
-        std::vector<const void*> rq(e.req_size.size());
-        std::vector<void*> rs(e.resp_size.size());
-        for (uint64_t lo = 0; lo < n; lo += _max) {
-            const uint64_t m = std::min(_max, n - lo);
-            st.chunks += 1;
-            for (size_t f = 0; f < rq.size(); ++f) rq[f] = static_cast<const uint8_t*>(d_req_cols[f]) + lo * e.req_size[f];
-            for (size_t f = 0; f < rs.size(); ++f) rs[f] = static_cast<uint8_t*>(d_resp_cols[f]) + lo * e.resp_size[f];
-            frame_walk w;
-            if (!_eof) {
-                auto t0 = clock::now();
-                check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _d_out, m * e.fin, stream), "srpc_gpu_pack");
-                check(hipMemcpyAsync(_h_out, _d_out, m * e.fin, hipMemcpyDeviceToHost, stream));
-                check(hipStreamSynchronize(stream));
-                st.gpu_seconds += secs(t0);
-                if (_hook) _hook(_h_out, lo, m, e.fin);
-            }
-            w = exchange(m, m * e.fin, e.fout, st);
-            auto t0 = clock::now();
-            const uint64_t nf = w.nframes;
-            if (nf) {
-                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
-                const bool uniform = w.all_full;
-                if (!uniform) check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
-                st.uniform_chunks += uniform;
-                check_srpc(srpc_frames_unpack_replies(e.resp->get(), _d_in, w.walked, uniform ? nullptr : _d_offs, nf,
-                                                      rs.data(), d_codes + lo, _d_status, stream),
-                           "srpc_frames_unpack_replies");
-                check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
-                check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
-            }
-            if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields
-                check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
-                for (size_t f = 0; f < rs.size(); ++f)
-                    check(hipMemsetAsync(static_cast<uint8_t*>(rs[f]) + nf * e.resp_size[f], 0, (m - nf) * e.resp_size[f], stream));
-                st.unanswered += m - nf;
-            }
-            check(hipStreamSynchronize(stream));
-            st.gpu_seconds += secs(t0);
-            if (nf) count(e.fout, e.resp_prefix, w, st);
-            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
-            // bytes after the chunk's last frame belong to the next chunk's replies
-            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
-            _have -= w.walked;
-        }
-        _last = st;
-        return st;
+        return run_calls(e, d_req_cols, nullptr, n, d_resp_cols, nullptr, nullptr, d_codes, stream);
     }
 
     /// The same from and to host records (host_columns<T> transposes them).
     template <SrpcMessage Req, SrpcMessage Resp>
     std::vector<response_t<Resp>> call(std::string const& method, std::vector<Req> const& reqs) {
         check(hipSetDevice(_dev));
-        (void)plans<Req, Resp>(method);  // string schemas are refused before anything is allocated
-        const uint64_t n = reqs.size();
-        host_columns<Req> in;
-        in.scatter(reqs);
-        host_columns<Resp> out;
-        out.n = n;
-        {
-            Resp probe{};
-            for_each_leaf<Resp>(probe, [&](const auto& v) { out.col.emplace_back(n * sizeof(v)); });
-            out.offs.resize(out.col.size());
-        }
-        device_buffers rq(in.col), rs(out.col);
-        std::vector<uint8_t> codes(n);
-        device_buffers dc(std::vector<std::vector<uint8_t>>{codes});
-        for (size_t f = 0; f < in.col.size(); ++f)
-            check(hipMemcpy(rq.p[f], in.col[f].data(), in.col[f].size(), hipMemcpyHostToDevice));
-        call<Req, Resp>(method, rq.p.data(), n, rs.p.data(), static_cast<uint8_t*>(dc.p[0]));
-        for (size_t f = 0; f < out.col.size(); ++f)
-            check(hipMemcpy(out.col[f].data(), rs.p[f], out.col[f].size(), hipMemcpyDeviceToHost));
-        check(hipMemcpy(codes.data(), dc.p[0], n, hipMemcpyDeviceToHost));
-        std::vector<Resp> vals;
-        out.gather(vals);
-        std::vector<response_t<Resp>> res(n);
-        for (uint64_t i = 0; i < n; ++i) {
-            res[i].set_code(static_cast<rpc_status_code>(codes[i]));
-            res[i].set_value(vals[i]);
-        }
-        return res;
+        // string schemas are refused before anything is allocated
+        return call_records<Req, Resp>(plans<Req, Resp>(method), method, reqs, nullptr);
     }
 
     /// n calls of a method whose Req and/or Resp has string fields.  The
@@ -250,137 +187,14 @@ public:
                         const uint64_t* resp_cap, uint8_t* d_codes, var_call_limits lim = {},
                         hipStream_t stream = nullptr) {
         check(hipSetDevice(_dev));
-        var_entry& e = var_plans<Req, Resp>(method);
-        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
-        for (size_t f = 0; f < ns; ++f)
+        entry& e = any_plans<Req, Resp>(method);
+        for (size_t f = 0; f < e.resp_size.size(); ++f)
             if (e.resp_size[f] && n * e.resp_size[f] > resp_cap[f])
                 throw plan_error("batch_client::call_var (response column)", SRPC_E_CAPACITY);
         ensure_bytes(_max * (e.req_var ? lim.max_request_bytes : e.fin) + 4096,
                      _max * (e.resp_var ? lim.max_reply_bytes : e.fout) + 4096);
         ensure_var(e);
-        call_stats st;
-        st.calls = n;
-        std::vector<const void*> rq(nq);
-        std::vector<const uint64_t*> rqo(nq, nullptr);
-        std::vector<void*> rs(ns);
-        std::vector<uint64_t*> rso(ns, nullptr);
-        std::vector<uint64_t> base(ns, 0);  // chars of response field f in the chunks before this one
-        for (uint64_t lo = 0; lo < n; lo += _max) {
-            const uint64_t m = std::min(_max, n - lo);
-            st.chunks += 1;
-            uint64_t total = 0;  // the chunk's request bytes
-            if (!_eof) {
-                auto t0 = clock::now();
-                for (size_t f = 0; f < nq; ++f) {
-                    const bool str = e.req_size[f] == 0;
-                    // a string column's offsets are absolute: its chars stay where they are
-                    rq[f] = str ? d_req_cols[f] : static_cast<const uint8_t*>(d_req_cols[f]) + lo * e.req_size[f];
-                    rqo[f] = str ? d_req_str_offs[f] + lo : nullptr;
-                }
-                if (e.req_var) {
-                    check_srpc(srpc_gpu_pack_var(e.req->get(), rq.data(), rqo.data(), m, _d_wire, _out_cap, _d_rec,
-                                                 _d_status, _d_vscratch, _vscratch_cap, stream),
-                               "srpc_gpu_pack_var");
-                    check_srpc(srpc_frames_frame_var(_d_wire, _d_rec, m, _d_out, _out_cap, _d_status, stream),
-                               "srpc_frames_frame_var");
-                    check(hipMemcpyAsync(_h_ends, _d_rec + m, 8, hipMemcpyDeviceToHost, stream));
-                    check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
-                    check(hipStreamSynchronize(stream));
-                    total = _h_ends[0] + 4 * m;
-                    if (total > _out_cap || _h_status->flags)
-                        throw plan_error("batch_client::call_var (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
-                } else {
-                    total = m * e.fin;
-                    check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _d_out, total, stream), "srpc_gpu_pack");
-                }
-                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
-                check(hipStreamSynchronize(stream));
-                st.gpu_seconds += secs(t0);
-                if (_hook) _hook(_h_out, lo, m, e.req_var ? 0 : e.fin);
-            }
-            const frame_walk w = exchange(m, total, e.resp_var ? 0 : e.fout, st);
-            auto t0 = clock::now();
-            const uint64_t nf = w.nframes;
-            for (size_t f = 0; f < ns; ++f) {
-                const bool str = e.resp_size[f] == 0;
-                // string fields are decoded into the client's staging first
-                rs[f] = str ? static_cast<void*>(_d_schars[e.resp_sidx[f]])
-                            : static_cast<uint8_t*>(d_resp_cols[f]) + lo * e.resp_size[f];
-                rso[f] = str ? _d_soffs[e.resp_sidx[f]] : nullptr;
-            }
-            if (nf) {
-                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
-                const bool uniform = !e.resp_var && w.all_full;
-                if (!uniform) check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
-                st.uniform_chunks += uniform;
-                if (e.resp_var) {
-                    check_srpc(srpc_frames_unpack_replies_var(e.resp->get(), _d_in, w.walked, _d_offs, nf, rs.data(),
-                                                              rso.data(), d_codes + lo, _d_status, _d_vscratch,
-                                                              _vscratch_cap, stream),
-                               "srpc_frames_unpack_replies_var");
-                    for (uint32_t t = 0; t < e.resp_nstr; ++t)
-                        check(hipMemcpyAsync(_h_soffs + t * (_max + 1), _d_soffs[t], 8 * (nf + 1), hipMemcpyDeviceToHost,
-                                             stream));
-                } else {
-                    check_srpc(srpc_frames_unpack_replies(e.resp->get(), _d_in, w.walked, uniform ? nullptr : _d_offs,
-                                                          nf, rs.data(), d_codes + lo, _d_status, stream),
-                               "srpc_frames_unpack_replies");
-                }
-                check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
-                check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
-            }
-            if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields (empty strings: below)
-                check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
-                for (size_t f = 0; f < ns; ++f)
-                    if (e.resp_size[f])
-                        check(hipMemsetAsync(static_cast<uint8_t*>(rs[f]) + nf * e.resp_size[f], 0,
-                                             (m - nf) * e.resp_size[f], stream));
-                st.unanswered += m - nf;
-            }
-            check(hipStreamSynchronize(stream));
-            // the chunk's chars, now that their totals are known: they must fit
-            // the caller's columns before a byte of them is written there
-            bool overflow = false;
-            for (size_t f = 0; f < ns; ++f) {
-                if (e.resp_size[f]) continue;
-                const uint32_t t = e.resp_sidx[f];
-                uint64_t* ho = _h_soffs + t * (_max + 1);
-                const uint64_t chars = nf ? ho[nf] : 0;
-                if (chars > resp_cap[f] || base[f] > resp_cap[f] - chars) {
-                    overflow = true;  // thrown once the chunk's bytes are accounted for
-                    continue;
-                }
-                if (chars)
-                    check(hipMemcpyAsync(static_cast<uint8_t*>(d_resp_cols[f]) + base[f], _d_schars[t], chars,
-                                         hipMemcpyDeviceToDevice, stream));
-                // absolute offsets; unanswered calls are empty strings at the chunk's end
-                if (!nf) ho[0] = 0;
-                for (uint64_t j = 0; j <= nf; ++j) ho[j] += base[f];
-                for (uint64_t j = nf + 1; j <= m; ++j) ho[j] = base[f] + chars;
-                check(hipMemcpyAsync(d_resp_str_offs[f] + lo, ho, 8 * (m + 1), hipMemcpyHostToDevice, stream));
-                base[f] += chars;
-            }
-            if (e.resp_var) check(hipStreamSynchronize(stream));
-            st.gpu_seconds += secs(t0);
-            if (nf) {
-                if (e.resp_var) count_var(e, w, st);
-                else count(e.fout, e.resp_prefix, w, st);
-            }
-            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
-            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
-            _have -= w.walked;
-            if (overflow) {
-                _last = st;
-                throw plan_error("batch_client::call_var (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
-            }
-        }
-        if (!n) {  // no chunk ran: the offsets of no calls
-            for (size_t f = 0; f < ns; ++f)
-                if (!e.resp_size[f]) check(hipMemsetAsync(d_resp_str_offs[f], 0, 8, stream));
-            check(hipStreamSynchronize(stream));
-        }
-        _last = st;
-        return st;
+        return run_calls(e, d_req_cols, d_req_str_offs, n, d_resp_cols, d_resp_str_offs, resp_cap, d_codes, stream);
     }
 
     /// The same from and to host records (host_columns<T> transposes them,
@@ -390,55 +204,7 @@ public:
     std::vector<response_t<Resp>> call_var(std::string const& method, std::vector<Req> const& reqs,
                                            var_call_limits lim = {}) {
         check(hipSetDevice(_dev));
-        var_entry& e = var_plans<Req, Resp>(method);
-        const uint64_t n = reqs.size();
-        host_columns<Req> in;
-        in.scatter(reqs);
-        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
-        device_allocs mem;
-        std::vector<void*> rq(nq), rs(ns);
-        std::vector<const uint64_t*> rqo(nq, nullptr);
-        std::vector<uint64_t*> rso(ns, nullptr);
-        std::vector<uint64_t> cap(ns);
-        for (size_t f = 0; f < nq; ++f) {
-            rq[f] = mem.add(in.col[f].size());
-            if (!in.col[f].empty()) check(hipMemcpy(rq[f], in.col[f].data(), in.col[f].size(), hipMemcpyHostToDevice));
-            if (e.req_size[f]) continue;
-            uint64_t* o = static_cast<uint64_t*>(mem.add(8 * (n + 1)));
-            check(hipMemcpy(o, in.offs[f].data(), 8 * (n + 1), hipMemcpyHostToDevice));
-            rqo[f] = o;
-        }
-        for (size_t f = 0; f < ns; ++f) {
-            cap[f] = e.resp_size[f] ? n * e.resp_size[f] : n * lim.max_reply_bytes + 4096;
-            rs[f] = mem.add(cap[f]);
-            if (!e.resp_size[f]) rso[f] = static_cast<uint64_t*>(mem.add(8 * (n + 1)));
-        }
-        uint8_t* d_codes = static_cast<uint8_t*>(mem.add(n));
-        call_var<Req, Resp>(method, rq.data(), rqo.data(), n, rs.data(), rso.data(), cap.data(), d_codes, lim);
-        host_columns<Resp> out;
-        out.n = n;
-        out.col.resize(ns);
-        out.offs.resize(ns);
-        for (size_t f = 0; f < ns; ++f) {
-            uint64_t bytes = n * e.resp_size[f];
-            if (!e.resp_size[f]) {
-                out.offs[f].resize(n + 1);
-                check(hipMemcpy(out.offs[f].data(), rso[f], 8 * (n + 1), hipMemcpyDeviceToHost));
-                bytes = out.offs[f][n];
-            }
-            out.col[f].resize(bytes);
-            if (bytes) check(hipMemcpy(out.col[f].data(), rs[f], bytes, hipMemcpyDeviceToHost));
-        }
-        std::vector<uint8_t> codes(n);
-        if (n) check(hipMemcpy(codes.data(), d_codes, n, hipMemcpyDeviceToHost));
-        std::vector<Resp> vals;
-        out.gather(vals);
-        std::vector<response_t<Resp>> res(n);
-        for (uint64_t i = 0; i < n; ++i) {
-            res[i].set_code(static_cast<rpc_status_code>(codes[i]));
-            res[i].set_value(vals[i]);
-        }
-        return res;
+        return call_records<Req, Resp>(any_plans<Req, Resp>(method), method, reqs, &lim);
     }
 
     /// One method of a call_mixed batch: `calls` calls of `method`, call r of
@@ -449,17 +215,7 @@ public:
     template <SrpcMessage Req, SrpcMessage Resp>
     mixed_leg leg(std::string const& method, void* const* d_req_cols, void* const* d_resp_cols, uint64_t calls) {
         check(hipSetDevice(_dev));
-        entry& e = plans<Req, Resp>(method);
-        mixed_leg l;
-        l.req = e.req->get();
-        l.resp = e.resp->get();
-        l.fin = e.fin;
-        l.fout = e.fout;
-        l.resp_prefix = &e.resp_prefix;
-        l.d_req_cols = d_req_cols;
-        l.d_resp_cols = d_resp_cols;
-        l.calls = calls;
-        return l;
+        return make_leg(plans<Req, Resp>(method), d_req_cols, nullptr, d_resp_cols, nullptr, nullptr, calls);
     }
 
     /// A leg whose request and/or response has std::string members, in
@@ -474,23 +230,8 @@ public:
                       void* const* d_resp_cols, uint64_t* const* d_resp_str_offs, const uint64_t* resp_cap,
                       uint64_t calls) {
         check(hipSetDevice(_dev));
-        var_entry& e = var_plans<Req, Resp>(method);
-        mixed_leg l;
-        l.req = e.req->get();
-        l.resp = e.resp->get();
-        l.fin = e.req_var ? 0 : e.fin;
-        l.fout = e.resp_var ? 0 : e.fout;
-        l.resp_prefix = &e.resp_prefix;
-        l.d_req_cols = d_req_cols;
-        l.d_resp_cols = d_resp_cols;
-        l.calls = calls;
-        l.req_var = e.req_var;
-        l.resp_var = e.resp_var;
-        l.d_req_str_offs = d_req_str_offs;
-        l.d_resp_str_offs = d_resp_str_offs;
-        l.resp_cap = resp_cap;
-        l.resp_leaf = &e.resp_leaf;
-        return l;
+        return make_leg(any_plans<Req, Resp>(method), d_req_cols, d_req_str_offs, d_resp_cols, d_resp_str_offs, resp_cap,
+                        calls);
     }
 
     /// n calls in the caller's order over at most SRPC_FRAMES_MAX_PLANS legs:
@@ -504,116 +245,13 @@ public:
     /// bytes-per-frame 0: the frames differ in length.
     call_stats call_mixed(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
                           hipStream_t stream = nullptr) {
-        check(hipSetDevice(_dev));
-        const size_t K = legs.size();
-        if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
-            throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
-        for (mixed_leg const& l : legs)
-            if (l.req_var || l.resp_var) return call_mixed(legs, d_method, n, d_codes, var_call_limits{}, stream);
-        uint64_t fin = 0, fout = 0;
-        std::vector<const srpc_plan*> rq(K), rs(K);
-        std::vector<const void* const*> rqc(K);
-        std::vector<void* const*> rsc(K);
-        std::vector<uint64_t> first(K, 0), cap(K);
-        std::vector<mixed_reply_plan> judge(K);
-        for (size_t k = 0; k < K; ++k) {
-            mixed_leg const& l = legs[k];
-            if (!l.req || !l.resp || !l.resp_prefix || !l.d_req_cols || !l.d_resp_cols)
-                throw plan_error("batch_client::call_mixed (leg)", SRPC_E_INVALID);
-            fin = std::max(fin, l.fin);
-            fout = std::max(fout, l.fout);
-            rq[k] = l.req;
-            rs[k] = l.resp;
-            rqc[k] = const_cast<const void* const*>(l.d_req_cols);
-            rsc[k] = l.d_resp_cols;
-            cap[k] = l.calls;
-            judge[k].prefix = l.resp_prefix->data();
-            judge[k].prefix_len = l.resp_prefix->size();
-            judge[k].F = l.fout;
-            judge[k].cap = l.calls;
-        }
-        ensure(fin, fout);  // staging by the largest frame of each side
-        ensure_mixed();
-        const int nk = static_cast<int>(K);
-        call_stats st;
-        st.calls = n;
-        for (uint64_t lo = 0; lo < n; lo += _max) {
-            const uint64_t m = std::min(_max, n - lo);
-            st.chunks += 1;
-            auto t0 = clock::now();
-            check_srpc(srpc_frames_mixed_index(d_method + lo, m, nk, _d_mindex, _mindex_bytes, _d_mcounts, _d_status, stream),
-                       "srpc_frames_mixed_index");
-            // the pack runs even after the peer closed: its status says whether the chunk is well formed
-            check_srpc(srpc_frames_pack_requests_mixed(rq.data(), nk, rqc.data(), first.data(), cap.data(), d_method + lo,
-                                                       _d_mindex, m, _d_out, _out_cap, _d_moffs, _d_status, stream),
-                       "srpc_frames_pack_requests_mixed");
-            check(hipMemcpyAsync(_h_mcounts, _d_mcounts, 8 * (K + 1), hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_mcounts + SRPC_FRAMES_MAX_PLANS + 1, _d_moffs + m, 4, hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
-            check(hipStreamSynchronize(stream));
-            if (_h_status->flags || _h_mcounts[K]) {  // an id out of range, or a leg with too few calls declared
-                _last = st;
-                throw plan_error("batch_client::call_mixed (d_method does not match the legs)", SRPC_E_INVALID);
-            }
-            const uint64_t total = _eof ? 0 : *reinterpret_cast<const uint32_t*>(_h_mcounts + SRPC_FRAMES_MAX_PLANS + 1);
-            if (total) {
-                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
-                check(hipStreamSynchronize(stream));
-            }
-            st.gpu_seconds += secs(t0);
-            if (total && _hook) _hook(_h_out, lo, m, 0);
-            const frame_walk w = exchange(m, total, 0, st);
-            t0 = clock::now();
-            const uint64_t nf = w.nframes;
-            if (nf) {
-                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
-                check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
-            }
-            // calls without a reply get RPC_ERR_RECV_TIMEOUT and zero fields from the decode itself
-            check_srpc(srpc_frames_unpack_replies_mixed(rs.data(), nk, _d_in, w.walked, _d_offs, nf, d_method + lo,
-                                                        _d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
-                                                        rsc.data(), first.data(), cap.data(), d_codes + lo, _d_status,
-                                                        stream),
-                       "srpc_frames_unpack_replies_mixed");
-            if (nf) check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
-            check(hipStreamSynchronize(stream));
-            st.gpu_seconds += secs(t0);
-            st.unanswered += m - nf;
-            if (nf && _h_status->flags == 0) {
-                const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
-                st.ok += ok;
-                st.failed += nf - ok;
-            } else if (nf) {  // a flagged chunk: the table on the host, frame by frame
-                std::vector<uint8_t> hm(m);
-                std::vector<uint32_t> rank(m);
-                std::vector<uint64_t> cnt(K + 1);
-                check(hipMemcpy(hm.data(), d_method + lo, m, hipMemcpyDeviceToHost));
-                mixed_ranks(hm.data(), m, static_cast<uint32_t>(K), rank.data(), cnt.data());
-                for (size_t k = 0; k < K; ++k) judge[k].first = first[k];
-                for (uint64_t i = 0; i < nf; ++i) {
-                    const reply_frame r = judge_reply_mixed(_h_in, w.walked, _h_offs[i], i + 1 < nf ? _h_offs[i + 1] : w.walked,
-                                                            hm[i], rank[i], judge.data(), static_cast<uint32_t>(K));
-                    if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
-                    else if (r.code == RPC_SUCCESS) st.ok += 1;
-                    else st.failed += 1;
-                }
-            }
-            for (size_t k = 0; k < K; ++k) first[k] += _h_mcounts[k];
-            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
-            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
-            _have -= w.walked;
-        }
-        _last = st;
-        for (size_t k = 0; k < K; ++k)
-            if (first[k] != legs[k].calls)
-                throw plan_error("batch_client::call_mixed (a leg declares more calls than d_method holds)", SRPC_E_INVALID);
-        return st;
+        return call_mixed(legs, d_method, n, d_codes, var_call_limits{}, stream);
     }
 
     /// call_mixed over legs of which some are string-bodied (leg_var); without
-    /// one it is the call above.  `lim` sizes the staging as for call_var (a
-    /// fixed leg's frames count with their own size).  Beyond the call above:
+    /// one it is the call above and `lim` is not used.  `lim` sizes the staging
+    /// as for call_var (a fixed leg's frames count with their own size).  Beyond
+    /// the call above:
     /// plan_error(SRPC_E_CAPACITY) before anything of a chunk is sent when its
     /// request frames outgrow the send buffer, and after a chunk is received and
     /// accounted for when the chars of some reply column pass its resp_cap
@@ -629,8 +267,7 @@ public:
             throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
         bool any_var = false;
         for (mixed_leg const& l : legs) any_var = any_var || l.req_var || l.resp_var;
-        if (!any_var) return call_mixed(legs, d_method, n, d_codes, stream);
-        uint64_t fin = lim.max_request_bytes, fout = lim.max_reply_bytes;
+        uint64_t fin = any_var ? lim.max_request_bytes : 0, fout = any_var ? lim.max_reply_bytes : 0;
         std::vector<const srpc_plan*> rq(K), rs(K);
         std::vector<const void* const*> rqc(K);
         std::vector<void* const*> rsc(K);
@@ -671,101 +308,116 @@ public:
                 scapp[k] = scap[k].data();
             }
         }
-        ensure_bytes(_max * fin + 4096, _max * fout + 4096);
-        ensure_mixed();
         const int nk = static_cast<int>(K);
-        ensure_mixed_var(rq.data(), rs.data(), nk);
+        // staging by the largest frame of each side
+        if (any_var) ensure_bytes(_max * fin + 4096, _max * fout + 4096);
+        else ensure(fin, fout);
+        ensure_mixed();
+        if (any_var) ensure_mixed_var(rq.data(), rs.data(), nk);
         const uint64_t out_cap = std::min<uint64_t>(_out_cap, (1ull << 32) - 1);
         const size_t nslots = slot_cap.size();
+        uint64_t* const h_counts = _s.h_mcounts;
         call_stats st;
         st.calls = n;
         for (uint64_t lo = 0; lo < n; lo += _max) {
             const uint64_t m = std::min(_max, n - lo);
             st.chunks += 1;
             auto t0 = clock::now();
-            check_srpc(srpc_frames_mixed_index(d_method + lo, m, nk, _d_mindex, _mindex_bytes, _d_mcounts, _d_status, stream),
+            check_srpc(srpc_frames_mixed_index(d_method + lo, m, nk, _s.d_mindex, _s.mindex_bytes, _s.d_mcounts, _s.d_status,
+                                               stream),
                        "srpc_frames_mixed_index");
             // the pack runs even after the peer closed: its status says whether the chunk is well formed
-            check_srpc(srpc_frames_pack_requests_mixed_var(rq.data(), nk, rqc.data(), rqo.data(), first.data(), cap.data(),
-                                                           d_method + lo, _d_mindex, m, _d_out, out_cap, _d_moffs, _d_mv,
-                                                           _d_status, _d_vscratch, _vscratch_cap, stream),
-                       "srpc_frames_pack_requests_mixed_var");
-            check(hipMemcpyAsync(_h_mcounts, _d_mcounts, 8 * (K + 1), hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_mv, _d_mv, 8, hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            if (any_var)
+                check_srpc(srpc_frames_pack_requests_mixed_var(rq.data(), nk, rqc.data(), rqo.data(), first.data(), cap.data(),
+                                                               d_method + lo, _s.d_mindex, m, _s.d_out, out_cap, _s.d_moffs,
+                                                               _s.d_mv, _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
+                           "srpc_frames_pack_requests_mixed_var");
+            else
+                check_srpc(srpc_frames_pack_requests_mixed(rq.data(), nk, rqc.data(), first.data(), cap.data(), d_method + lo,
+                                                           _s.d_mindex, m, _s.d_out, _out_cap, _s.d_moffs, _s.d_status, stream),
+                           "srpc_frames_pack_requests_mixed");
+            check(hipMemcpyAsync(h_counts, _s.d_mcounts, 8 * (K + 1), hipMemcpyDeviceToHost, stream));
+            // the chunk's request bytes: a u64 total, or the last of the u32 frame offsets
+            if (any_var) check(hipMemcpyAsync(_s.h_mv, _s.d_mv, 8, hipMemcpyDeviceToHost, stream));
+            else check(hipMemcpyAsync(h_counts + SRPC_FRAMES_MAX_PLANS + 1, _s.d_moffs + m, 4, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_s.h_status, _s.d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
             check(hipStreamSynchronize(stream));
-            bool fits = _h_mcounts[K] == 0;  // no id out of range, no leg with too few calls declared
-            for (size_t k = 0; k < K; ++k) fits = fits && _h_mcounts[k] <= cap[k] - std::min(cap[k], first[k]);
+            bool fits = h_counts[K] == 0;  // no id out of range
+            // no leg with too few calls declared: the fixed pack flags one itself
+            if (!any_var) fits = fits && _s.h_status->flags == 0;
+            for (size_t k = 0; any_var && k < K; ++k) fits = fits && h_counts[k] <= cap[k] - std::min(cap[k], first[k]);
             if (!fits) {
                 _last = st;
                 throw plan_error("batch_client::call_mixed (d_method does not match the legs)", SRPC_E_INVALID);
             }
-            if (_h_mv[0] > out_cap) {
+            if (any_var && _s.h_mv[0] > out_cap) {
                 _last = st;
                 throw plan_error("batch_client::call_mixed (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
             }
-            if (_h_status->flags) {
+            if (any_var && _s.h_status->flags) {
                 _last = st;
                 throw plan_error("batch_client::call_mixed (a request string's offsets decrease)", SRPC_E_INVALID);
             }
-            const uint64_t total = _eof ? 0 : _h_mv[0];
+            const uint64_t packed =
+                any_var ? _s.h_mv[0] : *reinterpret_cast<const uint32_t*>(h_counts + SRPC_FRAMES_MAX_PLANS + 1);
+            const uint64_t total = _eof ? 0 : packed;
             if (total) {
-                check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, stream));
+                check(hipMemcpyAsync(_s.h_out, _s.d_out, total, hipMemcpyDeviceToHost, stream));
                 check(hipStreamSynchronize(stream));
             }
             st.gpu_seconds += secs(t0);
-            if (total && _hook) _hook(_h_out, lo, m, 0);
+            if (total && _hook) _hook(_s.h_out, lo, m, 0);
             const frame_walk w = exchange(m, total, 0, st);
             t0 = clock::now();
             const uint64_t nf = w.nframes;
             if (nf) {
-                check(hipMemcpyAsync(_d_in, _h_in, w.walked, hipMemcpyHostToDevice, stream));
-                check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+                check(hipMemcpyAsync(_s.d_in, _s.h_in, w.walked, hipMemcpyHostToDevice, stream));
+                check(hipMemcpyAsync(_s.d_offs, _s.h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
             }
             // calls without a reply get RPC_ERR_RECV_TIMEOUT, zero fields and empty strings from the decode itself
-            check_srpc(srpc_frames_unpack_replies_mixed_var(rs.data(), nk, _d_in, w.walked, _d_offs, nf, d_method + lo,
-                                                            _d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
-                                                            rsc.data(), rso.data(), scapp.data(), first.data(), cap.data(),
-                                                            d_codes + lo, _d_mv + 1, _d_status, _d_vscratch, _vscratch_cap,
+            if (any_var)
+                check_srpc(srpc_frames_unpack_replies_mixed_var(rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo,
+                                                                _s.d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
+                                                                rsc.data(), rso.data(), scapp.data(), first.data(), cap.data(),
+                                                                d_codes + lo, _s.d_mv + 1, _s.d_status, _s.d_vscratch,
+                                                                _s.vscratch_cap, stream),
+                           "srpc_frames_unpack_replies_mixed_var");
+            else
+                check_srpc(srpc_frames_unpack_replies_mixed(rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo,
+                                                            _s.d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
+                                                            rsc.data(), first.data(), cap.data(), d_codes + lo, _s.d_status,
                                                             stream),
-                       "srpc_frames_unpack_replies_mixed_var");
-            if (nf) check(hipMemcpyAsync(_h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
-            if (nslots) check(hipMemcpyAsync(_h_mv + 1, _d_mv + 1, 8 * nslots, hipMemcpyDeviceToHost, stream));
-            check(hipMemcpyAsync(_h_status, _d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+                           "srpc_frames_unpack_replies_mixed");
+            if (nf) check(hipMemcpyAsync(_s.h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+            if (nslots) check(hipMemcpyAsync(_s.h_mv + 1, _s.d_mv + 1, 8 * nslots, hipMemcpyDeviceToHost, stream));
+            check(hipMemcpyAsync(_s.h_status, _s.d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
             check(hipStreamSynchronize(stream));
             st.gpu_seconds += secs(t0);
             st.unanswered += m - nf;
-            if (nf && _h_status->flags == 0) {
-                const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
-                st.ok += ok;
-                st.failed += nf - ok;
-            } else if (nf) {  // a flagged chunk: the tables on the host, frame by frame
-                std::vector<uint8_t> hm(m);
-                std::vector<uint32_t> rank(m);
-                std::vector<uint64_t> cnt(K + 1);
-                check(hipMemcpy(hm.data(), d_method + lo, m, hipMemcpyDeviceToHost));
-                mixed_ranks(hm.data(), m, static_cast<uint32_t>(K), rank.data(), cnt.data());
-                for (size_t k = 0; k < K; ++k) judge[k].first = first[k];
-                for (uint64_t i = 0; i < nf; ++i) {
-                    const reply_frame r = judge_reply_mixed_var(_h_in, w.walked, _h_offs[i],
-                                                                i + 1 < nf ? _h_offs[i + 1] : w.walked, hm[i], rank[i],
-                                                                judge.data(), static_cast<uint32_t>(K));
-                    if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
-                    else if (r.code == RPC_SUCCESS) st.ok += 1;
-                    else st.failed += 1;
+            if (nf) {
+                std::vector<uint8_t> hm;
+                std::vector<uint32_t> rank;
+                if (_s.h_status->flags) {  // a flagged chunk: the tables on the host, frame by frame
+                    hm.resize(m);
+                    rank.resize(m);
+                    std::vector<uint64_t> cnt(K + 1);
+                    check(hipMemcpy(hm.data(), d_method + lo, m, hipMemcpyDeviceToHost));
+                    mixed_ranks(hm.data(), m, static_cast<uint32_t>(K), rank.data(), cnt.data());
+                    for (size_t k = 0; k < K; ++k) judge[k].first = first[k];
                 }
+                count(w, st, [&](uint64_t i, uint64_t o, uint64_t end) {
+                    return judge_reply_mixed(_s.h_in, w.walked, o, end, hm[i], rank[i], judge.data(), static_cast<uint32_t>(K));
+                });
             }
-            for (size_t k = 0; k < K; ++k) first[k] += _h_mcounts[k];
-            if (_keep) _kept.insert(_kept.end(), _h_in, _h_in + w.walked);
-            std::memmove(_h_in, _h_in + w.walked, _have - w.walked);
-            _have -= w.walked;
+            for (size_t k = 0; k < K; ++k) first[k] += h_counts[k];
+            end_chunk(w);
             for (size_t s = 0; s < nslots; ++s)
-                if (_h_mv[1 + s] > slot_cap[s]) {
+                if (_s.h_mv[1 + s] > slot_cap[s]) {
                     _last = st;
                     throw plan_error("batch_client::call_mixed (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
                 }
         }
-        if (!n) {  // no chunk ran: the offsets of no calls
+        if (!n && any_var) {  // no chunk ran: the offsets of no calls
             for (size_t k = 0; k < K; ++k)
                 for (size_t f = 0; legs[k].resp_var && f < legs[k].resp_leaf->size(); ++f)
                     if ((*legs[k].resp_leaf)[f] == 0) check(hipMemsetAsync(legs[k].d_resp_str_offs[f], 0, 8, stream));
@@ -780,52 +432,11 @@ public:
 
 private:
     using clock = std::chrono::steady_clock;
-    struct entry {
-        std::unique_ptr<raw_plan> req, resp;
-        uint64_t fin = 0, fout = 0;  // request / full reply frame bytes
-        std::vector<uint64_t> req_size, resp_size;
-        std::vector<uint8_t> resp_prefix;
-    };
-    struct device_buffers {
-        std::vector<void*> p;
-        explicit device_buffers(std::vector<std::vector<uint8_t>> const& cols) {
-            for (auto const& c : cols) {
-                void* d = nullptr;
-                if (hipMalloc(&d, c.size() + 16) != hipSuccess) {
-                    free_all();
-                    throw plan_error("batch_client: hipMalloc", SRPC_E_HIP);
-                }
-                p.push_back(d);
-            }
-        }
-        device_buffers(device_buffers const&) = delete;
-        device_buffers& operator=(device_buffers const&) = delete;
-        ~device_buffers() { free_all(); }
-        void free_all() {
-            for (void* d : p) (void)hipFree(d);
-            p.clear();
-        }
-    };
 
-    /// Device allocations of one host-form call, freed together.
-    struct device_allocs {
-        std::vector<void*> p;
-        device_allocs() = default;
-        device_allocs(device_allocs const&) = delete;
-        device_allocs& operator=(device_allocs const&) = delete;
-        ~device_allocs() {
-            for (void* d : p) (void)hipFree(d);
-        }
-        void* add(uint64_t bytes) {
-            void* d = nullptr;
-            if (hipMalloc(&d, bytes + 16) != hipSuccess) throw plan_error("batch_client: hipMalloc", SRPC_E_HIP);
-            p.push_back(d);
-            return d;
-        }
-    };
-    /// A method of call_var: each side is a string plan (unframed prefix) or,
-    /// without strings, the framed fixed plan `call` uses.
-    struct var_entry {
+    /// A method's plans and leaf sizes, whichever form calls it: a side with
+    /// strings is a string plan (unframed prefix), one without the framed fixed
+    /// plan.
+    struct entry {
         std::unique_ptr<raw_plan> req, resp;
         bool req_var = false, resp_var = false;
         uint64_t fin = 0, fout = 0;                 // fixed sides: request / full reply frame bytes
@@ -844,36 +455,68 @@ private:
         if (rc < 0) throw plan_error(what, rc);
     }
 
+    /// Device (or pinned host) memory that frees itself; reads as its pointer.
+    template <class T, bool Pinned>
+    struct buffer {
+        T* p = nullptr;
+        buffer() = default;
+        buffer(buffer&& o) noexcept : p(o.p) { o.p = nullptr; }
+        buffer& operator=(buffer&& o) noexcept {
+            std::swap(p, o.p);
+            return *this;
+        }
+        ~buffer() { reset(); }
+        void reset() {
+            if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+            p = nullptr;
+        }
+        void alloc(uint64_t bytes) {
+            reset();
+            check(Pinned ? hipHostMalloc(reinterpret_cast<void**>(&p), bytes) : hipMalloc(reinterpret_cast<void**>(&p), bytes));
+        }
+        operator T*() const { return p; }
+        T* operator->() const { return p; }
+    };
+    template <class T>
+    using device_buffer = buffer<T, false>;
+    template <class T>
+    using pinned_buffer = buffer<T, true>;
+
+    /// All of the staging: ensure_bytes sizes the first group, the others are
+    /// created by the forms that need them, and a grow starts from an empty one.
+    struct staging {
+        device_buffer<uint8_t> d_out, d_in;
+        pinned_buffer<uint8_t> h_out, h_in, h_codes;
+        device_buffer<uint32_t> d_offs;
+        pinned_buffer<uint32_t> h_offs;
+        device_buffer<srpc_unpack_status> d_status;
+        pinned_buffer<srpc_unpack_status> h_status;
+        // string sides (ensure_var, ensure_mixed_var)
+        device_buffer<uint8_t> d_wire;
+        device_buffer<uint64_t> d_rec;
+        pinned_buffer<uint64_t> h_ends, h_soffs;
+        device_buffer<void> d_vscratch;
+        uint64_t vscratch_cap = 0;
+        std::vector<device_buffer<uint8_t>> d_schars;
+        std::vector<device_buffer<uint64_t>> d_soffs;
+        // call_mixed (ensure_mixed, ensure_mixed_var)
+        device_buffer<void> d_mindex;
+        uint64_t mindex_bytes = 0;
+        device_buffer<uint64_t> d_mcounts;
+        pinned_buffer<uint64_t> h_mcounts;  // [17]: the chunk's request bytes (fixed legs)
+        device_buffer<uint32_t> d_moffs;
+        device_buffer<uint64_t> d_mv;
+        pinned_buffer<uint64_t> h_mv;  // [0]: the chunk's request bytes, [1 + s]: reply string slot s's end
+    };
+
+    /// The plans of `method`, built once per client.
     template <SrpcMessage Req, SrpcMessage Resp>
-    entry& plans(std::string const& method) {
+    entry& any_plans(std::string const& method) {
         const std::string key = method + '\0' + Req::name + '\0' + Resp::name;
         auto it = _plans.find(key);
         if (it != _plans.end()) return it->second;
         const std::vector<int32_t> kq = flat_kinds<Req>(), ks = flat_kinds<Resp>();
-        for (int32_t k : kq)
-            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string request)", SRPC_E_UNSUPPORTED);
-        for (int32_t k : ks)
-            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string response)", SRPC_E_UNSUPPORTED);
         entry e;
-        e.resp_prefix = framed_response_prefix<Resp>(RPC_SUCCESS);
-        e.req = std::make_unique<raw_plan>(kq, framed_request_prefix<Req>(method), _dev);
-        e.resp = std::make_unique<raw_plan>(ks, e.resp_prefix, _dev);
-        e.fin = e.req->record_bytes();
-        e.fout = e.resp->record_bytes();
-        Req rq{};
-        for_each_leaf<Req>(rq, [&](const auto& v) { e.req_size.push_back(sizeof(v)); });
-        Resp rs{};
-        for_each_leaf<Resp>(rs, [&](const auto& v) { e.resp_size.push_back(sizeof(v)); });
-        return _plans.emplace(key, std::move(e)).first->second;
-    }
-
-    template <SrpcMessage Req, SrpcMessage Resp>
-    var_entry& var_plans(std::string const& method) {
-        const std::string key = method + '\0' + Req::name + '\0' + Resp::name;
-        auto it = _vplans.find(key);
-        if (it != _vplans.end()) return it->second;
-        const std::vector<int32_t> kq = flat_kinds<Req>(), ks = flat_kinds<Resp>();
-        var_entry e;
         for (int32_t k : kq) e.req_var = e.req_var || k == SRPC_KIND_STRING;
         for (int32_t k : ks) e.resp_var = e.resp_var || k == SRPC_KIND_STRING;
         e.resp_prefix = e.resp_var ? response_prefix<Resp>(RPC_SUCCESS) : framed_response_prefix<Resp>(RPC_SUCCESS);
@@ -896,13 +539,245 @@ private:
             e.resp_sidx.push_back(str ? e.resp_nstr++ : 0);
         });
         if (e.resp_nstr > SRPC_FRAMES_MAX_STRINGS) throw plan_error("batch_client::call_var", SRPC_E_UNSUPPORTED);
-        return _vplans.emplace(key, std::move(e)).first->second;
+        return _plans.emplace(key, std::move(e)).first->second;
+    }
+
+    /// The same for call and leg: a string schema is refused before a plan is built.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    entry& plans(std::string const& method) {
+        for (int32_t k : flat_kinds<Req>())
+            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string request)", SRPC_E_UNSUPPORTED);
+        for (int32_t k : flat_kinds<Resp>())
+            if (k == SRPC_KIND_STRING) throw plan_error("batch_client::call (string response)", SRPC_E_UNSUPPORTED);
+        return any_plans<Req, Resp>(method);
+    }
+
+    mixed_leg make_leg(entry& e, void* const* d_req_cols, const uint64_t* const* d_req_str_offs, void* const* d_resp_cols,
+                       uint64_t* const* d_resp_str_offs, const uint64_t* resp_cap, uint64_t calls) {
+        mixed_leg l;
+        l.req = e.req->get();
+        l.resp = e.resp->get();
+        l.fin = e.req_var ? 0 : e.fin;
+        l.fout = e.resp_var ? 0 : e.fout;
+        l.resp_prefix = &e.resp_prefix;
+        l.d_req_cols = d_req_cols;
+        l.d_resp_cols = d_resp_cols;
+        l.calls = calls;
+        l.req_var = e.req_var;
+        l.resp_var = e.resp_var;
+        l.d_req_str_offs = d_req_str_offs;
+        l.d_resp_str_offs = d_resp_str_offs;
+        l.resp_cap = resp_cap;
+        l.resp_leaf = &e.resp_leaf;
+        return l;
+    }
+
+    /// The chunk loop of call and call_var over a staging already sized.  A
+    /// side without strings (for `call`, both) is packed by srpc_gpu_pack and
+    /// decoded by srpc_frames_unpack_replies; the string arguments of such a
+    /// side are not read.
+    call_stats run_calls(entry& e, void* const* d_req_cols, const uint64_t* const* d_req_str_offs, uint64_t n,
+                         void* const* d_resp_cols, uint64_t* const* d_resp_str_offs, const uint64_t* resp_cap,
+                         uint8_t* d_codes, hipStream_t stream) {
+        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
+        call_stats st;
+        st.calls = n;
+        std::vector<const void*> rq(nq);
+        std::vector<const uint64_t*> rqo(nq, nullptr);
+        std::vector<void*> rs(ns);
+        std::vector<uint64_t*> rso(ns, nullptr);
+        std::vector<uint64_t> base(ns, 0);  // chars of response field f in the chunks before this one
+        for (uint64_t lo = 0; lo < n; lo += _max) {
+            const uint64_t m = std::min(_max, n - lo);
+            st.chunks += 1;
+            uint64_t total = 0;  // the chunk's request bytes
+            if (!_eof) {
+                auto t0 = clock::now();
+                for (size_t f = 0; f < nq; ++f) {
+                    const bool str = e.req_size[f] == 0;
+                    // a string column's offsets are absolute: its chars stay where they are
+                    rq[f] = str ? d_req_cols[f] : static_cast<const uint8_t*>(d_req_cols[f]) + lo * e.req_size[f];
+                    rqo[f] = str ? d_req_str_offs[f] + lo : nullptr;
+                }
+                if (e.req_var) {
+                    check_srpc(srpc_gpu_pack_var(e.req->get(), rq.data(), rqo.data(), m, _s.d_wire, _out_cap, _s.d_rec,
+                                                 _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
+                               "srpc_gpu_pack_var");
+                    check_srpc(srpc_frames_frame_var(_s.d_wire, _s.d_rec, m, _s.d_out, _out_cap, _s.d_status, stream),
+                               "srpc_frames_frame_var");
+                    check(hipMemcpyAsync(_s.h_ends, _s.d_rec + m, 8, hipMemcpyDeviceToHost, stream));
+                    check(hipMemcpyAsync(_s.h_status, _s.d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+                    check(hipStreamSynchronize(stream));
+                    total = _s.h_ends[0] + 4 * m;
+                    if (total > _out_cap || _s.h_status->flags)
+                        throw plan_error("batch_client::call_var (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
+                } else {
+                    total = m * e.fin;
+                    check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _s.d_out, total, stream), "srpc_gpu_pack");
+                }
+                check(hipMemcpyAsync(_s.h_out, _s.d_out, total, hipMemcpyDeviceToHost, stream));
+                check(hipStreamSynchronize(stream));
+                st.gpu_seconds += secs(t0);
+                if (_hook) _hook(_s.h_out, lo, m, e.req_var ? 0 : e.fin);
+            }
+            const frame_walk w = exchange(m, total, e.resp_var ? 0 : e.fout, st);
+            auto t0 = clock::now();
+            const uint64_t nf = w.nframes;
+            for (size_t f = 0; f < ns; ++f) {
+                const bool str = e.resp_size[f] == 0;
+                // string fields are decoded into the client's staging first
+                rs[f] = str ? static_cast<void*>(_s.d_schars[e.resp_sidx[f]].p)
+                            : static_cast<uint8_t*>(d_resp_cols[f]) + lo * e.resp_size[f];
+                rso[f] = str ? _s.d_soffs[e.resp_sidx[f]].p : nullptr;
+            }
+            if (nf) {
+                check(hipMemcpyAsync(_s.d_in, _s.h_in, w.walked, hipMemcpyHostToDevice, stream));
+                const bool uniform = !e.resp_var && w.all_full;
+                if (!uniform) check(hipMemcpyAsync(_s.d_offs, _s.h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
+                st.uniform_chunks += uniform;
+                if (e.resp_var) {
+                    check_srpc(srpc_frames_unpack_replies_var(e.resp->get(), _s.d_in, w.walked, _s.d_offs, nf, rs.data(),
+                                                              rso.data(), d_codes + lo, _s.d_status, _s.d_vscratch,
+                                                              _s.vscratch_cap, stream),
+                               "srpc_frames_unpack_replies_var");
+                    for (uint32_t t = 0; t < e.resp_nstr; ++t)
+                        check(hipMemcpyAsync(_s.h_soffs + t * (_max + 1), _s.d_soffs[t], 8 * (nf + 1), hipMemcpyDeviceToHost,
+                                             stream));
+                } else {
+                    check_srpc(srpc_frames_unpack_replies(e.resp->get(), _s.d_in, w.walked, uniform ? nullptr : _s.d_offs.p,
+                                                          nf, rs.data(), d_codes + lo, _s.d_status, stream),
+                               "srpc_frames_unpack_replies");
+                }
+                check(hipMemcpyAsync(_s.h_codes, d_codes + lo, nf, hipMemcpyDeviceToHost, stream));
+                check(hipMemcpyAsync(_s.h_status, _s.d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
+            }
+            if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields (empty strings: below)
+                check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
+                for (size_t f = 0; f < ns; ++f)
+                    if (e.resp_size[f])
+                        check(hipMemsetAsync(static_cast<uint8_t*>(rs[f]) + nf * e.resp_size[f], 0,
+                                             (m - nf) * e.resp_size[f], stream));
+                st.unanswered += m - nf;
+            }
+            check(hipStreamSynchronize(stream));
+            // the chunk's chars, now that their totals are known: they must fit
+            // the caller's columns before a byte of them is written there
+            bool overflow = false;
+            for (size_t f = 0; f < ns; ++f) {
+                if (e.resp_size[f]) continue;
+                const uint32_t t = e.resp_sidx[f];
+                uint64_t* ho = _s.h_soffs + t * (_max + 1);
+                const uint64_t chars = nf ? ho[nf] : 0;
+                if (chars > resp_cap[f] || base[f] > resp_cap[f] - chars) {
+                    overflow = true;  // thrown once the chunk's bytes are accounted for
+                    continue;
+                }
+                if (chars)
+                    check(hipMemcpyAsync(static_cast<uint8_t*>(d_resp_cols[f]) + base[f], _s.d_schars[t], chars,
+                                         hipMemcpyDeviceToDevice, stream));
+                // absolute offsets; unanswered calls are empty strings at the chunk's end
+                if (!nf) ho[0] = 0;
+                for (uint64_t j = 0; j <= nf; ++j) ho[j] += base[f];
+                for (uint64_t j = nf + 1; j <= m; ++j) ho[j] = base[f] + chars;
+                check(hipMemcpyAsync(d_resp_str_offs[f] + lo, ho, 8 * (m + 1), hipMemcpyHostToDevice, stream));
+                base[f] += chars;
+            }
+            if (e.resp_var) check(hipStreamSynchronize(stream));
+            st.gpu_seconds += secs(t0);
+            if (nf)
+                count(w, st, [&](uint64_t, uint64_t o, uint64_t end) {
+                    return e.resp_var ? walk_reply_var(_s.h_in + o, end - o, e.resp_prefix.data(), e.resp_prefix.size(),
+                                                       e.resp_leaf.data(), static_cast<uint32_t>(e.resp_leaf.size()))
+                                      : judge_reply_fixed(_s.h_in, w.walked, o, end, e.fout, e.resp_prefix.data(),
+                                                          e.resp_prefix.size());
+                });
+            end_chunk(w);
+            if (overflow) {
+                _last = st;
+                throw plan_error("batch_client::call_var (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
+            }
+        }
+        if (!n && d_resp_str_offs) {  // call_var, and no chunk ran: the offsets of no calls
+            for (size_t f = 0; f < ns; ++f)
+                if (!e.resp_size[f]) check(hipMemsetAsync(d_resp_str_offs[f], 0, 8, stream));
+            check(hipStreamSynchronize(stream));
+        }
+        _last = st;
+        return st;
+    }
+
+    /// The host-record forms: the records' columns to the device, the call
+    /// (`call` without limits, `call_var` with), the reply columns back.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    std::vector<response_t<Resp>> call_records(entry& e, std::string const& method, std::vector<Req> const& reqs,
+                                               const var_call_limits* lim) {
+        const uint64_t n = reqs.size();
+        host_columns<Req> in;
+        in.scatter(reqs);
+        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
+        std::vector<device_buffer<uint8_t>> mem;  // freed together
+        auto add = [&](uint64_t bytes) {
+            mem.emplace_back().alloc(bytes + 16);
+            return mem.back().p;
+        };
+        std::vector<void*> rq(nq), rs(ns);
+        std::vector<const uint64_t*> rqo(nq, nullptr);
+        std::vector<uint64_t*> rso(ns, nullptr);
+        std::vector<uint64_t> cap(ns);
+        for (size_t f = 0; f < nq; ++f) {
+            rq[f] = add(in.col[f].size());
+            if (!in.col[f].empty()) check(hipMemcpy(rq[f], in.col[f].data(), in.col[f].size(), hipMemcpyHostToDevice));
+            if (e.req_size[f]) continue;
+            uint64_t* o = reinterpret_cast<uint64_t*>(add(8 * (n + 1)));
+            check(hipMemcpy(o, in.offs[f].data(), 8 * (n + 1), hipMemcpyHostToDevice));
+            rqo[f] = o;
+        }
+        for (size_t f = 0; f < ns; ++f) {
+            cap[f] = e.resp_size[f] ? n * e.resp_size[f] : n * lim->max_reply_bytes + 4096;
+            rs[f] = add(cap[f]);
+            if (!e.resp_size[f]) rso[f] = reinterpret_cast<uint64_t*>(add(8 * (n + 1)));
+        }
+        uint8_t* d_codes = add(n);
+        if (lim) call_var<Req, Resp>(method, rq.data(), rqo.data(), n, rs.data(), rso.data(), cap.data(), d_codes, *lim);
+        else call<Req, Resp>(method, rq.data(), n, rs.data(), d_codes);
+        host_columns<Resp> out;
+        out.n = n;
+        out.col.resize(ns);
+        out.offs.resize(ns);
+        for (size_t f = 0; f < ns; ++f) {
+            uint64_t bytes = n * e.resp_size[f];
+            if (!e.resp_size[f]) {
+                out.offs[f].resize(n + 1);
+                check(hipMemcpy(out.offs[f].data(), rso[f], 8 * (n + 1), hipMemcpyDeviceToHost));
+                bytes = out.offs[f][n];
+            }
+            out.col[f].resize(bytes);
+            if (bytes) check(hipMemcpy(out.col[f].data(), rs[f], bytes, hipMemcpyDeviceToHost));
+        }
+        std::vector<uint8_t> codes(n);
+        if (n) check(hipMemcpy(codes.data(), d_codes, n, hipMemcpyDeviceToHost));
+        std::vector<Resp> vals;
+        out.gather(vals);
+        std::vector<response_t<Resp>> res(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            res[i].set_code(static_cast<rpc_status_code>(codes[i]));
+            res[i].set_value(vals[i]);
+        }
+        return res;
+    }
+
+    /// The scratch of the string calls, grown to `need` bytes.
+    void ensure_vscratch(uint64_t need) {
+        if (need <= _s.vscratch_cap) return;
+        _s.vscratch_cap = 0;
+        _s.d_vscratch.alloc(need);
+        _s.vscratch_cap = need;
     }
 
     /// call_var's own staging beside ensure_bytes': the packed records before
     /// they are framed, the scratch of the var calls, and per response string
     /// field the chars and offsets a chunk is decoded into.
-    void ensure_var(var_entry const& e) {
+    void ensure_var(entry const& e) {
         uint64_t need = 0, b = 0;
         if (e.req_var) {
             check_srpc(srpc_plan_var_scratch_bytes(e.req->get(), _max, _out_cap, &b), "srpc_plan_var_scratch_bytes");
@@ -913,42 +788,29 @@ private:
                        "srpc_frames_replies_var_scratch_bytes");
             need = std::max(need, b);
         }
-        if (need > _vscratch_cap) {
-            (void)hipFree(_d_vscratch);
-            _d_vscratch = nullptr;
-            _vscratch_cap = 0;
-            check(hipMalloc(&_d_vscratch, need));
-            _vscratch_cap = need;
+        ensure_vscratch(need);
+        if (e.req_var && !_s.d_wire) {
+            _s.d_wire.alloc(_out_cap + 16);
+            _s.d_rec.alloc(8 * (_max + 1) + 16);
         }
-        if (e.req_var && !_d_wire) {
-            check(hipMalloc(reinterpret_cast<void**>(&_d_wire), _out_cap + 16));
-            check(hipMalloc(reinterpret_cast<void**>(&_d_rec), 8 * (_max + 1) + 16));
+        if (!_s.h_ends) _s.h_ends.alloc(64);
+        if (e.resp_nstr > _s.d_schars.size()) _s.h_soffs.reset();
+        while (_s.d_schars.size() < e.resp_nstr) {
+            _s.d_schars.emplace_back().alloc(_in_cap + 16);
+            _s.d_soffs.emplace_back().alloc(8 * (_max + 1) + 16);
         }
-        if (!_h_ends) check(hipHostMalloc(reinterpret_cast<void**>(&_h_ends), 64));
-        if (e.resp_nstr > _d_schars.size() && _h_soffs) {
-            (void)hipHostFree(_h_soffs);
-            _h_soffs = nullptr;
-        }
-        while (_d_schars.size() < e.resp_nstr) {
-            void *c = nullptr, *o = nullptr;
-            check(hipMalloc(&c, _in_cap + 16));
-            _d_schars.push_back(static_cast<uint8_t*>(c));
-            check(hipMalloc(&o, 8 * (_max + 1) + 16));
-            _d_soffs.push_back(static_cast<uint64_t*>(o));
-        }
-        if (e.resp_nstr && !_h_soffs)
-            check(hipHostMalloc(reinterpret_cast<void**>(&_h_soffs), 8 * (_max + 1) * _d_schars.size()));
+        if (e.resp_nstr && !_s.h_soffs) _s.h_soffs.alloc(8 * (_max + 1) * _s.d_schars.size());
     }
 
     /// call_mixed's own staging beside ensure's: the call index of a chunk,
     /// its counts and its request offsets.
     void ensure_mixed() {
-        if (_d_mindex) return;
-        check_srpc(srpc_frames_mixed_index_bytes(_max, SRPC_FRAMES_MAX_PLANS, &_mindex_bytes), "srpc_frames_mixed_index_bytes");
-        check(hipMalloc(&_d_mindex, _mindex_bytes));
-        check(hipMalloc(reinterpret_cast<void**>(&_d_mcounts), 8 * (SRPC_FRAMES_MAX_PLANS + 1)));
-        check(hipMalloc(reinterpret_cast<void**>(&_d_moffs), 4 * (_max + 1)));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_mcounts), 8 * (SRPC_FRAMES_MAX_PLANS + 2)));
+        if (_s.d_mindex) return;
+        check_srpc(srpc_frames_mixed_index_bytes(_max, SRPC_FRAMES_MAX_PLANS, &_s.mindex_bytes), "srpc_frames_mixed_index_bytes");
+        _s.d_mindex.alloc(_s.mindex_bytes);
+        _s.d_mcounts.alloc(8 * (SRPC_FRAMES_MAX_PLANS + 1));
+        _s.d_moffs.alloc(4 * (_max + 1));
+        _s.h_mcounts.alloc(8 * (SRPC_FRAMES_MAX_PLANS + 2));
     }
 
     /// The string form's staging beside ensure_mixed's: the scratch of both
@@ -958,17 +820,10 @@ private:
         uint64_t a = 0, b = 0;
         check_srpc(srpc_frames_mixed_var_scratch_bytes(rq, nk, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
         check_srpc(srpc_frames_mixed_var_scratch_bytes(rs, nk, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
-        const uint64_t need = std::max(a, b);
-        if (need > _vscratch_cap) {
-            (void)hipFree(_d_vscratch);
-            _d_vscratch = nullptr;
-            _vscratch_cap = 0;
-            check(hipMalloc(&_d_vscratch, need));
-            _vscratch_cap = need;
-        }
-        if (!_d_mv) {
-            check(hipMalloc(reinterpret_cast<void**>(&_d_mv), 8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS)));
-            check(hipHostMalloc(reinterpret_cast<void**>(&_h_mv), 8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS)));
+        ensure_vscratch(std::max(a, b));
+        if (!_s.d_mv) {
+            _s.d_mv.alloc(8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS));
+            _s.h_mv.alloc(8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS));
         }
     }
 
@@ -980,67 +835,28 @@ private:
         if (out <= _out_cap && in <= _in_cap) return;
         if (in >= (1ull << 32)) throw plan_error("batch_client: max_batch replies pass 4 GiB", SRPC_E_CAPACITY);
         std::vector<uint8_t> carry;
-        if (_have) carry.assign(_h_in, _h_in + _have);
-        release();
+        if (_have) carry.assign(_s.h_in.p, _s.h_in + _have);
+        _s = staging{};  // the string and mixed staging is sized by the same capacities
+        _have = 0;
         _out_cap = std::max(out, _out_cap);
         _in_cap = std::max(in, _in_cap);
-        check(hipMalloc(reinterpret_cast<void**>(&_d_out), _out_cap));
-        check(hipMalloc(reinterpret_cast<void**>(&_d_in), _in_cap + 16));
-        check(hipMalloc(reinterpret_cast<void**>(&_d_offs), 4 * _max));
-        check(hipMalloc(reinterpret_cast<void**>(&_d_status), sizeof(srpc_unpack_status)));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_out), _out_cap));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_in), _in_cap));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_offs), 4 * _max));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_codes), _max));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_status), sizeof(srpc_unpack_status)));
-        if (!carry.empty()) std::memcpy(_h_in, carry.data(), carry.size());
+        _s.d_out.alloc(_out_cap);
+        _s.d_in.alloc(_in_cap + 16);
+        _s.d_offs.alloc(4 * _max);
+        _s.d_status.alloc(sizeof(srpc_unpack_status));
+        _s.h_out.alloc(_out_cap);
+        _s.h_in.alloc(_in_cap);
+        _s.h_offs.alloc(4 * _max);
+        _s.h_codes.alloc(_max);
+        _s.h_status.alloc(sizeof(srpc_unpack_status));
+        if (!carry.empty()) std::memcpy(_s.h_in, carry.data(), carry.size());
         _have = carry.size();
-    }
-
-    void release() {
-        (void)hipFree(_d_mv);
-        (void)hipHostFree(_h_mv);
-        _d_mv = _h_mv = nullptr;
-        (void)hipFree(_d_mindex);
-        (void)hipFree(_d_mcounts);
-        (void)hipFree(_d_moffs);
-        (void)hipHostFree(_h_mcounts);
-        _d_mindex = nullptr;
-        _d_mcounts = _h_mcounts = nullptr;
-        _d_moffs = nullptr;
-        // call_var's staging is sized by the same capacities
-        (void)hipFree(_d_wire);
-        (void)hipFree(_d_rec);
-        (void)hipFree(_d_vscratch);
-        (void)hipHostFree(_h_ends);
-        (void)hipHostFree(_h_soffs);
-        for (uint8_t* c : _d_schars) (void)hipFree(c);
-        for (uint64_t* o : _d_soffs) (void)hipFree(o);
-        _d_schars.clear();
-        _d_soffs.clear();
-        _d_wire = nullptr;
-        _d_rec = _h_ends = _h_soffs = nullptr;
-        _d_vscratch = nullptr;
-        _vscratch_cap = 0;
-        (void)hipFree(_d_out);
-        (void)hipFree(_d_in);
-        (void)hipFree(_d_offs);
-        (void)hipFree(_d_status);
-        (void)hipHostFree(_h_out);
-        (void)hipHostFree(_h_in);
-        (void)hipHostFree(_h_offs);
-        (void)hipHostFree(_h_codes);
-        (void)hipHostFree(_h_status);
-        _d_out = _d_in = _h_out = _h_in = _h_codes = nullptr;
-        _d_offs = _h_offs = nullptr;
-        _d_status = _h_status = nullptr;
-        _have = 0;
     }
 
     /// Send the chunk's `total` request bytes while receiving its m replies.
     /// Neither direction blocks: poll waits for whichever is ready.
     frame_walk exchange(uint64_t m, uint64_t total, uint64_t fout, call_stats& st) {
-        frame_walk w = walk_frames(_h_in, _have, m, _h_offs, fout);
+        frame_walk w = walk_frames(_s.h_in, _have, m, _s.h_offs, fout);
         uint64_t sent = 0;
         bool send_dead = false;
         while (w.nframes < m && !_eof) {
@@ -1059,19 +875,19 @@ private:
             }
             if (p.revents & (POLLIN | POLLHUP | POLLERR)) {
                 t0 = clock::now();
-                const ssize_t k = recv(_fd, _h_in + _have, _in_cap - _have, MSG_DONTWAIT);
+                const ssize_t k = recv(_fd, _s.h_in + _have, _in_cap - _have, MSG_DONTWAIT);
                 st.recv_seconds += secs(t0);
                 if (k > 0) {
                     _have += static_cast<uint64_t>(k);
                     st.received_bytes += static_cast<uint64_t>(k);
-                    w = walk_frames(_h_in, _have, m, _h_offs, fout, w);
+                    w = walk_frames(_s.h_in, _have, m, _s.h_offs, fout, w);
                 } else if (k == 0 || (errno != EAGAIN && errno != EWOULDBLOCK && errno != EINTR)) {
                     _eof = true;
                 }
             }
             if ((p.revents & POLLOUT) && sent < total && !send_dead) {
                 t0 = clock::now();
-                const ssize_t k = send(_fd, _h_out + sent, total - sent, MSG_DONTWAIT | MSG_NOSIGNAL);
+                const ssize_t k = send(_fd, _s.h_out + sent, total - sent, MSG_DONTWAIT | MSG_NOSIGNAL);
                 st.send_seconds += secs(t0);
                 if (k > 0) {
                     sent += static_cast<uint64_t>(k);
@@ -1084,46 +900,22 @@ private:
         return w;
     }
 
-    /// The chunk's counts from the codes; only a chunk the decode flagged is
-    /// looked at frame by frame (the table of include/srpc_gpu.h on the host).
-    void count(uint64_t fout, std::vector<uint8_t> const& resp_prefix, frame_walk const& w, call_stats& st) {
-        const uint64_t nf = w.nframes;
-        if (_h_status->flags == 0) {
-            const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
-            st.ok += ok;
-            st.failed += nf - ok;
-            return;
-        }
-        for (uint64_t i = 0; i < nf; ++i) {
-            const uint64_t o = _h_offs[i], end = i + 1 < nf ? _h_offs[i + 1] : w.walked, len = end - o;
-            const uint8_t* f = _h_in + o;
-            const bool full = len == fout && std::memcmp(f, resp_prefix.data(), 4) == 0 &&
-                              std::memcmp(f + 5, resp_prefix.data() + 5, resp_prefix.size() - 5) == 0;
-            const bool bare = len == 5 && f[4] != 0;
-            if (!(full || bare)) st.malformed += 1;
-            else if (_h_codes[i] == RPC_SUCCESS) st.ok += 1;
-            else st.failed += 1;
-        }
+    /// The chunk's counts (tally_replies): from the codes, or, for a chunk the
+    /// decode flagged, from judge(i, o, end) on frame i = bytes [o, end) of the
+    /// receive buffer -- the table of include/srpc_gpu.h on the host.
+    template <class Judge>
+    void count(frame_walk const& w, call_stats& st, Judge&& judge) {
+        const uint32_t* offs = _s.h_offs;
+        tally_replies(_s.h_codes, w.nframes, _s.h_status->flags != 0,
+                      [&](uint64_t i) { return judge(i, offs[i], i + 1 < w.nframes ? offs[i + 1] : w.walked); }, st);
     }
 
-    /// count for a string reply stream: a flagged chunk is recounted with the
-    /// table of srpc_frames_unpack_replies_var on the host (walk_reply_var).
-    void count_var(var_entry const& e, frame_walk const& w, call_stats& st) {
-        const uint64_t nf = w.nframes;
-        if (_h_status->flags == 0) {
-            const uint64_t ok = static_cast<uint64_t>(std::count(_h_codes, _h_codes + nf, static_cast<uint8_t>(RPC_SUCCESS)));
-            st.ok += ok;
-            st.failed += nf - ok;
-            return;
-        }
-        for (uint64_t i = 0; i < nf; ++i) {
-            const uint64_t o = _h_offs[i], end = i + 1 < nf ? _h_offs[i + 1] : w.walked;
-            const reply_frame r = walk_reply_var(_h_in + o, end - o, e.resp_prefix.data(), e.resp_prefix.size(),
-                                                 e.resp_leaf.data(), static_cast<uint32_t>(e.resp_leaf.size()));
-            if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
-            else if (r.code == RPC_SUCCESS) st.ok += 1;
-            else st.failed += 1;
-        }
+    /// The end of every chunk: its reply bytes are kept if asked for; bytes
+    /// after its last frame belong to the next chunk's replies.
+    void end_chunk(frame_walk const& w) {
+        if (_keep) _kept.insert(_kept.end(), _s.h_in.p, _s.h_in + w.walked);
+        std::memmove(_s.h_in, _s.h_in + w.walked, _have - w.walked);
+        _have -= w.walked;
     }
 
     int _fd;
@@ -1137,23 +929,7 @@ private:
     std::vector<uint8_t> _kept;
     call_stats _last;
     uint64_t _out_cap = 0, _in_cap = 0, _have = 0;
-    uint8_t *_d_out = nullptr, *_d_in = nullptr, *_h_out = nullptr, *_h_in = nullptr, *_h_codes = nullptr;
-    uint32_t *_d_offs = nullptr, *_h_offs = nullptr;
-    srpc_unpack_status *_d_status = nullptr, *_h_status = nullptr;
-    // call_var
-    std::map<std::string, var_entry> _vplans;
-    uint8_t* _d_wire = nullptr;
-    uint64_t *_d_rec = nullptr, *_h_ends = nullptr, *_h_soffs = nullptr;
-    void* _d_vscratch = nullptr;
-    uint64_t _vscratch_cap = 0;
-    std::vector<uint8_t*> _d_schars;
-    std::vector<uint64_t*> _d_soffs;
-    // call_mixed
-    void* _d_mindex = nullptr;
-    uint64_t _mindex_bytes = 0;
-    uint64_t *_d_mcounts = nullptr, *_h_mcounts = nullptr;  // _h_mcounts[17]: the chunk's request bytes
-    uint32_t* _d_moffs = nullptr;
-    uint64_t *_d_mv = nullptr, *_h_mv = nullptr;  // [0]: the chunk's request bytes, [1 + s]: reply string slot s's end
+    staging _s;
 };
 
 }  // namespace srpc::gpu

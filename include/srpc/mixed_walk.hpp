@@ -1,10 +1,12 @@
 // srpc/mixed_walk.hpp -- the host form of a mixed batch's ranks and of the
 // per-frame judgement of srpc_frames_unpack_replies_mixed and
 // srpc_frames_unpack_replies_mixed_var (include/srpc_gpu.h).
-// srpc::gpu::batch_client::call_mixed uses it to recount a chunk the device
-// decode flagged (gpu_client.hpp); the kernels apply the same rules.  Host code
-// only, no dependencies, so it can be tested (and sanitized) on its own, like
-// frame_walk.hpp and reply_walk.hpp (whose reply_kind / reply_frame it shares).
+// srpc::gpu::batch_client uses judge_reply_fixed (call, call_var) and
+// judge_reply_mixed (both forms of call_mixed) as the per-frame judges of
+// tally_replies when the device decode flagged a chunk (gpu_client.hpp); the
+// kernels apply the same rules.  Host code only, no dependencies, so it can be
+// tested (and sanitized) on its own, like frame_walk.hpp and reply_walk.hpp
+// (whose reply_kind / reply_frame it shares).
 #pragma once
 
 #include <cstdint>
@@ -69,30 +71,22 @@ struct mixed_reply_plan {
     uint64_t F = 0;       // frame bytes
     uint64_t first = 0;   // h_first[k]
     uint64_t cap = 0;     // h_cap[k]
-    // a string plan (judge_reply_mixed_var): prefix is the unframed `u8 code |
+    // a string plan: prefix is the unframed `u8 code |
     // str(Resp::name)`, F is unused, leaf[f] the bytes of leaf f (0: a string)
     bool var = false;
     const uint8_t* leaf = nullptr;
     uint32_t nleaves = 0;
 };
 
-/// Frame i of a chunk: a bad call (id out of range, or no element left in its
-/// plan's columns) is the table's first row whatever its bytes.  rank: from
-/// mixed_ranks; end: offs[i + 1], or buf_len for the last frame.
+/// Frame i of a chunk against the table of srpc_frames_unpack_replies_mixed or
+/// _mixed_var: a bad call (id out of range, or no element left in its plan's
+/// columns) is the first row whatever its bytes; a frame of a string plan is
+/// judged by walk_reply_var, one of a fixed plan by judge_reply_fixed.  rank:
+/// from mixed_ranks; end: offs[i + 1], or buf_len for the last frame.  Offsets
+/// out of order or past the end are bad_bounds under either; no byte outside
+/// [buf + o, buf + end) is read.
 inline reply_frame judge_reply_mixed(const uint8_t* buf, uint64_t buf_len, uint64_t o, uint64_t end, uint32_t method,
                                      uint32_t rank, const mixed_reply_plan* plans, uint32_t nplans) {
-    if (method >= nplans || rank == mixed_no_rank) return reply_frame{};
-    const mixed_reply_plan& p = plans[method];
-    if (p.first >= p.cap || rank >= p.cap - p.first) return reply_frame{};
-    return judge_reply_fixed(buf, buf_len, o, end, p.F, p.prefix, p.prefix_len);
-}
-
-/// The same for srpc_frames_unpack_replies_mixed_var: a frame of a string plan
-/// is judged by the table of srpc_frames_unpack_replies_var (walk_reply_var), one
-/// of a fixed plan as above.  Offsets out of order or past the end are bad_bounds
-/// under either; no byte outside [buf + o, buf + end) is read.
-inline reply_frame judge_reply_mixed_var(const uint8_t* buf, uint64_t buf_len, uint64_t o, uint64_t end, uint32_t method,
-                                         uint32_t rank, const mixed_reply_plan* plans, uint32_t nplans) {
     if (method >= nplans || rank == mixed_no_rank) return reply_frame{};
     const mixed_reply_plan& p = plans[method];
     if (p.first >= p.cap || rank >= p.cap - p.first) return reply_frame{};

@@ -1,11 +1,13 @@
 // srpc/reply_walk.hpp -- one reply frame of a string response against the
 // per-frame table of srpc_frames_unpack_replies_var (include/srpc_gpu.h), on
-// the host.  srpc::gpu::batch_client::call_var uses it to recount a chunk the
-// device decode flagged (gpu_client.hpp); the kernel applies the same table.
-// Host code only, no dependencies, so it can be tested (and sanitized) on its
-// own, like frame_walk.hpp.
+// the host, and the one rule by which srpc::gpu::batch_client counts a chunk's
+// replies (tally_replies): every form of call recounts a chunk the device
+// decode flagged with a per-frame judge (gpu_client.hpp); the kernels apply the
+// same tables.  Host code only, no dependencies, so it can be tested (and
+// sanitized) on its own, like frame_walk.hpp.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 
 namespace srpc::gpu {
@@ -60,6 +62,27 @@ inline reply_frame walk_reply_var(const uint8_t* f, uint64_t len, const uint8_t*
     }
     if (c == len) r.kind = reply_kind::full;
     return r;
+}
+
+/// Adds a chunk's nframes replies to st.ok / st.failed / st.malformed.  A
+/// chunk the decode did not flag holds only full and bare frames, so codes[i]
+/// (the decode's) tells: 0 (RPC_SUCCESS) is ok, anything else failed.  A flagged
+/// chunk is judged frame by frame on the host: judge(i) is the table's verdict
+/// on frame i, a frame neither full nor bare is malformed whatever its code.
+template <class Stats, class Judge>
+void tally_replies(const uint8_t* codes, uint64_t nframes, bool flagged, Judge&& judge, Stats& st) {
+    if (!flagged) {
+        const uint64_t ok = static_cast<uint64_t>(std::count(codes, codes + nframes, uint8_t{0}));
+        st.ok += ok;
+        st.failed += nframes - ok;
+        return;
+    }
+    for (uint64_t i = 0; i < nframes; ++i) {
+        const reply_frame r = judge(i);
+        if (r.kind != reply_kind::full && r.kind != reply_kind::bare) st.malformed += 1;
+        else if (r.code == 0) st.ok += 1;
+        else st.failed += 1;
+    }
 }
 
 }  // namespace srpc::gpu

@@ -5,7 +5,8 @@
 // device, divide unknown to the server -- packed in call order from per-method
 // columns, answered in request order, decoded into per-method columns with one
 // code per call; a leg that declares one call too few; a peer that closes after
-// half the replies.
+// half the replies; a scripted peer whose middle chunk holds every malformed row
+// of the reply table.
 #include <hip/hip_runtime_api.h>
 #include <srpc/gpu_client.hpp>
 #include <srpc/gpu_server.hpp>
@@ -18,6 +19,8 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+
+#include "scripted_peer.hpp"
 
 static int g_fail = 0, g_pass = 0;
 #define CHECK(c)                                                                    \
@@ -271,10 +274,69 @@ static void peer_closes_after_half() {
     peer.join();
 }
 
+// Three chunks of 16, 16 and 8 calls answered in one send by a scripted peer
+// (every leg's reply a Number holding the request's last int32): the middle
+// chunk holds a wrong name (PREFIX), a bare frame, an empty payload (BOUNDS) and a
+// full frame with a nonzero code, on calls of at least two legs with nonzero
+// first[], so its counts come from the host's recount (judge_reply_mixed).
+static void flagged_middle_chunk() {
+    constexpr uint64_t n = 40, batch = 16;
+    mixed_calls d(n);
+    // the chunk's first call, then the first call of another leg, then the next two
+    const uint64_t kName = batch;
+    uint64_t kBare = kName + 1;
+    while (kBare < 2 * batch && d.method[kBare] == d.method[kName]) ++kBare;
+    CHECK(kBare + 2 < 2 * batch);
+    const uint64_t kEmpty = kBare + 1, kCode = kBare + 2;
+    CHECK(d.rank[kName] > 0 || d.rank[kBare] > 0);  // first[k] != 0 for one of them
+    scripted::bytes replies;
+    std::vector<int32_t> last(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        const int k = d.method[i];
+        last[i] = k == 0 ? d.left[k][d.rank[i]] : d.right[k][d.rank[i]];
+        Number v;
+        v.num = last[i];
+        const scripted::bytes f = i == kBare    ? scripted::bare(srpc::RPC_ERR_FUNCTION_NOT_REGISTERED)
+                                  : i == kName  ? scripted::wrong_name(scripted::full(v))
+                                  : i == kEmpty ? scripted::empty()
+                                  : i == kCode  ? scripted::full(v, srpc::RPC_ERR_RECV_TIMEOUT)
+                                                : scripted::full(v);
+        replies.insert(replies.end(), f.begin(), f.end());
+    }
+    int sv[2];
+    if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
+    std::thread peer = scripted::answer_at_once(sv[1], batch, replies);
+    {
+        srpc::gpu::batch_client cl(sv[0], batch);
+        const srpc::gpu::call_stats st = cl.call_mixed(d.legs(cl), d.d_method, n, d.d_codes);
+        d.fetch();
+        bool right = true;
+        uint64_t sent = 0;
+        const uint64_t fin[kLegs] = {57, 62, 67, 67, 65};
+        for (uint64_t i = 0; i < n; ++i) {
+            const int32_t out = d.out[d.method[i]][d.rank[i]];
+            if (i < batch) sent += fin[d.method[i]];
+            if (i == kBare) right = right && d.hcodes[i] == srpc::RPC_ERR_FUNCTION_NOT_REGISTERED && out == 0;
+            else if (i == kName) right = right && d.hcodes[i] == srpc::RPC_SUCCESS && out == 0;  // payload[0], zero
+            else if (i == kEmpty) right = right && d.hcodes[i] == SRPC_REPLY_NO_CODE && out == 0;
+            else if (i == kCode) right = right && d.hcodes[i] == srpc::RPC_ERR_RECV_TIMEOUT && out == last[i];
+            else right = right && d.hcodes[i] == srpc::RPC_SUCCESS && out == last[i];
+        }
+        CHECK(right);
+        CHECK(st.calls == n && st.ok == n - 4 && st.failed == 2 && st.malformed == 2 && st.unanswered == 0);
+        CHECK(st.chunks == 3 && st.uniform_chunks == 0);
+        // the later chunks' replies were there before their requests could leave
+        CHECK(st.received_bytes == replies.size() && st.sent_bytes == sent);
+    }
+    close(sv[0]);
+    peer.join();
+}
+
 int main() {
     five_legs_in_call_order();
     a_leg_one_call_short();
     peer_closes_after_half();
+    flagged_middle_chunk();
     std::printf("%d passed, %d failed\n", g_pass, g_fail);
     return g_fail ? 1 : 0;
 }

@@ -5,7 +5,9 @@
 // status code per call -- all replies full (the uniform decode), every 7th
 // call to a method the server does not know (bare error frames among full
 // ones), the host-vector overload against packer::unpack_response<Number> on
-// the same reply bytes, and a peer that closes after half the replies.
+// the same reply bytes, a peer that closes after half the replies, and a
+// scripted peer whose middle chunk holds every malformed row of the reply table
+// (the chunk is flagged and recounted frame by frame on the host).
 #include <hip/hip_runtime_api.h>
 #include <srpc/gpu_client.hpp>
 #include <srpc/gpu_server.hpp>
@@ -17,6 +19,8 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+
+#include "scripted_peer.hpp"
 
 static int g_fail = 0, g_pass = 0;
 #define CHECK(c)                                                                    \
@@ -242,6 +246,49 @@ static void peer_closes_after_half() {
     peer.join();
 }
 
+// Three chunks of 16, 16 and 8 calls answered in one send: the middle chunk
+// holds a bare frame, a full frame with a nonzero code, a wrong name (PREFIX)
+// and an empty payload (BOUNDS), so its counts come from the host's recount.
+static void flagged_middle_chunk() {
+    constexpr uint64_t n = 40, batch = 16;
+    constexpr uint64_t kBare = 18, kName = 21, kEmpty = 25, kCode = 28;
+    device_calls d(n);
+    scripted::bytes replies;
+    for (uint64_t i = 0; i < n; ++i) {
+        Number v;
+        v.num = d.in[i];
+        const scripted::bytes f = i == kBare    ? scripted::bare(srpc::RPC_ERR_FUNCTION_NOT_REGISTERED)
+                                  : i == kName  ? scripted::wrong_name(scripted::full(v))
+                                  : i == kEmpty ? scripted::empty()
+                                  : i == kCode  ? scripted::full(v, srpc::RPC_ERR_RECV_TIMEOUT)
+                                                : scripted::full(v);
+        replies.insert(replies.end(), f.begin(), f.end());
+    }
+    int sv[2];
+    if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
+    std::thread peer = scripted::answer_at_once(sv[1], batch, replies);
+    {
+        srpc::gpu::batch_client cl(sv[0], batch);
+        const srpc::gpu::call_stats st = cl.call<Number, Number>(kMethod, &d.req, n, &d.resp, d.codes);
+        d.fetch();
+        bool right = true;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (i == kBare) right = right && d.hcodes[i] == srpc::RPC_ERR_FUNCTION_NOT_REGISTERED && d.out[i] == 0;
+            else if (i == kName) right = right && d.hcodes[i] == srpc::RPC_SUCCESS && d.out[i] == 0;  // payload[0], zero
+            else if (i == kEmpty) right = right && d.hcodes[i] == SRPC_REPLY_NO_CODE && d.out[i] == 0;
+            else if (i == kCode) right = right && d.hcodes[i] == srpc::RPC_ERR_RECV_TIMEOUT && d.out[i] == d.in[i];
+            else right = right && d.hcodes[i] == srpc::RPC_SUCCESS && d.out[i] == d.in[i];
+        }
+        CHECK(right);
+        CHECK(st.calls == n && st.ok == n - 4 && st.failed == 2 && st.malformed == 2 && st.unanswered == 0);
+        CHECK(st.chunks == 3 && st.uniform_chunks == 2);
+        // the later chunks' replies were there before their requests could leave
+        CHECK(st.received_bytes == replies.size() && st.sent_bytes == batch * request_bytes());
+    }
+    close(sv[0]);
+    peer.join();
+}
+
 static void string_schemas_refused() {
     int sv[2];
     if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
@@ -270,6 +317,7 @@ int main() {
     every_seventh_unknown();
     host_vectors_match_scalar_unpack();
     peer_closes_after_half();
+    flagged_middle_chunk();
     string_schemas_refused();
     std::printf("%d passed, %d failed\n", g_pass, g_fail);
     return g_fail ? 1 : 0;

@@ -9,8 +9,9 @@
 // column too small for the reply chars, requests too large for the send
 // buffer.  Against a scalar peer built on the
 // packer itself: Text -> Number and Number -> Text (each side's fixed path;
-// batch_server's string methods take strings on both sides) and a peer that
-// closes after half the replies.
+// batch_server's string methods take strings on both sides), a peer that
+// closes after half the replies, and a scripted peer whose middle chunk holds
+// every malformed row of the string reply table.
 #include <hip/hip_runtime_api.h>
 #include <srpc/gpu_client.hpp>
 #include <srpc/gpu_server.hpp>
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "echo_records.hpp"
+#include "scripted_peer.hpp"
 
 static int g_fail = 0, g_pass = 0;
 #define CHECK(c)                                                                    \
@@ -420,6 +422,60 @@ static void peer_closes_after_half() {
     peer.join();
 }
 
+// Three chunks of 16, 16 and 8 calls answered in one send by a scripted peer:
+// the middle chunk holds a bare frame, a full frame with a nonzero code, a wrong
+// name (PREFIX), an empty payload and a string running past its frame (BOUNDS),
+// so its counts come from the host's recount (walk_reply_var).
+static void flagged_middle_chunk() {
+    constexpr uint64_t n = 40, batch = 16;
+    constexpr uint64_t kBare = 18, kName = 21, kEmpty = 25, kOverrun = 27, kCode = 29;
+    mp_calls d(n);
+    scripted::bytes replies;
+    uint64_t chars = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const scripted::bytes f = i == kBare      ? scripted::bare(srpc::RPC_ERR_FUNCTION_NOT_REGISTERED)
+                                  : i == kName    ? scripted::wrong_name(scripted::full(d.in[i]))
+                                  : i == kEmpty   ? scripted::empty()
+                                  : i == kOverrun ? scripted::string_overrun(scripted::full(d.in[i]), d.in[i].arg4.size())
+                                  : i == kCode    ? scripted::full(d.in[i], srpc::RPC_ERR_RECV_TIMEOUT)
+                                                  : scripted::full(d.in[i]);
+        replies.insert(replies.end(), f.begin(), f.end());
+        if (i != kBare && i != kName && i != kEmpty && i != kOverrun) chars += d.in[i].arg4.size();
+    }
+    int sv[2];
+    if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
+    std::thread peer = scripted::answer_at_once(sv[1], batch, replies);
+    {
+        srpc::gpu::batch_client cl(sv[0], batch);
+        const srpc::gpu::call_stats st = d.call(cl);
+        d.fetch(n);
+        std::vector<MP> got;
+        d.hout.gather(got);
+        bool right = true;
+        uint64_t sent = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (i < batch) sent += frame_bytes(d.in[i], true);
+            if (i == kBare) right = right && d.hcodes[i] == srpc::RPC_ERR_FUNCTION_NOT_REGISTERED && zero(got[i]);
+            else if (i == kName || i == kOverrun) right = right && d.hcodes[i] == srpc::RPC_SUCCESS && zero(got[i]);  // payload[0]
+            else if (i == kEmpty) right = right && d.hcodes[i] == SRPC_REPLY_NO_CODE && zero(got[i]);
+            else if (i == kCode) right = right && d.hcodes[i] == srpc::RPC_ERR_RECV_TIMEOUT && same(got[i], d.in[i]);
+            else right = right && d.hcodes[i] == srpc::RPC_SUCCESS && same(got[i], d.in[i]);
+        }
+        CHECK(right);
+        // absolute offsets over the three chunks; the malformed replies are empty strings
+        CHECK(d.offsets_monotone_from_zero() && d.roffs[n] == chars && d.roffs[batch] == d.hin.offs[3][batch]);
+        bool guard = true;
+        for (uint64_t k = d.roffs[n]; k < d.chars_cap + 64; ++k) guard = guard && d.rchars[k] == 0xA5;
+        CHECK(guard);
+        CHECK(st.calls == n && st.ok == n - 5 && st.failed == 2 && st.malformed == 3 && st.unanswered == 0);
+        CHECK(st.chunks == 3 && st.uniform_chunks == 0);
+        // the later chunks' replies were there before their requests could leave
+        CHECK(st.received_bytes == replies.size() && st.sent_bytes == sent);
+    }
+    close(sv[0]);
+    peer.join();
+}
+
 static void response_column_too_small() {
     constexpr uint64_t n = 1000, batch = 256;
     srpc::gpu::host_columns<MP> probe;
@@ -479,6 +535,7 @@ int main() {
     each_side_fixed();
     host_vectors_match_scalar_unpack();
     peer_closes_after_half();
+    flagged_middle_chunk();
     response_column_too_small();
     requests_too_large();
     std::printf("%d passed, %d failed\n", g_pass, g_fail);

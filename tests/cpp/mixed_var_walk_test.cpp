@@ -1,4 +1,4 @@
-// srpc::gpu::judge_reply_mixed_var (include/srpc/mixed_walk.hpp): the host form
+// srpc::gpu::judge_reply_mixed (include/srpc/mixed_walk.hpp): the host form
 // of the per-frame tables of srpc_frames_unpack_replies_mixed_var -- a string
 // plan's frame by the table of srpc_frames_unpack_replies_var, a fixed plan's by
 // that of srpc_frames_unpack_replies, each call under its own plan.  A
@@ -106,7 +106,7 @@ static std::unique_ptr<uint8_t[]> exact(bytes const& b) {
 // the frame alone in a stream of exactly its bytes, judged as a call of plan k
 static reply_frame judge(plans3 const& P, uint32_t k, bytes const& f, uint32_t rank = 0) {
     const auto b = exact(f);
-    return judge_reply_mixed_var(b.get(), f.size(), 0, f.size(), k, rank, P.plans.data(), 3);
+    return judge_reply_mixed(b.get(), f.size(), 0, f.size(), k, rank, P.plans.data(), 3);
 }
 
 static bool is(reply_frame r, reply_kind kind, uint8_t code) { return r.kind == kind && r.code == code; }
@@ -183,8 +183,8 @@ static void bad_calls_and_offsets() {
     const bytes f = P.text(0, "abc");
     // an id out of range, no rank, no element left: the first row whatever the bytes
     const auto b = exact(f);
-    CHECK(is(judge_reply_mixed_var(b.get(), f.size(), 0, f.size(), 3, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
-    CHECK(is(judge_reply_mixed_var(b.get(), f.size(), 0, f.size(), 2, mixed_no_rank, P.plans.data(), 3),
+    CHECK(is(judge_reply_mixed(b.get(), f.size(), 0, f.size(), 3, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
+    CHECK(is(judge_reply_mixed(b.get(), f.size(), 0, f.size(), 2, mixed_no_rank, P.plans.data(), 3),
              reply_kind::bad_bounds, 0xFF));
     P.plans[2].first = 990;
     CHECK(is(judge(P, 2, f, 9), reply_kind::full, 0));
@@ -194,10 +194,10 @@ static void bad_calls_and_offsets() {
     P.plans[2].first = 0;
     // offsets out of order or past the end, under a string plan and a fixed one: nothing is read
     for (uint32_t k : {0u, 2u}) {
-        CHECK(is(judge_reply_mixed_var(b.get(), f.size(), 5, 2, k, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
-        CHECK(is(judge_reply_mixed_var(b.get(), f.size(), 0, f.size() + 1, k, 0, P.plans.data(), 3), reply_kind::bad_bounds,
+        CHECK(is(judge_reply_mixed(b.get(), f.size(), 5, 2, k, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
+        CHECK(is(judge_reply_mixed(b.get(), f.size(), 0, f.size() + 1, k, 0, P.plans.data(), 3), reply_kind::bad_bounds,
                  0xFF));
-        CHECK(is(judge_reply_mixed_var(b.get(), f.size(), f.size() + 1, f.size() + 9, k, 0, P.plans.data(), 3),
+        CHECK(is(judge_reply_mixed(b.get(), f.size(), f.size() + 1, f.size() + 9, k, 0, P.plans.data(), 3),
                  reply_kind::bad_bounds, 0xFF));
     }
     // two frames in one stream, each judged inside its own bytes
@@ -206,9 +206,9 @@ static void bad_calls_and_offsets() {
     const bytes second = P.number(2, 9);
     two.insert(two.end(), second.begin(), second.end());
     const auto s = exact(two);
-    CHECK(is(judge_reply_mixed_var(s.get(), two.size(), 0, cut, 1, 0, P.plans.data(), 3), reply_kind::full, 0));
-    CHECK(is(judge_reply_mixed_var(s.get(), two.size(), cut, two.size(), 0, 0, P.plans.data(), 3), reply_kind::full, 2));
-    CHECK(is(judge_reply_mixed_var(s.get(), two.size(), 0, two.size(), 1, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
+    CHECK(is(judge_reply_mixed(s.get(), two.size(), 0, cut, 1, 0, P.plans.data(), 3), reply_kind::full, 0));
+    CHECK(is(judge_reply_mixed(s.get(), two.size(), cut, two.size(), 0, 0, P.plans.data(), 3), reply_kind::full, 2));
+    CHECK(is(judge_reply_mixed(s.get(), two.size(), 0, two.size(), 1, 0, P.plans.data(), 3), reply_kind::bad_bounds, 0xFF));
 }
 
 int main() {

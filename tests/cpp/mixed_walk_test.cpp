@@ -1,6 +1,7 @@
 // srpc::gpu::mixed_ranks / judge_reply_fixed / judge_reply_mixed
 // (include/srpc/mixed_walk.hpp): the host form of a mixed batch's ranks and of
-// the per-frame table of srpc_frames_unpack_replies_mixed.  A stand-alone
+// the per-frame table of srpc_frames_unpack_replies_mixed, and tally_replies
+// (include/srpc/reply_walk.hpp) over literal chunks of them.  A stand-alone
 // program, so it can be built with -fsanitize=address,undefined and simply
 // run: every stream is a heap allocation of exactly its bytes, so a read past
 // its end is an ASan error.
@@ -170,10 +171,133 @@ static void truncated_streams() {
     CHECK(ok);
 }
 
+struct tally {
+    uint64_t ok = 0, failed = 0, malformed = 0;
+    bool is(uint64_t o, uint64_t f, uint64_t m) const { return ok == o && failed == f && malformed == m; }
+};
+
+// The rule batch_client::call counted a flagged chunk by before it used
+// judge_reply_fixed: 'm' malformed, 'o' ok, 'f' failed, from the frame's bytes
+// and the code the decode gave it.
+static char inline_rule(const uint8_t* f, uint64_t len, uint64_t fout, bytes const& prefix, uint8_t code) {
+    const bool full = len == fout && std::memcmp(f, prefix.data(), 4) == 0 &&
+                      std::memcmp(f + 5, prefix.data() + 5, prefix.size() - 5) == 0;
+    const bool bare = len == 5 && f[4] != 0;
+    return !(full || bare) ? 'm' : code == 0 ? 'o' : 'f';
+}
+
+// tally_replies over a literal chunk of one fixed method (plan 0: Number, F =
+// 23): the shortcut of an unflagged chunk trusts the codes, the recount of a
+// flagged one judges every frame, and judge_reply_fixed classifies every row as
+// the inline rule did.
+static void tally_of_a_fixed_chunk() {
+    const plan3 P;
+    const uint64_t F = P.plans[0].F;
+    struct row {
+        bytes frame;
+        uint8_t code;  // d_codes[i] by the table of srpc_frames_unpack_replies
+        char want;     // the recount's verdict
+    };
+    std::vector<row> rows;
+    rows.push_back({P.frame(0, 0, 0x11), 0, 'o'});  // full
+    rows.push_back({P.frame(0, 2, 0x22), 2, 'f'});  // full with a nonzero code
+    rows.push_back({{0, 0, 0, 1, 1}, 1, 'f'});      // bare
+    rows.push_back({{0, 0, 0, 1, 0}, 0, 'm'});      // bare with code 0: no answer (PREFIX)
+    bytes g = P.frame(0, 0, 0x33);
+    g[13] ^= 0x20;
+    rows.push_back({g, 0, 'm'});  // one prefix byte wrong, the length right (PREFIX)
+    rows.push_back({P.frame(0, 200, 0x44), 200, 'f'});  // only the code byte differs from the plan's prefix: full
+    g = P.frame(0, 0, 0x55);
+    g.push_back(0);
+    g[3] += 1;
+    rows.push_back({g, 0, 'm'});  // one byte longer, its BE32 agreeing (PREFIX)
+    g = P.frame(0, 0, 0x66);
+    g.pop_back();
+    g[3] -= 1;
+    rows.push_back({g, 0, 'm'});             // one byte shorter
+    rows.push_back({{0, 0, 0, 0}, 0xFF, 'm'});  // an empty payload (BOUNDS, SRPC_REPLY_NO_CODE)
+    CHECK(rows[0].frame.size() == F);
+
+    bytes stream;
+    std::vector<uint64_t> offs;
+    std::vector<uint8_t> codes;
+    for (row const& r : rows) {
+        offs.push_back(stream.size());
+        stream.insert(stream.end(), r.frame.begin(), r.frame.end());
+        codes.push_back(r.code);
+    }
+    offs.push_back(stream.size());
+    auto b = exact(stream.data(), stream.size());
+    const uint64_t n = rows.size();
+    auto judge = [&](uint64_t i) {
+        return judge_reply_fixed(b.get(), stream.size(), offs[i], offs[i + 1], F, P.prefix[0].data(), P.prefix[0].size());
+    };
+    // every row alone: the verdict stated, and the inline rule's
+    bool each = true, as_before = true;
+    for (uint64_t i = 0; i < n; ++i) {
+        tally t;
+        tally_replies(codes.data() + i, 1, true, [&](uint64_t) { return judge(i); }, t);
+        const char got = t.malformed ? 'm' : t.ok ? 'o' : 'f';
+        each = each && t.ok + t.failed + t.malformed == 1 && got == rows[i].want;
+        as_before = as_before && got == inline_rule(b.get() + offs[i], offs[i + 1] - offs[i], F, P.prefix[0], codes[i]);
+    }
+    CHECK(each);
+    CHECK(as_before);
+    // the chunk, flagged: 1 ok, 3 failed, 5 malformed
+    tally t;
+    tally_replies(codes.data(), n, true, judge, t);
+    CHECK(t.is(1, 3, 5));
+    // the shortcut reads the codes alone: 5 zeros, 4 others, nothing malformed -- right only for an unflagged chunk
+    tally s;
+    tally_replies(codes.data(), n, false, judge, s);
+    CHECK(s.is(5, 4, 0));
+    // an unflagged chunk (the first three rows: full, full with a code, bare) counts the same either way
+    tally u, v;
+    tally_replies(codes.data(), 3, false, judge, u);
+    tally_replies(codes.data(), 3, true, judge, v);
+    CHECK(u.is(1, 2, 0) && v.is(1, 2, 0));
+    // both add to what is there, and no frames add nothing
+    tally_replies(codes.data(), 3, false, judge, u);
+    tally_replies(codes.data(), 0, true, judge, u);
+    tally_replies(codes.data(), 0, false, judge, u);
+    CHECK(u.is(2, 4, 0));
+}
+
+// The same through judge_reply_mixed over two plans, one of them short of
+// elements: a bad call's frame is malformed whatever its bytes.
+static void tally_of_a_mixed_chunk() {
+    plan3 P;
+    P.plans[1].first = 998;  // two elements left
+    const uint8_t method[6] = {0, 1, 1, 1, 0, 7};
+    uint32_t rank[6];
+    uint64_t counts[4];
+    (void)mixed_ranks(method, 6, 3, rank, counts);
+    const bytes frames[6] = {P.frame(0, 0, 1), P.frame(1, 0, 2), P.frame(1, 3, 3),
+                             P.frame(1, 0, 4),  // plan 1's third call: no element left
+                             {0, 0, 0, 1, 1},   // bare
+                             P.frame(0, 0, 5)};  // an id out of range
+    const uint8_t codes[6] = {0, 0, 3, 0xFF, 1, 0xFF};
+    bytes stream;
+    std::vector<uint64_t> offs;
+    for (bytes const& f : frames) {
+        offs.push_back(stream.size());
+        stream.insert(stream.end(), f.begin(), f.end());
+    }
+    offs.push_back(stream.size());
+    auto b = exact(stream.data(), stream.size());
+    tally t;
+    tally_replies(codes, 6, true, [&](uint64_t i) {
+        return judge_reply_mixed(b.get(), stream.size(), offs[i], offs[i + 1], method[i], rank[i], P.plans.data(), 3);
+    }, t);
+    CHECK(t.is(2, 2, 2));
+}
+
 int main() {
     ranks();
     table();
     truncated_streams();
+    tally_of_a_fixed_chunk();
+    tally_of_a_mixed_chunk();
     std::printf("%d passed, %d failed\n", g_pass, g_fail);
     return g_fail ? 1 : 0;
 }

@@ -1,5 +1,6 @@
 // srpc::gpu::walk_reply_var (include/srpc/reply_walk.hpp): the host form of the
-// per-frame table of srpc_frames_unpack_replies_var.  A stand-alone program,
+// per-frame table of srpc_frames_unpack_replies_var, and tally_replies over a
+// literal chunk of such frames.  A stand-alone program,
 // so it can be built with -fsanitize=address,undefined and simply run: every
 // frame is a heap allocation of exactly its bytes, so a read past the frame's
 // end is an ASan error.
@@ -158,6 +159,31 @@ int main() {
         g.push_back(0);
         set_be32(g, static_cast<uint32_t>(g.size() - 4));
         CHECK(is(walk(g), reply_kind::bad_bounds, 0));
+    }
+    // ---- tally_replies over a literal chunk of string replies ----
+    {
+        struct tally {
+            uint64_t ok = 0, failed = 0, malformed = 0;
+            bool is(uint64_t o, uint64_t f, uint64_t m) const { return ok == o && failed == f && malformed == m; }
+        };
+        bytes wrong = full_frame(0, "ab", "c");
+        wrong[4 + 9] ^= 0x20;  // the name's first letter
+        bytes overrun = full_frame(0, "hello", "wor");
+        overrun[4 + P + 8 + 5 + 4 + 1] = 4;  // c's length + 1024: past the frame's end
+        const std::vector<bytes> frames = {full_frame(0, "hello", ""), full_frame(2, "", "x"), framed({1}), framed({0}),
+                                           wrong,                      overrun,                framed({})};
+        const uint8_t codes[7] = {0, 2, 1, 0, 0, 0, 0xFF};  // d_codes by the table
+        auto judge = [&](uint64_t i) { return walk(frames[i]); };
+        tally t;
+        srpc::gpu::tally_replies(codes, 7, true, judge, t);  // flagged: frame by frame
+        CHECK(t.is(1, 2, 4));
+        tally s;
+        srpc::gpu::tally_replies(codes, 7, false, judge, s);  // the shortcut trusts the codes: right only when unflagged
+        CHECK(s.is(4, 3, 0));
+        tally u, v;  // the three well-formed rows alone count the same either way
+        srpc::gpu::tally_replies(codes, 3, false, judge, u);
+        srpc::gpu::tally_replies(codes, 3, true, judge, v);
+        CHECK(u.is(1, 2, 0) && v.is(1, 2, 0));
     }
     std::printf("%d passed, %d failed\n", g_pass, g_fail);
     return g_fail ? 1 : 0;

@@ -1,0 +1,24 @@
+"""One srpc::gpu::batch_client making every form of call (call, call_var, both
+call_mixed forms) on one connection, its staging growing in between:
+tests/cpp/gpu_client_forms_test.cpp."""
+import os
+import subprocess
+
+import pytest
+
+from tests.cpp import build_cpp
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def test_cpp_batch_client_every_form_on_one_connection():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from srpc_amd import build
+    build.build()
+    exe = build_cpp.build_one(os.path.join(HERE, "cpp", "gpu_client_forms_test.cpp"))
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and " 0 failed" in out.stdout, out.stdout + out.stderr

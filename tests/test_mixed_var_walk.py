@@ -1,4 +1,4 @@
-"""judge_reply_mixed_var (include/srpc/mixed_walk.hpp), the host restatement of
+"""judge_reply_mixed (include/srpc/mixed_walk.hpp), the host restatement of
 the decode's per-frame tables with string plans, row by row and with string
 lengths of 2^63 and 2^64 - 1, under AddressSanitizer / UndefinedBehaviorSanitizer
 in a stand-alone program: tests/cpp/mixed_var_walk_test.cpp."""
