@@ -30,6 +30,19 @@
 // srpc::server, in its place in the reply order; only those frames leave the
 // GPU path.  A frame longer than the batch buffer is read on its own and
 // answered the same way.
+//
+// The buckets are filled with atomics: a handler sees its requests in an order
+// that differs from run to run, and no handler sees the order across methods.
+// Ordered mode (set_ordered / set_ordered_handler; fixed-size methods only)
+// serves a batch in arrival order instead:
+//
+//   H2D -> srpc_frames_unpack_requests_mixed (every frame classified as above
+//   and decoded straight into its method's request columns at its arrival
+//   rank) -> the handlers, or the one ordered handler with each frame's method
+//   and rank -> srpc_frames_pack_requests_mixed over the framed response plans
+//   (the replies in arrival order, nothing for an unknown frame) -> D2H.
+//
+// No gather, no scatter and no second response buffer, whatever the mix.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -140,6 +153,24 @@ struct var_batch {
 struct var_limits {
     uint64_t max_request_bytes = 512;  // frame bytes the receive buffer is sized for
     uint64_t max_response_chars = 256; // chars of one response's string field (batch average)
+};
+
+/// A batch in ordered mode (batch_server::set_ordered_handler): the n frames
+/// of the batch in arrival order.  Frame i is a request of method d_method[i]
+/// (registration order) and element d_rank[i] of that method's columns --
+/// req_cols[k][f] / resp_cols[k][f], one column per flattened field of the
+/// method's Req / Resp, as handler_t gets them.  d_method[i] ==
+/// SRPC_FRAME_UNKNOWN (d_rank[i] == 0xFFFFFFFF): no registered method's frame;
+/// the CPU server answers it after the handler ran.  The handler writes element
+/// d_rank[i] of method d_method[i]'s response columns for every other frame.
+struct ordered_batch {
+    uint64_t n = 0;
+    const uint8_t* d_method = nullptr;   // device, n
+    const uint32_t* d_rank = nullptr;    // device, n
+    const uint64_t* counts = nullptr;    // host, methods + 1: frames per method, then the unknown ones
+    size_t methods = 0;
+    void* const* const* req_cols = nullptr;   // host array per method of device columns
+    void* const* const* resp_cols = nullptr;
 };
 
 struct batch_stats {
@@ -264,6 +295,40 @@ public:
         release();
     }
 
+    /// handler(batch, stream) over a whole batch of every method in arrival
+    /// order (ordered_batch).
+    using ordered_handler_t = std::function<int(ordered_batch const&, hipStream_t)>;
+
+    /// Ordered mode (off by default).  The bucket route hands each method its
+    /// requests in an order that differs from run to run; in ordered mode
+    /// request r of a method's batch is the r-th frame of that method in
+    /// arrival order, and the batch goes through one
+    /// srpc_frames_unpack_requests_mixed and one srpc_frames_pack_requests_mixed
+    /// over the response plans whatever its mix: no gather, no scatter.
+    /// Fixed-size methods only: serve_connection throws
+    /// plan_error(SRPC_E_UNSUPPORTED) when a register_var_method method is
+    /// present.
+    void set_ordered(bool on) {
+        if (on == _ordered) return;
+        _ordered = on;
+        release();
+    }
+    bool ordered() const { return _ordered; }
+    /// One handler for every method, run once per batch instead of the
+    /// per-method handlers; implies ordered mode.  Batches reach it in
+    /// connection order on the server's stream, so device state it keeps sees
+    /// the registered methods' requests in the order they arrived, across
+    /// methods.  Frames the GPU path does not take (a method nobody registered,
+    /// a malformed frame) are answered by the CPU server AFTER the batch's
+    /// handler ran: a service that needs a total order registers all its
+    /// methods.  At serve start it is run once on a batch of one unknown frame
+    /// (every counts[k] == 0), as the per-method handlers are run on one zero
+    /// record.
+    void set_ordered_handler(ordered_handler_t handler) {
+        _ohandler = std::move(handler);
+        set_ordered(true);
+    }
+
     uint64_t request_frame_bytes(size_t k = 0) const { return _m.at(k)->fin; }
     uint64_t response_frame_bytes(size_t k = 0) const { return _m.at(k)->fout; }
     /// Bytes of the receive buffer: max_batch frames of the longest method.
@@ -280,6 +345,9 @@ public:
     /// waiting.  Answers leave in request order.
     batch_stats serve_connection(int fd) {
         if (_m.empty()) throw plan_error("batch_server::serve_connection (no methods)", SRPC_E_INVALID);
+        if (_ordered && any_var_method())
+            throw plan_error("batch_server::serve_connection (ordered mode with a string-bodied method)",
+                             SRPC_E_UNSUPPORTED);
         check(hipSetDevice(_dev));
         ensure();
         batch_stats st;
@@ -528,16 +596,39 @@ private:
         check(hipMalloc(&_d_in, _cap + 16));
         check(hipMalloc(&_d_offs, 4 * _max + 16));
         check(hipMalloc(&_d_cls, _max + 16));
-        check(hipMalloc(&_d_index, 4 * K * _max + 16));
         check(hipMalloc(&_d_counts, 8 * (K + 2) + 16));
-        check(hipMalloc(&_d_out_off, 8 * (_max + 1) + 16));
-        check(hipMalloc(&_d_gather, _cap + 16));
-        check(hipMalloc(&_d_resp, out_cap + 16));
         check(hipMalloc(&_d_out, out_cap + 16));
         check(hipMalloc(&_d_status, 2 * K * sizeof(srpc_unpack_status)));
-        check_srpc(srpc_frames_scratch_bytes(_max, static_cast<int>(K), &_scratch_bytes), "srpc_frames_scratch_bytes");
-        check(hipMalloc(&_d_scratch, _scratch_bytes));
+        if (_ordered) {
+            // the call index and the ranks stand in for the buckets: no bucket
+            // index, no gather buffer, no second response buffer
+            check_srpc(srpc_frames_mixed_index_bytes(_max, static_cast<int>(K), &_mix_index_bytes),
+                       "srpc_frames_mixed_index_bytes");
+            check(hipMalloc(&_d_mix_index, _mix_index_bytes + 16));
+            check(hipMalloc(&_d_rank, 4 * _max + 16));
+        } else {
+            check(hipMalloc(&_d_index, 4 * K * _max + 16));
+            check(hipMalloc(&_d_out_off, 8 * (_max + 1) + 16));
+            check(hipMalloc(&_d_gather, _cap + 16));
+            check(hipMalloc(&_d_resp, out_cap + 16));
+            check_srpc(srpc_frames_scratch_bytes(_max, static_cast<int>(K), &_scratch_bytes),
+                       "srpc_frames_scratch_bytes");
+            check(hipMalloc(&_d_scratch, _scratch_bytes));
+        }
         _in_plans.clear();
+        _out_plans.clear();
+        _req_tbl.clear();
+        _resp_tbl.clear();
+        _const_resp.clear();
+        _caps.assign(K, _max);
+        for (auto const& m : _m) {
+            _out_plans.push_back(m->out->get());
+            _req_tbl.push_back(m->req_cols.data());
+            _const_resp.emplace_back(m->resp_cols.begin(), m->resp_cols.end());
+        }
+        for (auto const& c : _const_resp) _resp_tbl.push_back(c.data());
+        _resp_mut_tbl.clear();
+        for (auto const& m : _m) _resp_mut_tbl.push_back(m->resp_cols.data());
         _resp_bytes.clear();
         _var_rec.clear();
         _var_idx.clear();
@@ -555,6 +646,7 @@ private:
     /// buffer, at serve start: first uses cost milliseconds that otherwise land
     /// on the connection's first batch (profiles/r02_e2e_warmup.log).
     void warm_up() {
+        if (_ordered) return warm_up_ordered();
         const int K = static_cast<int>(_m.size());
         const uint64_t out_cap = this->out_cap();
         check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
@@ -622,6 +714,82 @@ private:
             check(hipStreamSynchronize(_s));
         }
     }
+    /// Ordered mode, the decode half of a batch: one
+    /// srpc_frames_unpack_requests_mixed over the nf frames in _d_in[0, used)
+    /// into the methods' request columns (and the ranks, when the ordered
+    /// handler is set), then the counts on the host after one sync.
+    void ordered_decode(uint64_t nf, uint64_t used) {
+        const int K = static_cast<int>(_m.size());
+        check(hipMemsetAsync(_d_status, 0, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status), _s));
+        check_srpc(srpc_frames_unpack_requests_mixed(_in_plans.data(), K, static_cast<const uint8_t*>(_d_in), used,
+                                                     static_cast<const uint32_t*>(_d_offs), nf, _req_tbl.data(),
+                                                     nullptr, _caps.data(), static_cast<uint8_t*>(_d_cls),
+                                                     _d_mix_index, _mix_index_bytes,
+                                                     static_cast<uint64_t*>(_d_counts), _d_status, _s),
+                   "srpc_frames_unpack_requests_mixed");
+        if (_ohandler)
+            check_srpc(srpc_frames_mixed_ranks(_d_mix_index, static_cast<const uint8_t*>(_d_cls), nf, K,
+                                               static_cast<uint32_t*>(_d_rank), _s),
+                       "srpc_frames_mixed_ranks");
+        check(hipMemcpyAsync(_h_counts, _d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
+        check(hipStreamSynchronize(_s));
+    }
+    int run_ordered_handler(uint64_t nf) {
+        ordered_batch b;
+        b.n = nf;
+        b.d_method = static_cast<const uint8_t*>(_d_cls);
+        b.d_rank = static_cast<const uint32_t*>(_d_rank);
+        b.counts = _h_counts;
+        b.methods = _m.size();
+        b.req_cols = _req_tbl.data();
+        b.resp_cols = _resp_mut_tbl.data();
+        return _ohandler(b, _s);
+    }
+    /// Ordered mode, the reply half: the response plans' frames in arrival
+    /// order straight into _d_out (an unknown frame gets no bytes: the pack's
+    /// "bad call", answered on the CPU in its place, so the flag it would
+    /// raise is not asked for).
+    void ordered_pack(uint64_t nf) {
+        check_srpc(srpc_frames_pack_requests_mixed(_out_plans.data(), static_cast<int>(_m.size()), _resp_tbl.data(),
+                                                   nullptr, _caps.data(), static_cast<const uint8_t*>(_d_cls),
+                                                   _d_mix_index, nf, static_cast<uint8_t*>(_d_out), out_cap(), nullptr,
+                                                   nullptr, _s),
+                   "srpc_frames_pack_requests_mixed (replies)");
+    }
+    /// warm_up for ordered mode: the batch's sequence on one all-zero frame
+    /// (nobody's), every per-method handler on one zero record -- or the
+    /// ordered handler on that batch of one unknown frame -- twice.
+    void warm_up_ordered() {
+        const uint64_t out_cap = this->out_cap();
+        check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
+        check(hipMemsetAsync(_d_cls, 0, _max + 16, _s));
+        check(hipMemsetAsync(_d_mix_index, 0, _mix_index_bytes + 16, _s));
+        check(hipMemsetAsync(_d_rank, 0, 4 * _max + 16, _s));
+        for (auto const& m : _m) {
+            memset_cols(m->req_cols, m->req_bytes);
+            memset_cols(m->resp_cols, m->resp_bytes);
+        }
+        std::memset(_h_in, 0, _cap);
+        std::memset(_h_offs, 0, 4 * _max);
+        for (int pass = 0; pass < 2; ++pass) {
+            check(hipMemcpyAsync(_d_in, _h_in, _cap, hipMemcpyHostToDevice, _s));
+            check(hipMemcpyAsync(_d_offs, _h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
+            ordered_decode(1, std::min<uint64_t>(8, _cap));
+            if (_ohandler) {
+                check_srpc(run_ordered_handler(1), "ordered batch handler (warm-up)");
+            } else {
+                for (auto const& m : _m)
+                    check_srpc(m->handler(m->req_cols.data(), m->resp_cols.data(), 1, _s), "batch handler (warm-up)");
+            }
+            ordered_pack(1);
+            check(hipMemcpyAsync(_h_out, _d_out, out_cap, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(_h_cls, _d_cls, _max, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(_h_status, _d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
+                                 _s));
+            check(hipStreamSynchronize(_s));
+        }
+    }
+
     /// One string-method batch on one well-formed request with empty strings
     /// (its prefix, zeros): every kernel of the var path and the handler load
     /// their code objects here, not on the first batch.
@@ -694,8 +862,9 @@ private:
         _d_var_rec = _d_var_scratch = nullptr;
         _h_out_off = nullptr;
         for (void* p : {_d_in, _d_offs, _d_cls, _d_index, _d_counts, _d_out_off, _d_gather, _d_resp, _d_out,
-                        static_cast<void*>(_d_status), _d_scratch})
+                        static_cast<void*>(_d_status), _d_scratch, _d_mix_index, _d_rank})
             if (p) (void)hipFree(p);
+        _d_mix_index = _d_rank = nullptr;
         for (slot& z : _slots) {
             for (void* p : {static_cast<void*>(z.h_in), static_cast<void*>(z.h_offs), static_cast<void*>(z.h_out),
                             static_cast<void*>(z.h_cls), static_cast<void*>(z.h_status)})
@@ -736,6 +905,7 @@ private:
     /// its bucket counts, a string method's response sizes), the last copy
     /// marked by the slot's event.  process_end answers it.
     pending process_begin(uint64_t nf, uint64_t used, batch_stats& st) {
+        if (_ordered) return process_begin_ordered(nf, used, st);
         auto t0 = clock::now();
         auto mark = [&](const char* what) {
             if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
@@ -879,6 +1049,65 @@ private:
         pd.unknown = unknown;
         pd.total = total;
         pd.any_var = any_var;
+        pd.mixed = mixed;
+        pd.gpu_s = secs(t0);
+        return pd;
+    }
+
+    /// process_begin in ordered mode: H2D, one decode of every method's frames
+    /// into its request columns at their arrival ranks, the counts and one
+    /// sync, the handlers, one reply pack in arrival order into _d_out, D2H.
+    /// The methods' columns and _d_cls are shared by the two staging slots:
+    /// everything that touches them is in stream order.
+    pending process_begin_ordered(uint64_t nf, uint64_t used, batch_stats& st) {
+        auto t0 = clock::now();
+        auto mark = [&](const char* what) {
+            if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
+                                    (unsigned long long)nf, what, 1e3 * secs(t0));
+        };
+        const int K = static_cast<int>(_m.size());
+        check(hipMemcpyAsync(_d_in, _h_in, used, hipMemcpyHostToDevice, _s));
+        check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
+        mark("h2d");
+        ordered_decode(nf, used);
+        mark("decode");
+        st.classify_seconds += secs(t0);
+        const uint64_t unknown = _h_counts[K];
+        uint64_t total = 0;
+        bool mixed = false;
+        for (int k = 0; k < K; ++k) {
+            const uint64_t n = _h_counts[k];
+            total += n * _m[static_cast<size_t>(k)]->fout;
+            mixed |= n && n != nf;
+        }
+        if (_ohandler) {
+            check_srpc(run_ordered_handler(nf), "ordered batch handler");
+        } else {
+            for (int k = 0; k < K; ++k) {
+                method_entry& m = *_m[static_cast<size_t>(k)];
+                if (_h_counts[k])
+                    check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), _h_counts[k], _s), "batch handler");
+            }
+        }
+        mark("handler");
+        if (total) {
+            ordered_pack(nf);
+            check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, _s));
+        }
+        mark("pack");
+        if (unknown) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
+        check(hipMemcpyAsync(_h_status, _d_status, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status),
+                             hipMemcpyDeviceToHost, _s));
+        mark("d2h");
+        pending pd;
+        for (int i = 0; i < _nslots; ++i)
+            if (_slots[i].h_in == _h_in) pd.slot = i;
+        check(hipEventRecord(_slots[pd.slot].done, _s));
+        pd.valid = true;
+        pd.nf = nf;
+        pd.used = used;
+        pd.unknown = unknown;
+        pd.total = total;
         pd.mixed = mixed;
         pd.gpu_s = secs(t0);
         return pd;
@@ -1053,6 +1282,16 @@ private:
     void *_d_in = nullptr, *_d_offs = nullptr, *_d_cls = nullptr, *_d_index = nullptr, *_d_counts = nullptr,
          *_d_out_off = nullptr, *_d_gather = nullptr, *_d_resp = nullptr, *_d_out = nullptr, *_d_scratch = nullptr;
     srpc_unpack_status* _d_status = nullptr;
+    // ordered mode
+    bool _ordered = false;
+    ordered_handler_t _ohandler;
+    void *_d_mix_index = nullptr, *_d_rank = nullptr;
+    uint64_t _mix_index_bytes = 0;
+    std::vector<const srpc_plan*> _out_plans;             // the framed response plans
+    std::vector<uint64_t> _caps;                          // elements of every method's columns (_max)
+    std::vector<void* const*> _req_tbl, _resp_mut_tbl;    // per method: its request / response columns
+    std::vector<std::vector<const void*>> _const_resp;
+    std::vector<const void* const*> _resp_tbl;
     // string methods
     std::vector<const uint64_t*> _var_rec;  // per method: its response index (nullptr: fixed)
     std::vector<size_t> _var_idx;           // the string methods' slots

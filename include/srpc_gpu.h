@@ -419,7 +419,8 @@ int srpc_group_pack_gather(const srpc_plan* const* plans, srpc_comm* const* comm
  * Outputs (device):
  *   d_class[i]             k, or SRPC_FRAME_UNKNOWN (the caller answers it);
  *   d_index[k*nframes + j] the frames of bucket k (j < d_counts[k]; order
- *                          within a bucket is unspecified);
+ *                          within a bucket is unspecified; for fixed-size plans
+ *                          srpc_frames_unpack_requests_mixed keeps arrival order);
  *   d_counts[0..nplans+1]  frames per bucket, then the response stream's total
  *                          bytes, then the number of unknown frames;
  *   d_out_off[0..nframes]  byte offset of frame i's response in the batch's
@@ -701,6 +702,70 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
                                      const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
                                      srpc_unpack_status* d_status, void* stream);
 
+/* ---- batches of request frames of several methods, in arrival order (server
+ * side; added within ABI 8) ------------------------------------------------------
+ * The server's counterpart of the section above: where srpc_frames_classify
+ * fills per-method buckets in no particular order, this call keeps the order
+ * the frames arrived in, within a method and (through d_class and the index)
+ * across methods, and needs no per-method gather.
+ *
+ * srpc_frames_unpack_requests_mixed takes K = nplans fixed-size request plans
+ * with framed prefixes (as the *_mixed calls above) and nframes frames, frame i
+ * being bytes [d_offs[i], end_i) of d_buf, end_i = d_offs[i + 1], or buf_len for
+ * the last frame (the extent convention of srpc_frames_classify).
+ *   d_class[i] (u8, device, out) is k when the frame is exactly one record of
+ *     plan k: its length is F_k and its first prefix_len_k bytes are plan k's
+ *     prefix, the BE32 included; the first matching plan wins.  Every other
+ *     frame is SRPC_FRAME_UNKNOWN: offsets out of order, an end past buf_len, a
+ *     frame under 4 bytes.  This is srpc_frames_classify's rule for fixed-size
+ *     plans; the two calls write the same d_class for every input.
+ *   rank(i) is the number of frames j < i with d_class[j] == d_class[i].  A
+ *     frame of class k has its fields (raw little-endian, as srpc_gpu_unpack
+ *     reads them) written to element h_first[k] + rank(i) of d_cols[k][f];
+ *     d_cols, h_first (NULL = zeros) and h_cap as in the section above.  No
+ *     element is written for an unknown frame.  A frame whose element would be
+ *     at or past h_cap[k] keeps its class and writes nothing: SRPC_STATUS_BOUNDS,
+ *     first_bad_record the smallest such i.
+ *   d_index (opaque, 8-byte aligned, srpc_frames_mixed_index_bytes(nframes, K))
+ *     receives the call index over d_class, the one srpc_frames_mixed_index
+ *     builds: it serves srpc_frames_mixed_ranks and the reply pack below.
+ *   d_counts[k] (u64, device, K + 1 entries) = frames of plan k, d_counts[K] =
+ *     unknown frames.
+ *   - no byte outside [d_buf, d_buf + buf_len) is read;
+ *   - no column element is written but the frames' own;
+ *   - *d_status (may be NULL) is reset by the call;
+ *   - the call is stream-ordered, allocates nothing, waits on nothing; its
+ *     launches (status reset, classify, the index's two, decode) do not depend
+ *     on the data; work is bounded by buf_len + nframes * max_k F_k.  The
+ *     stream is read twice: a frame's rank needs the class of every frame
+ *     before it.
+ *
+ * Refused with nothing launched, in this order: a NULL required pointer
+ * (req_plans, d_cols, h_cap, d_index, d_counts; d_buf, d_offs, d_class when
+ * nframes > 0), nplans outside 1..16, buf_len >= 4 GiB or nframes >= 2^32
+ * (SRPC_E_INVALID; checked before any plan is read); a string plan, a prefix
+ * under 4 bytes or more than SRPC_FRAMES_MIXED_MAX_FIELDS leaves
+ * (SRPC_E_UNSUPPORTED); a misaligned d_buf, column (16), index, d_counts (8) or
+ * d_offs (4) (SRPC_E_ALIGN); an index smaller than
+ * srpc_frames_mixed_index_bytes(nframes, nplans) (SRPC_E_CAPACITY).
+ *
+ * The ordered reply pack is srpc_frames_pack_requests_mixed itself, which by
+ * its contract writes the frames of any fixed-size plans with framed prefixes:
+ * called with the framed RESPONSE plans, the response columns, d_method =
+ * d_class and the d_index this call wrote, it writes the reply stream in
+ * arrival order.  An unknown frame is that call's bad call: zero bytes,
+ * d_offs[i + 1] == d_offs[i], for the caller to answer in its place.  The
+ * SRPC_STATUS_BOUNDS it raises for ids >= K then means only "unknown frames
+ * present" (or a short response column): such callers pass a status of their
+ * own, or NULL. */
+int srpc_frames_unpack_requests_mixed(const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
+                                      uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                      void* const* const* d_cols, const uint64_t* h_first,
+                                      const uint64_t* h_cap, uint8_t* d_class /* nframes, out */,
+                                      void* d_index, uint64_t index_bytes,
+                                      uint64_t* d_counts /* nplans + 1, out */,
+                                      srpc_unpack_status* d_status, void* stream);
+
 /* ---- batches of calls of several methods with string bodies, in call order
  * (client side; added within ABI 8) ----------------------------------------------
  * The calls above with string plans allowed beside the fixed-size ones: the
@@ -850,8 +915,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
  * srpc_frames_unpack_replies / _unpack_replies_var / srpc_frames_mixed_index /
- * _pack_requests_mixed / _unpack_replies_mixed / _pack_requests_mixed_var /
- * _unpack_replies_mixed_var call made on this host
+ * _pack_requests_mixed / _unpack_replies_mixed / _unpack_requests_mixed /
+ * _pack_requests_mixed_var / _unpack_replies_mixed_var call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

@@ -43,22 +43,6 @@ namespace {
 
 constexpr uint32_t kMixScanBlock = 1024;
 
-struct MixArgs {
-    uint8_t* col[kMixFields];        // plan k's columns: [field0[k], field0[k + 1])
-    uint16_t off[kMixFields];        // field offset inside the frame
-    uint8_t size[kMixFields];
-    const uint8_t* prefix[kMixPlans];  // device prefix (8-byte aligned, zero-padded 16 bytes past its end)
-    uint64_t first[kMixPlans];       // element of the chunk's first call of plan k
-    uint32_t room[kMixPlans];        // elements the columns have from `first` on
-    uint32_t F[kMixPlans];           // frame bytes
-    uint16_t prefix_len[kMixPlans];
-    uint16_t tmpl[kMixPlans];        // LDS offset of plan k's prefix template (8-byte aligned)
-    uint16_t field0[kMixPlans + 1];
-    uint32_t nplans;
-    uint32_t T;                      // calls per workgroup tile (divides kMixGranule)
-    uint32_t img;                    // LDS bytes of the image (multiple of 16)
-};
-
 // A workgroup per super-row of kMixSuper granules: granule row = the calls of
 // each class before it inside the super-row, super-row = their total (scanned
 // by k_mixed_scan).
@@ -129,58 +113,6 @@ __global__ __launch_bounds__(kBlock) void k_mixed_ranks(const uint32_t* __restri
     const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
     const uint64_t i = g * kMixGranule + threadIdx.x;
     if (i < ncalls) rank[i] = r.cls < K ? r.rank : kNoRank;
-}
-
-// The lookups a lane makes by its own plan, in LDS: indexed from the kernel
-// arguments they would be vector loads, several of them dependent, per lane.
-struct MixLds {
-    uint8_t* col[kMixFields];
-    uint64_t first[kMixPlans];
-    uint32_t room[kMixPlans];
-    uint32_t F[kMixPlans];
-    uint16_t off[kMixFields];
-    uint16_t prefix_len[kMixPlans];
-    uint16_t tmpl[kMixPlans];
-    uint16_t field0[kMixPlans + 1];
-    uint8_t size[kMixFields];
-};
-
-// Filled by the whole workgroup; complete after the next barrier.
-__device__ __forceinline__ void mix_lds_fill(MixLds& d, const MixArgs& a) {
-    const uint32_t K = a.nplans, nf = a.field0[K];
-    for (uint32_t f = threadIdx.x; f < nf; f += kBlock) {
-        d.col[f] = a.col[f];
-        d.off[f] = a.off[f];
-        d.size[f] = a.size[f];
-    }
-    if (threadIdx.x <= K) d.field0[threadIdx.x] = a.field0[threadIdx.x];
-    if (threadIdx.x < K) {
-        const uint32_t k = threadIdx.x;
-        d.first[k] = a.first[k];
-        d.room[k] = a.room[k];
-        d.F[k] = a.F[k];
-        d.prefix_len[k] = a.prefix_len[k];
-        d.tmpl[k] = a.tmpl[k];
-    }
-}
-
-// The K prefixes into LDS at dst + a.tmpl[k]: a lane per byte of the template
-// region, its plan picked with uniform (scalar) argument reads, so the
-// prefixes cost one global latency whatever K is.
-__device__ __forceinline__ void mix_templates(uint8_t* dst, const MixArgs& a) {
-    const uint32_t K = a.nplans;
-    const uint32_t tb = a.tmpl[K - 1] + a.prefix_len[K - 1];
-    for (uint32_t t = threadIdx.x; t < tb; t += kBlock) {
-        uint32_t off = 0, pl = a.prefix_len[0];
-        const uint8_t* ptr = a.prefix[0];
-        for (uint32_t k = 1; k < K; ++k) {
-            const bool in = a.tmpl[k] <= t;
-            off = in ? a.tmpl[k] : off;
-            pl = in ? a.prefix_len[k] : pl;
-            ptr = in ? a.prefix[k] : ptr;
-        }
-        if (t - off < pl) dst[t] = ptr[t - off];
-    }
 }
 
 // LDS of k_mixed_pack: image[a.img] | templates[tmpl_bytes] | 16 pad, then
@@ -412,62 +344,25 @@ __global__ void k_mixed_reset_status(srpc_unpack_status* st) {
     }
 }
 
-inline uint32_t mix_tile(uint32_t fmax) {
-    uint32_t t = kMixGranule;
-    while (t > 16 && t * fmax > kMixImage) t >>= 1;
-    return t;
-}
-
-// The plans of one side: fixed-size, a prefix of at least min_prefix bytes.
-int mix_plans_ok(const srpc_plan* const* plans, int nplans, uint32_t min_prefix, uint32_t* fmax) {
-    uint32_t fields = 0, m = 0;
-    for (int k = 0; k < nplans; ++k) {
-        const srpc_plan* p = plans[k];
-        if (!p) return SRPC_E_INVALID;
-        if (p->has_string || p->prefix_len < min_prefix) return SRPC_E_UNSUPPORTED;
-        fields += p->nfields;
-        m = std::max<uint32_t>(m, static_cast<uint32_t>(p->stride));
-    }
-    if (fields > static_cast<uint32_t>(kMixFields)) return SRPC_E_UNSUPPORTED;
-    *fmax = m;
-    return SRPC_OK;
-}
-
-// Columns, rooms and layouts into the kernel's arguments.
-int mix_args(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols, const uint64_t* h_first,
-             const uint64_t* h_cap, uint32_t fmax, MixArgs* a, uint32_t* tmpl_bytes) {
-    uint32_t nf = 0, tb = 0;
-    for (int k = 0; k < nplans; ++k) {
-        const srpc_plan* p = plans[k];
-        const uint64_t first = h_first ? h_first[k] : 0;
-        const uint64_t room = h_cap[k] > first ? h_cap[k] - first : 0;
-        if (!d_cols[k]) return SRPC_E_INVALID;
-        a->field0[k] = static_cast<uint16_t>(nf);
-        for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
-            const void* c = d_cols[k][f];
-            if (room && !c) return SRPC_E_INVALID;
-            if (!aligned(c, 16)) return SRPC_E_ALIGN;
-            a->col[nf] = static_cast<uint8_t*>(const_cast<void*>(c));
-            a->off[nf] = static_cast<uint16_t>(p->off[f]);
-            a->size[nf] = static_cast<uint8_t>(p->size[f]);
-        }
-        a->prefix[k] = p->d_prefix;
-        a->first[k] = first;
-        a->room[k] = static_cast<uint32_t>(std::min<uint64_t>(room, 0xffffffffull));
-        a->F[k] = static_cast<uint32_t>(p->stride);
-        a->prefix_len[k] = static_cast<uint16_t>(p->prefix_len);
-        a->tmpl[k] = static_cast<uint16_t>(tb);
-        tb += (p->prefix_len + 7) & ~7u;  // 8-byte aligned: the decode compares eight bytes at a time
-    }
-    a->field0[nplans] = static_cast<uint16_t>(nf);
-    a->nplans = static_cast<uint32_t>(nplans);
-    a->T = mix_tile(fmax);
-    a->img = (a->T * fmax + 16 + 15) & ~15u;
-    *tmpl_bytes = tb;
-    return SRPC_OK;
-}
-
 }  // namespace
+
+int mix_index_launch(const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* table, uint64_t* d_counts,
+                     srpc_unpack_status* d_status, hipStream_t s) {
+    const uint64_t rows = mix_rows(ncalls);
+    if (d_status) hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    if (rows)
+        launch(k_mixed_hist, dim3(static_cast<uint32_t>(mix_super_rows(rows))), dim3(kBlock), 0, s, d_method, ncalls,
+               static_cast<uint32_t>(nplans), table, rows, d_status);
+    launch(k_mixed_scan, dim3(1), dim3(kMixScanBlock), 0, s, table + rows * (nplans + 1), mix_super_rows(rows),
+           static_cast<uint32_t>(nplans + 1), d_counts);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int mix_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s) {
+    hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
 }  // namespace srpc_impl
 
 using namespace srpc_impl;
@@ -487,16 +382,8 @@ int srpc_frames_mixed_index(const uint8_t* d_method, uint64_t ncalls, int nplans
         return SRPC_E_INVALID;
     if (!aligned(d_index, 8) || !aligned(d_counts, 8)) return SRPC_E_ALIGN;
     if (index_bytes < mix_index_bytes(ncalls, nplans)) return SRPC_E_CAPACITY;
-    auto s = static_cast<hipStream_t>(stream);
-    auto* table = static_cast<uint32_t*>(d_index);
-    const uint64_t rows = mix_rows(ncalls);
-    if (d_status) hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
-    if (rows)
-        launch(k_mixed_hist, dim3(static_cast<uint32_t>(mix_super_rows(rows))), dim3(kBlock), 0, s, d_method, ncalls,
-               static_cast<uint32_t>(nplans), table, rows, d_status);
-    launch(k_mixed_scan, dim3(1), dim3(kMixScanBlock), 0, s, table + rows * (nplans + 1), mix_super_rows(rows),
-           static_cast<uint32_t>(nplans + 1), d_counts);
-    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+    return mix_index_launch(d_method, ncalls, nplans, static_cast<uint32_t*>(d_index), d_counts, d_status,
+                            static_cast<hipStream_t>(stream));
 }
 
 int srpc_frames_mixed_ranks(const void* d_index, const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* d_rank,

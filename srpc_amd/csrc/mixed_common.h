@@ -1,6 +1,8 @@
-// mixed_common.h -- internal: what the kernels of mixed.hip (fixed-size plans)
-// and mixed_var.hip (fixed-size and string plans) share: the call index's
-// geometry and mix_ranks, the rank of every call of a granule from that index.
+// mixed_common.h -- internal: what the kernels of mixed.hip (fixed-size plans,
+// client side), mixed_req.hip (fixed-size plans, server side) and mixed_var.hip
+// (fixed-size and string plans) share: the call index's geometry and mix_ranks,
+// the rank of every call of a granule from that index; for the two fixed-size
+// files also the kernels' arguments, their LDS lookups and prefix templates.
 #pragma once
 
 #include <algorithm>
@@ -88,5 +90,138 @@ inline uint64_t mix_index_bytes(uint64_t ncalls, int nplans) {
     const uint64_t rows = mix_rows(ncalls);
     return std::max<uint64_t>(8, ((rows + mix_super_rows(rows)) * (nplans + 1) * 4 + 7) & ~7ull);
 }
+
+// ---- fixed-size plans: what mixed.hip (client side) and mixed_req.hip (server
+// side) share ----
+
+struct MixArgs {
+    uint8_t* col[kMixFields];        // plan k's columns: [field0[k], field0[k + 1])
+    uint16_t off[kMixFields];        // field offset inside the frame
+    uint8_t size[kMixFields];
+    const uint8_t* prefix[kMixPlans];  // device prefix (8-byte aligned, zero-padded 16 bytes past its end)
+    uint64_t first[kMixPlans];       // element of the chunk's first call of plan k
+    uint32_t room[kMixPlans];        // elements the columns have from `first` on
+    uint32_t F[kMixPlans];           // frame bytes
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];        // LDS offset of plan k's prefix template (8-byte aligned)
+    uint16_t field0[kMixPlans + 1];
+    uint32_t nplans;
+    uint32_t T;                      // calls per workgroup tile (divides kMixGranule)
+    uint32_t img;                    // LDS bytes of the image (multiple of 16)
+};
+
+// The lookups a lane makes by its own plan, in LDS: indexed from the kernel
+// arguments they would be vector loads, several of them dependent, per lane.
+struct MixLds {
+    uint8_t* col[kMixFields];
+    uint64_t first[kMixPlans];
+    uint32_t room[kMixPlans];
+    uint32_t F[kMixPlans];
+    uint16_t off[kMixFields];
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];
+    uint16_t field0[kMixPlans + 1];
+    uint8_t size[kMixFields];
+};
+
+// Filled by the whole workgroup; complete after the next barrier.
+__device__ __forceinline__ void mix_lds_fill(MixLds& d, const MixArgs& a) {
+    const uint32_t K = a.nplans, nf = a.field0[K];
+    for (uint32_t f = threadIdx.x; f < nf; f += kBlock) {
+        d.col[f] = a.col[f];
+        d.off[f] = a.off[f];
+        d.size[f] = a.size[f];
+    }
+    if (threadIdx.x <= K) d.field0[threadIdx.x] = a.field0[threadIdx.x];
+    if (threadIdx.x < K) {
+        const uint32_t k = threadIdx.x;
+        d.first[k] = a.first[k];
+        d.room[k] = a.room[k];
+        d.F[k] = a.F[k];
+        d.prefix_len[k] = a.prefix_len[k];
+        d.tmpl[k] = a.tmpl[k];
+    }
+}
+
+// The K prefixes into LDS at dst + a.tmpl[k]: a lane per byte of the template
+// region, its plan picked with uniform (scalar) argument reads, so the
+// prefixes cost one global latency whatever K is.
+__device__ __forceinline__ void mix_templates(uint8_t* dst, const MixArgs& a) {
+    const uint32_t K = a.nplans;
+    const uint32_t tb = a.tmpl[K - 1] + a.prefix_len[K - 1];
+    for (uint32_t t = threadIdx.x; t < tb; t += kBlock) {
+        uint32_t off = 0, pl = a.prefix_len[0];
+        const uint8_t* ptr = a.prefix[0];
+        for (uint32_t k = 1; k < K; ++k) {
+            const bool in = a.tmpl[k] <= t;
+            off = in ? a.tmpl[k] : off;
+            pl = in ? a.prefix_len[k] : pl;
+            ptr = in ? a.prefix[k] : ptr;
+        }
+        if (t - off < pl) dst[t] = ptr[t - off];
+    }
+}
+
+inline uint32_t mix_tile(uint32_t fmax) {
+    uint32_t t = kMixGranule;
+    while (t > 16 && t * fmax > kMixImage) t >>= 1;
+    return t;
+}
+
+// The plans of one side: fixed-size, a prefix of at least min_prefix bytes.
+inline int mix_plans_ok(const srpc_plan* const* plans, int nplans, uint32_t min_prefix, uint32_t* fmax) {
+    uint32_t fields = 0, m = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        if (!p) return SRPC_E_INVALID;
+        if (p->has_string || p->prefix_len < min_prefix) return SRPC_E_UNSUPPORTED;
+        fields += p->nfields;
+        m = std::max<uint32_t>(m, static_cast<uint32_t>(p->stride));
+    }
+    if (fields > static_cast<uint32_t>(kMixFields)) return SRPC_E_UNSUPPORTED;
+    *fmax = m;
+    return SRPC_OK;
+}
+
+// Columns, rooms and layouts into the kernel's arguments.
+inline int mix_args(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
+                    const uint64_t* h_first, const uint64_t* h_cap, uint32_t fmax, MixArgs* a, uint32_t* tmpl_bytes) {
+    uint32_t nf = 0, tb = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const srpc_plan* p = plans[k];
+        const uint64_t first = h_first ? h_first[k] : 0;
+        const uint64_t room = h_cap[k] > first ? h_cap[k] - first : 0;
+        if (!d_cols[k]) return SRPC_E_INVALID;
+        a->field0[k] = static_cast<uint16_t>(nf);
+        for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
+            const void* c = d_cols[k][f];
+            if (room && !c) return SRPC_E_INVALID;
+            if (!aligned(c, 16)) return SRPC_E_ALIGN;
+            a->col[nf] = static_cast<uint8_t*>(const_cast<void*>(c));
+            a->off[nf] = static_cast<uint16_t>(p->off[f]);
+            a->size[nf] = static_cast<uint8_t>(p->size[f]);
+        }
+        a->prefix[k] = p->d_prefix;
+        a->first[k] = first;
+        a->room[k] = static_cast<uint32_t>(std::min<uint64_t>(room, 0xffffffffull));
+        a->F[k] = static_cast<uint32_t>(p->stride);
+        a->prefix_len[k] = static_cast<uint16_t>(p->prefix_len);
+        a->tmpl[k] = static_cast<uint16_t>(tb);
+        tb += (p->prefix_len + 7) & ~7u;  // 8-byte aligned: the decode compares eight bytes at a time
+    }
+    a->field0[nplans] = static_cast<uint16_t>(nf);
+    a->nplans = static_cast<uint32_t>(nplans);
+    a->T = mix_tile(fmax);
+    a->img = (a->T * fmax + 16 + 15) & ~15u;
+    *tmpl_bytes = tb;
+    return SRPC_OK;
+}
+
+// mixed.hip: the index over ncalls method bytes (k_mixed_hist, k_mixed_scan;
+// ids >= nplans land in column nplans), d_status reset and flagged when given;
+// and the status reset alone.
+int mix_index_launch(const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* table, uint64_t* d_counts,
+                     srpc_unpack_status* d_status, hipStream_t s);
+int mix_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
 
 }  // namespace srpc_impl

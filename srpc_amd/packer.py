@@ -532,6 +532,17 @@ class MixedFrames:
                                                            arr, h_first, h_cap, _dptr(codes), _dptr(status),
                                                            _stream(stream))
 
+    def unpack_requests(self, buf, buf_len: int, offs, nframes: int, cols, first, cap, cls, index, index_bytes: int,
+                        counts, status=None, stream=None) -> int:
+        """Server side (srpc_frames_unpack_requests_mixed): classify the frames
+        against these request plans and decode each into its plan's columns at
+        its arrival rank; ``cls``, ``index`` and ``counts`` are outputs."""
+        arr, h_first, h_cap = self._args(cols, first, cap)
+        return _lib.lib().srpc_frames_unpack_requests_mixed(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                            nframes, arr, h_first, h_cap, _dptr(cls), _dptr(index),
+                                                            index_bytes, _dptr(counts), _dptr(status),
+                                                            _stream(stream))
+
 
 class MixedVarFrames:
     """A batch of calls of several methods in call order, string-bodied ones

@@ -565,6 +565,149 @@ def main():
             **alternate(decode, route_decode), route_name=f"{K} x srpc_frames_unpack_replies (indexed)",
             new_name="decode")
 
+    def requests_case(name, methods, n):
+        """Server side: a stream of n request frames over the methods in a
+        uniformly random order, classified and decoded into the methods' columns
+        in arrival order by one srpc_frames_unpack_requests_mixed.  The stream is
+        srpc_frames_pack_requests_mixed's (its first 4096 frames checked against
+        the CPU oracle); the decode is checked against the method vector and the
+        columns the frames were packed from.  Algorithmic bytes: frames + fields
+        + 1 class byte + 4 offset bytes per frame + the index.  Beside it, timed
+        alternately on stream events, the bucket route of batch_server:
+        srpc_frames_classify, then per method srpc_frames_gather and
+        srpc_gpu_unpack (a batch of one method skips the gather, as the server
+        does; the route's host sync for the bucket counts is not in its time)."""
+        if args.only not in name:
+            return
+        from srpc_amd import FrameClassifier, MixedFrames, framed_request_prefix
+        K = len(methods)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(7)
+        d_method = torch.randint(0, K, (n,), dtype=torch.uint8, device=dev, generator=gen)
+        counts = torch.bincount(d_method.to(torch.int64), minlength=K).cpu().numpy()
+        req = [GpuPacker(rq, framed_request_prefix(rq, m)) for m, rq, _ in methods]
+        qcols = []
+        for _, rq, _ in methods:
+            cs = []
+            for k in rq.kinds:
+                c = torch.randint(0, 256, (n * oracle.KIND_SIZE[k],), dtype=torch.uint8, device=dev, generator=gen)
+                cs.append(c & 1 if k == oracle.BOOL else c)
+            qcols.append(cs)
+        mq = MixedFrames(req)
+        cap = [n] * K
+        nb = MixedFrames.index_bytes(n, K)
+        d_index = torch.empty(nb, dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(8 * (K + 1), dtype=torch.uint8, device=dev)
+        st = torch.zeros(16, dtype=torch.uint8, device=dev)
+        assert MixedFrames.index(d_method, n, K, d_index, nb, d_counts, st, stream=s) == 0
+        fmax = max(p.record_bytes for p in req)
+        buf = torch.empty(n * fmax + 16, dtype=torch.uint8, device=dev)
+        offs = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        assert mq.pack(qcols, None, cap, d_method, d_index, n, buf, n * fmax, offs, st, stream=s) == 0
+        torch.cuda.synchronize()
+        total = int(offs[n].item()) & 0xffffffff
+        # the stream's first 4096 frames against the oracle's, interleaved on the host
+        m = min(4096, n)
+        hm = d_method[:m].cpu().numpy()
+        orows = []
+        for p, cs in zip(req, qcols):
+            hc = [c[: m * oracle.KIND_SIZE[k]].cpu().numpy().view(oracle.KIND_DTYPE[k]) for c, k in zip(cs, p.schema.kinds)]
+            orows.append(np.frombuffer(oracle.pack(p.schema.kinds, hc, m, p.prefix), np.uint8).reshape(m, p.record_bytes))
+        seen = [0] * K
+        want = []
+        for i in range(m):
+            want.append(orows[hm[i]][seen[hm[i]]].tobytes())
+            seen[hm[i]] += 1
+        want = b"".join(want)
+        ok = buf[: len(want)].cpu().numpy().tobytes() == want and not bool(st[:4].any())
+
+        back = [[torch.empty_like(c) for c in cs] for cs in qcols]
+        cls = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+
+        def clear():
+            for b in back:
+                for c in b:
+                    c.fill_(0xA5)
+            cls.fill_(0xA5)
+
+        def same():
+            good = torch.equal(cls[:n], d_method)
+            for k, p in enumerate(req):
+                for a, b, kind in zip(qcols[k], back[k], p.schema.kinds):
+                    used = int(counts[k]) * oracle.KIND_SIZE[kind]
+                    good = good and torch.equal(a[:used], b[:used])
+            return good
+
+        def decode():
+            assert mq.unpack_requests(buf, total, offs, n, back, None, cap, cls, d_index, nb, d_counts, st, stream=s) == 0
+
+        clear()
+        decode()
+        torch.cuda.synchronize()
+        ok = ok and same() and not bool(st[:4].any())
+        ok = ok and np.array_equal(d_counts.cpu().numpy().view(np.uint64), np.append(counts, 0).astype(np.uint64))
+
+        # the bucket route
+        fc = FrameClassifier([(p, 23) for p in req])
+        r_cls = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        r_idx = torch.empty(4 * K * n + 16, dtype=torch.uint8, device=dev)
+        r_counts = torch.empty(8 * (K + 2), dtype=torch.uint8, device=dev)
+        r_out_off = torch.empty(8 * (n + 1), dtype=torch.uint8, device=dev)
+        sb = fc.scratch_bytes(n)
+        scratch = torch.empty(sb, dtype=torch.uint8, device=dev)
+        gathered = torch.empty(n * fmax + 16, dtype=torch.uint8, device=dev)
+
+        def route():
+            fc.classify(buf, total, offs, n, r_cls, r_idx, r_counts, r_out_off, scratch, sb, stream=s)
+            for k, p in enumerate(req):
+                c = int(counts[k])
+                if not c:
+                    continue
+                src = buf
+                if c != n:
+                    FrameClassifier.gather(buf, offs, r_idx.data_ptr() + 4 * k * n, c, p.record_bytes, gathered, stream=s)
+                    src = gathered
+                p.unpack(src, c * p.record_bytes, c, back[k], stream=s)
+
+        clear()
+        route()
+        torch.cuda.synchronize()
+        route_ok = torch.equal(r_cls[:n], d_method)
+        for k, p in enumerate(req):  # the buckets' order is unspecified: the columns as multisets
+            for a, b, kind in zip(qcols[k], back[k], p.schema.kinds):
+                used = int(counts[k]) * oracle.KIND_SIZE[kind]
+                dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[oracle.KIND_SIZE[kind]]
+                route_ok = route_ok and torch.equal(a[:used].view(dt).sort().values, b[:used].view(dt).sort().values)
+
+        def ev(fn):
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / 1e3
+
+        for _ in range(3):
+            route()
+            decode()
+        t_new, t_route = [], []
+        for _ in range(args.reps):
+            t_new.append(ev(decode))
+            t_route.append(ev(route))
+        clear()
+        t = timeit(decode)
+        torch.cuda.synchronize()
+        ok = ok and same()
+        fields = sum(int(c) * p.schema.body_bytes for c, p in zip(counts, req))
+        alg = total + fields + 5 * n + nb
+        rows.append({"case": f"{name}_decode", "mixed": True, "calls": n, "plans": K, "alg_bytes": alg,
+                     "us": round(t * 1e6, 2), "GBps": round(alg / t / 1e9, 1), "frac": round(alg / t / 8e12, 4),
+                     "parity_ok": bool(ok), "route_parity_ok": bool(route_ok), "frame_bytes": round(total / n, 1),
+                     "index_bytes": nb, "ab_new": spread(t_new), "ab_route": spread(t_route),
+                     "new_name": "unpack_requests_mixed",
+                     "route_name": f"classify + {K if K > 1 else 0} x gather + {K} x srpc_gpu_unpack"})
+
     def aos_case(name, sch, n, vptr=True):
         """Records as C-aligned structs behind an 8-byte vtable slot (a C++
         std::vector<T> of srpc messages copied to the device; vptr=False: a
@@ -736,6 +879,9 @@ def main():
     mixed_case(f"mixed_k1_square_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER)], NM)
     mixed_case(f"mixed_k4_calculator_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER), (svc + "add", two, NUMBER),
                                                (svc + "subtract", two, NUMBER), (svc + "multiply", two, NUMBER)], NM)
+    requests_case(f"requests_k1_square_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER)], NM)
+    requests_case(f"requests_k4_calculator_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER), (svc + "add", two, NUMBER),
+                                                     (svc + "subtract", two, NUMBER), (svc + "multiply", two, NUMBER)], NM)
     aos_case("quad_aos_16M", QUAD, N)
     aos_case("quad_aos_plain_16M", QUAD, N, vptr=False)
     aos_case("all_kinds_aos_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),

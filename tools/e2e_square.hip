@@ -11,7 +11,9 @@
 //           compared with the reference digest;
 //   server: --mode gpu: srpc::gpu::batch_server (include/srpc/gpu_server.hpp)
 //                       with square (and with --gpu-methods all: add, subtract,
-//                       multiply) on the GPU, the rest on the CPU server;
+//                       multiply) on the GPU, the rest on the CPU server; with
+//                       --gpu-methods all,ordered in ordered mode (set_ordered:
+//                       one request decode and one reply pack per batch);
 //           --mode cpu: the scalar srpc::server (include/srpc/server.hpp),
 //                       the reference's per-request dispatch path.
 // Traffic: num = splitmix64(0x5EED) % 46341 for square;
@@ -284,6 +286,7 @@ int main(int argc, char** argv) {
             gsrv->register_method<TwoNumbers, Number>("Calculator_servicer::subtract", binop_batch<SUB>);
             gsrv->register_method<TwoNumbers, Number>("Calculator_servicer::multiply", binop_batch<MUL>);
         }
+        if (gpu_methods.find("ordered") != std::string::npos) gsrv->set_ordered(true);
         buffer_bytes = gsrv->buffer_bytes();
     }
 

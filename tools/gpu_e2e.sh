@@ -2,7 +2,8 @@
 # Calculator e2e over loopback (BASELINE configs[4]) on the GPU box: the pure
 # square stream at three batch sizes, the scalar CPU server, and mixed traffic
 # (a poisoned frame at index 0, 1 % and 10 % divide requests the GPU server
-# does not have, four methods on the GPU).  Usage: tools/gpu_e2e.sh [log]
+# does not have, four methods on the GPU by the bucket route and in ordered
+# mode).  Usage: tools/gpu_e2e.sh [log]
 set -o pipefail
 mkdir -p gpurun_out
 log=${1:-gpurun_out/e2e.log}
@@ -18,3 +19,5 @@ timeout -k 10 120 $E --mode gpu --n $N --batch 262144 --port 18403 --foreign 0.0
 timeout -k 10 120 $E --mode gpu --n $N --batch 262144 --port 18404 --foreign 0.10 >> "$log" 2>&1 || exit 6
 timeout -k 10 120 $E --mode gpu --n $N --batch 262144 --port 18405 --mix 0.5 --gpu-methods all >> "$log" 2>&1 || exit 7
 timeout -k 10 120 $E --mode cpu --n $N --port 18406 --mix 0.5 >> "$log" 2>&1 || exit 8
+# the same mix in ordered mode (one request decode, one reply pack per batch), next to the bucket route's row
+timeout -k 10 120 $E --mode gpu --n $N --batch 262144 --port 18407 --mix 0.5 --gpu-methods all,ordered >> "$log" 2>&1 || exit 9
