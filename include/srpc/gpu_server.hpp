@@ -43,6 +43,18 @@
 //   (the replies in arrival order, nothing for an unknown frame) -> D2H.
 //
 // No gather, no scatter and no second response buffer, whatever the mix.
+//
+// Ordered mode over string-bodied methods too (set_ordered_var /
+// set_ordered_var_handler) is the same route through the calls that take both
+// plan kinds:
+//
+//   H2D -> srpc_frames_unpack_requests_mixed_var (fixed leaves, chars and
+//   offsets of every method at their arrival ranks) -> the handlers (a string
+//   method's var_handler_t on its n = counts[k] requests), or the one ordered
+//   handler -> the string responses' sizes checked on the host against their
+//   columns (a method that overflows is answered on the CPU for this batch) ->
+//   srpc_frames_pack_requests_mixed_var over the response plans with d_method =
+//   d_class -> the total (and, with unknown frames, the offsets) -> D2H.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -173,6 +185,27 @@ struct ordered_batch {
     void* const* const* resp_cols = nullptr;
 };
 
+/// A batch in ordered mode with string-bodied methods
+/// (batch_server::set_ordered_var_handler): ordered_batch's fields, and per
+/// method the offsets arrays of its string leaves -- req_str_offs[k][f] /
+/// resp_str_offs[k][f], one entry per flattened field, nullptr for a fixed leaf
+/// -- as var_batch has them: request element r's string is bytes [offs[r],
+/// offs[r + 1]) of req_cols[k][f], offs[0] == 0.  The handler writes every
+/// response column and, for every response string leaf of method k, its
+/// counts[k] + 1 offsets (at most resp_cap[k][f] chars).
+struct ordered_var_batch {
+    uint64_t n = 0;
+    const uint8_t* d_method = nullptr;   // device, n
+    const uint32_t* d_rank = nullptr;    // device, n
+    const uint64_t* counts = nullptr;    // host, methods + 1: frames per method, then the unknown ones
+    size_t methods = 0;
+    void* const* const* req_cols = nullptr;   // host array per method of device columns
+    void* const* const* resp_cols = nullptr;
+    const uint64_t* const* const* req_str_offs = nullptr;  // host array per method of per-leaf device pointers
+    uint64_t* const* const* resp_str_offs = nullptr;
+    const uint64_t* const* resp_cap = nullptr;             // per method: the bytes of each response column
+};
+
 struct batch_stats {
     uint64_t requests = 0;           // frames answered
     uint64_t gpu_batches = 0;        // batches that went through the GPU path
@@ -241,6 +274,8 @@ public:
         m->out = std::make_unique<raw_plan>(flat_kinds<Resp>(), framed_response_prefix<Resp>(RPC_SUCCESS), _dev);
         m->fin = m->in->record_bytes();
         m->fout = m->out->record_bytes();
+        m->in_kinds = flat_kinds<Req>();
+        m->out_kinds = flat_kinds<Resp>();
         Req rq{};
         for_each_leaf<Req>(rq, [&](const auto& v) {
             m->req_bytes.push_back(_max * sizeof(v) + 16);
@@ -279,6 +314,13 @@ public:
         m->fin = std::max<uint64_t>(lim.max_request_bytes, 4 + m->min_in);
         m->fout = 0;  // response frames vary
         m->lim = lim;
+        // the ordered route's plans (ensure): a side without strings is a fixed-size plan behind the framed prefix
+        m->in_kinds = flat_kinds<Req>();
+        m->out_kinds = flat_kinds<Resp>();
+        m->framed_in = be32(static_cast<uint32_t>(m->min_in));
+        m->framed_in.insert(m->framed_in.end(), rq.begin(), rq.end());
+        m->framed_out = be32(static_cast<uint32_t>(m->min_out));
+        m->framed_out.insert(m->framed_out.end(), rs.begin(), rs.end());
         Req rq0{};
         for_each_leaf<Req>(rq0, [&](const auto& v) {
             using F = std::remove_cvref_t<decltype(v)>;
@@ -311,6 +353,7 @@ public:
     void set_ordered(bool on) {
         if (on == _ordered) return;
         _ordered = on;
+        if (!on) _ordered_var = false;
         release();
     }
     bool ordered() const { return _ordered; }
@@ -329,6 +372,39 @@ public:
         set_ordered(true);
     }
 
+    /// handler(batch, stream) over a whole batch of every method, string-bodied
+    /// ones included, in arrival order (ordered_var_batch).
+    using ordered_var_handler_t = std::function<int(ordered_var_batch const&, hipStream_t)>;
+
+    /// Ordered mode that admits register_var_method methods (off by default;
+    /// implies ordered mode).  Fixed methods keep their handler_t; a string
+    /// method's var_handler_t gets a var_batch with n = counts[k] whose request r
+    /// is the method's r-th frame in arrival order (its request offsets start at
+    /// 0).  A batch goes through one srpc_frames_unpack_requests_mixed_var and
+    /// one srpc_frames_pack_requests_mixed_var over the response plans.  A string
+    /// method whose responses do not fit their columns (var_limits) is answered
+    /// by the CPU server for that batch, its frames in their places
+    /// (batch_stats::overflow_batches); the other methods' elements do not move.
+    /// One batch is in flight at a time: the route syncs for the reply stream's
+    /// size.  set_ordered / set_ordered_handler keep refusing string methods.
+    void set_ordered_var(bool on) {
+        if (on == _ordered_var && on == _ordered) return;
+        _ordered_var = on;
+        _ordered = on;
+        release();
+    }
+    bool ordered_var() const { return _ordered_var; }
+    /// One handler for every method, string-bodied ones included, run once per
+    /// batch instead of the per-method handlers; implies set_ordered_var(true).
+    /// Timing and warm-up are set_ordered_handler's: batches reach it in
+    /// connection order on the server's stream, frames the GPU path does not
+    /// take are answered by the CPU server after the batch's handler ran, and at
+    /// serve start it is run on a batch of one unknown frame.
+    void set_ordered_var_handler(ordered_var_handler_t handler) {
+        _ovhandler = std::move(handler);
+        set_ordered_var(true);
+    }
+
     uint64_t request_frame_bytes(size_t k = 0) const { return _m.at(k)->fin; }
     uint64_t response_frame_bytes(size_t k = 0) const { return _m.at(k)->fout; }
     /// Bytes of the receive buffer: max_batch frames of the longest method.
@@ -345,7 +421,7 @@ public:
     /// waiting.  Answers leave in request order.
     batch_stats serve_connection(int fd) {
         if (_m.empty()) throw plan_error("batch_server::serve_connection (no methods)", SRPC_E_INVALID);
-        if (_ordered && any_var_method())
+        if (_ordered && !_ordered_var && any_var_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a string-bodied method)",
                              SRPC_E_UNSUPPORTED);
         check(hipSetDevice(_dev));
@@ -464,6 +540,16 @@ private:
         uint64_t resp_wire_cap = 0;
         uint64_t* resp_rec = nullptr;
         uint64_t* h_ends = nullptr;                 // pinned: per response field, offs[0] and offs[n]
+        // ordered mode with string methods (set_ordered_var): the plan kinds the *_mixed_var calls
+        // take, per side -- `in` / `out` where they already are of that kind, else a fixed-size plan
+        // behind the framed prefix -- and the per-leaf tables those calls and the handlers read
+        std::vector<int32_t> in_kinds, out_kinds;
+        std::vector<uint8_t> framed_in, framed_out;
+        std::unique_ptr<raw_plan> ord_in, ord_out;
+        std::vector<const uint64_t*> c_req_offs, c_resp_offs;
+        std::vector<uint64_t> req_scap;             // bytes of every request column
+        bool in_str() const { return std::find(req_string.begin(), req_string.end(), true) != req_string.end(); }
+        bool out_str() const { return std::find(resp_string.begin(), resp_string.end(), true) != resp_string.end(); }
     };
     void memset_cols(std::vector<void*> const& cols, std::vector<uint64_t> const& bytes) {
         for (size_t f = 0; f < cols.size(); ++f) check(hipMemsetAsync(cols[f], 0, bytes[f], _s));
@@ -533,9 +619,10 @@ private:
             m.resp_cols.push_back(alloc(b));
             m.resp_offs.push_back(m.resp_string[f] ? static_cast<uint64_t*>(alloc(8 * (_max + 1) + 16)) : nullptr);
         }
+        check(hipHostMalloc(reinterpret_cast<void**>(&m.h_ends), 16 * m.resp_string.size() + 16, hipHostMallocDefault));
+        if (_ordered_var) return;  // the replies are packed straight into the reply stream
         m.resp_wire = static_cast<uint8_t*>(alloc(m.resp_wire_cap));
         m.resp_rec = static_cast<uint64_t*>(alloc(8 * (_max + 1) + 16));
-        check(hipHostMalloc(reinterpret_cast<void**>(&m.h_ends), 16 * m.resp_string.size() + 16, hipHostMallocDefault));
         uint64_t a = 0, b = 0;
         check_srpc(srpc_plan_var_scratch_bytes(m.in->get(), _max, _cap, &a), "srpc_plan_var_scratch_bytes");
         check_srpc(srpc_plan_var_scratch_bytes(m.out->get(), _max, m.resp_wire_cap, &b), "srpc_plan_var_scratch_bytes");
@@ -578,7 +665,7 @@ private:
         // batches need the host between their kernels (SRPC_SERVER_SLOTS=1:
         // one batch at a time, the A/B baseline)
         const char* slots_env = std::getenv("SRPC_SERVER_SLOTS");
-        _nslots = any_var_method() || (slots_env && slots_env[0] == '1') ? 1 : 2;
+        _nslots = any_var_method() || _ordered_var || (slots_env && slots_env[0] == '1') ? 1 : 2;
         for (int i = 0; i < _nslots; ++i) {
             slot& z = _slots[i];
             check(hipHostMalloc(reinterpret_cast<void**>(&z.h_in), _cap + 16, hipHostMallocDefault));
@@ -606,6 +693,7 @@ private:
                        "srpc_frames_mixed_index_bytes");
             check(hipMalloc(&_d_mix_index, _mix_index_bytes + 16));
             check(hipMalloc(&_d_rank, 4 * _max + 16));
+            if (_ordered_var) ensure_ordered_var(out_cap);
         } else {
             check(hipMalloc(&_d_index, 4 * K * _max + 16));
             check(hipMalloc(&_d_out_off, 8 * (_max + 1) + 16));
@@ -646,6 +734,7 @@ private:
     /// buffer, at serve start: first uses cost milliseconds that otherwise land
     /// on the connection's first batch (profiles/r02_e2e_warmup.log).
     void warm_up() {
+        if (_ordered_var) return warm_up_ordered_var();
         if (_ordered) return warm_up_ordered();
         const int K = static_cast<int>(_m.size());
         const uint64_t out_cap = this->out_cap();
@@ -790,6 +879,158 @@ private:
         }
     }
 
+    // ---- ordered mode with string-bodied methods (set_ordered_var) ----
+
+    /// The route's plans, tables and buffers (ensure; the methods' columns are
+    /// allocated).  Per method and per side: a side with strings keeps the
+    /// unframed-prefix string plan register_var_method built, a side without
+    /// gets a fixed-size plan behind the framed prefix (register_method's own,
+    /// or one built here for a string method's fixed side).
+    void ensure_ordered_var(uint64_t out_cap) {
+        const int K = static_cast<int>(_m.size());
+        if (out_cap > 0xffffffffull) throw plan_error("batch_server: reply buffer over 4 GiB", SRPC_E_UNSUPPORTED);
+        _ov_in_plans.clear(), _ov_out_plans.clear();
+        _ov_req_offs.clear(), _ov_c_req_offs.clear(), _ov_resp_offs.clear(), _ov_c_resp_offs.clear();
+        _ov_req_scap.clear(), _ov_resp_cap.clear();
+        _ov_slots = 0;
+        for (auto& m : _m) {
+            if (m->var && !m->in_str()) m->ord_in = std::make_unique<raw_plan>(m->in_kinds, m->framed_in, _dev);
+            if (m->var && !m->out_str()) m->ord_out = std::make_unique<raw_plan>(m->out_kinds, m->framed_out, _dev);
+            _ov_in_plans.push_back(m->ord_in ? m->ord_in->get() : m->in->get());
+            _ov_out_plans.push_back(m->ord_out ? m->ord_out->get() : m->out->get());
+            if (!m->var) {  // no offsets arrays: a nullptr per leaf
+                m->req_offs.assign(m->req_cols.size(), nullptr);
+                m->resp_offs.assign(m->resp_cols.size(), nullptr);
+            }
+            m->c_req_offs.assign(m->req_offs.begin(), m->req_offs.end());
+            m->c_resp_offs.assign(m->resp_offs.begin(), m->resp_offs.end());
+            m->req_scap.clear();
+            for (uint64_t b : m->req_bytes) m->req_scap.push_back(b - 16);  // a string column: the receive buffer's bytes
+            for (uint64_t* o : m->req_offs) _ov_slots += o ? 1 : 0;
+        }
+        for (auto const& m : _m) {
+            _ov_req_offs.push_back(m->req_offs.data());
+            _ov_c_req_offs.push_back(m->c_req_offs.data());
+            _ov_resp_offs.push_back(m->resp_offs.data());
+            _ov_c_resp_offs.push_back(m->c_resp_offs.data());
+            _ov_req_scap.push_back(m->req_scap.data());
+            _ov_resp_cap.push_back(m->resp_bytes.data());
+        }
+        uint64_t a = 0, b = 0;
+        check_srpc(srpc_frames_mixed_var_scratch_bytes(_ov_in_plans.data(), K, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
+        check_srpc(srpc_frames_mixed_var_scratch_bytes(_ov_out_plans.data(), K, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
+        _ov_scratch_bytes = std::max(a, b);
+        _d_ov_scratch = alloc(_ov_scratch_bytes + 16);
+        _d_ov_ends = alloc(8 * (_ov_slots + 1) + 16);
+        _d_ov_total = alloc(16);
+        _d_ov_offs = alloc(4 * (_max + 1) + 16);
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_ends), 8 * (_ov_slots + 1) + 16, hipHostMallocDefault));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_total), 16, hipHostMallocDefault));
+        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_offs), 4 * (_max + 1) + 16, hipHostMallocDefault));
+    }
+
+    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed_var over
+    /// the nf frames in _d_in[0, used) into the methods' request columns, chars
+    /// and offsets (and the ranks, when the ordered handler is set), then the
+    /// counts and the string slots' ends on the host after one sync.
+    void ordered_var_decode(uint64_t nf, uint64_t used) {
+        const int K = static_cast<int>(_m.size());
+        check(hipMemsetAsync(_d_status, 0, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status), _s));
+        check_srpc(srpc_frames_unpack_requests_mixed_var(
+                       _ov_in_plans.data(), K, static_cast<const uint8_t*>(_d_in), used,
+                       static_cast<const uint32_t*>(_d_offs), nf, _req_tbl.data(), _ov_req_offs.data(), _ov_req_scap.data(),
+                       nullptr, _caps.data(), static_cast<uint8_t*>(_d_cls), _d_mix_index, _mix_index_bytes,
+                       static_cast<uint64_t*>(_d_counts), static_cast<uint64_t*>(_d_ov_ends), _d_status, _d_ov_scratch,
+                       _ov_scratch_bytes, _s),
+                   "srpc_frames_unpack_requests_mixed_var");
+        if (_ovhandler)
+            check_srpc(srpc_frames_mixed_ranks(_d_mix_index, static_cast<const uint8_t*>(_d_cls), nf, K,
+                                               static_cast<uint32_t*>(_d_rank), _s),
+                       "srpc_frames_mixed_ranks");
+        check(hipMemcpyAsync(_h_counts, _d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
+        if (_ov_slots) check(hipMemcpyAsync(_h_ov_ends, _d_ov_ends, 8 * _ov_slots, hipMemcpyDeviceToHost, _s));
+        check(hipStreamSynchronize(_s));
+    }
+    int run_ordered_var_handler(uint64_t nf) {
+        ordered_var_batch b;
+        b.n = nf;
+        b.d_method = static_cast<const uint8_t*>(_d_cls);
+        b.d_rank = static_cast<const uint32_t*>(_d_rank);
+        b.counts = _h_counts;
+        b.methods = _m.size();
+        b.req_cols = _req_tbl.data();
+        b.resp_cols = _resp_mut_tbl.data();
+        b.req_str_offs = _ov_c_req_offs.data();
+        b.resp_str_offs = _ov_resp_offs.data();
+        b.resp_cap = _ov_resp_cap.data();
+        return _ovhandler(b, _s);
+    }
+    /// Method k's handler over its n requests in arrival order.
+    int run_ordered_var_method(method_entry& m, uint64_t n) {
+        if (!m.var) return m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s);
+        var_batch b;
+        b.n = n;
+        b.req_cols = m.req_cols.data();
+        b.req_str_offs = m.c_req_offs.data();
+        b.resp_cols = m.resp_cols.data();
+        b.resp_str_offs = m.resp_offs.data();
+        b.resp_cap = m.resp_bytes.data();
+        return m.vhandler(b, _s);
+    }
+    /// The reply half: the response plans' frames in arrival order straight
+    /// into _d_out, nothing for an unknown frame; the stream's size, and with
+    /// unknown frames every answer's offset, to the host.  No sync here.
+    void ordered_var_pack(uint64_t nf, bool unknown) {
+        const int K = static_cast<int>(_m.size());
+        // an unknown frame is the pack's "bad call" and would raise its flag: asked for only without one
+        check_srpc(srpc_frames_pack_requests_mixed_var(
+                       _ov_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(), nullptr, _caps.data(),
+                       static_cast<const uint8_t*>(_d_cls), _d_mix_index, nf, static_cast<uint8_t*>(_d_out), out_cap(),
+                       static_cast<uint32_t*>(_d_ov_offs), static_cast<uint64_t*>(_d_ov_total),
+                       unknown ? nullptr : _d_status + K, _d_ov_scratch, _ov_scratch_bytes, _s),
+                   "srpc_frames_pack_requests_mixed_var (replies)");
+        check(hipMemcpyAsync(_h_ov_total, _d_ov_total, 8, hipMemcpyDeviceToHost, _s));
+        if (unknown) check(hipMemcpyAsync(_h_ov_offs, _d_ov_offs, 4 * (nf + 1), hipMemcpyDeviceToHost, _s));
+    }
+    /// warm_up for this route: the batch's sequence on one all-zero frame
+    /// (nobody's), every per-method handler on one zero record (empty strings)
+    /// -- or the ordered handler on that batch of one unknown frame -- twice.
+    void warm_up_ordered_var() {
+        const uint64_t out_cap = this->out_cap();
+        check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
+        check(hipMemsetAsync(_d_cls, 0, _max + 16, _s));
+        check(hipMemsetAsync(_d_mix_index, 0, _mix_index_bytes + 16, _s));
+        check(hipMemsetAsync(_d_rank, 0, 4 * _max + 16, _s));
+        check(hipMemsetAsync(_d_ov_scratch, 0, _ov_scratch_bytes, _s));
+        check(hipMemsetAsync(_d_ov_offs, 0, 4 * (_max + 1) + 16, _s));
+        for (auto const& m : _m) {
+            memset_cols(m->req_cols, m->req_bytes);
+            memset_cols(m->resp_cols, m->resp_bytes);
+            for (uint64_t* p : m->req_offs)
+                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
+            for (uint64_t* p : m->resp_offs)
+                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
+        }
+        std::memset(_h_in, 0, _cap);
+        std::memset(_h_offs, 0, 4 * _max);
+        for (int pass = 0; pass < 2; ++pass) {
+            check(hipMemcpyAsync(_d_in, _h_in, _cap, hipMemcpyHostToDevice, _s));
+            check(hipMemcpyAsync(_d_offs, _h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
+            ordered_var_decode(1, std::min<uint64_t>(8, _cap));
+            if (_ovhandler) {
+                check_srpc(run_ordered_var_handler(1), "ordered batch handler (warm-up)");
+            } else {
+                for (auto const& m : _m) check_srpc(run_ordered_var_method(*m, 1), "batch handler (warm-up)");
+            }
+            ordered_var_pack(1, true);
+            check(hipMemcpyAsync(_h_out, _d_out, out_cap, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(_h_cls, _d_cls, _max, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(_h_status, _d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
+                                 _s));
+            check(hipStreamSynchronize(_s));
+        }
+    }
+
     /// One string-method batch on one well-formed request with empty strings
     /// (its prefix, zeros): every kernel of the var path and the handler load
     /// their code objects here, not on the first batch.
@@ -865,6 +1106,14 @@ private:
                         static_cast<void*>(_d_status), _d_scratch, _d_mix_index, _d_rank})
             if (p) (void)hipFree(p);
         _d_mix_index = _d_rank = nullptr;
+        for (void* p : {_d_ov_ends, _d_ov_total, _d_ov_offs, _d_ov_scratch})
+            if (p) (void)hipFree(p);
+        for (void* p : {static_cast<void*>(_h_ov_ends), static_cast<void*>(_h_ov_total), static_cast<void*>(_h_ov_offs)})
+            if (p) (void)hipHostFree(p);
+        _d_ov_ends = _d_ov_total = _d_ov_offs = _d_ov_scratch = nullptr;
+        _h_ov_ends = _h_ov_total = nullptr;
+        _h_ov_offs = nullptr;
+        for (auto& m : _m) m->ord_in.reset(), m->ord_out.reset();
         for (slot& z : _slots) {
             for (void* p : {static_cast<void*>(z.h_in), static_cast<void*>(z.h_offs), static_cast<void*>(z.h_out),
                             static_cast<void*>(z.h_cls), static_cast<void*>(z.h_status)})
@@ -889,6 +1138,7 @@ private:
         int slot = 0;
         uint64_t nf = 0, used = 0, unknown = 0, total = 0;
         bool any_var = false, mixed = false;
+        bool ov = false;   // the ordered route over string methods: the answers' offsets are _h_ov_offs
         double gpu_s = 0;  // host time spent on the batch's GPU work (enqueue, syncs, the final wait)
     };
     void use_slot(int i) {
@@ -905,6 +1155,7 @@ private:
     /// its bucket counts, a string method's response sizes), the last copy
     /// marked by the slot's event.  process_end answers it.
     pending process_begin(uint64_t nf, uint64_t used, batch_stats& st) {
+        if (_ordered_var) return process_begin_ordered_var(nf, used, st);
         if (_ordered) return process_begin_ordered(nf, used, st);
         auto t0 = clock::now();
         auto mark = [&](const char* what) {
@@ -1113,6 +1364,106 @@ private:
         return pd;
     }
 
+    /// process_begin on this route: H2D, one decode, the counts and one sync,
+    /// the handlers, the string responses' sizes checked against their columns
+    /// (a second sync, only when a string response exists), one reply pack in
+    /// arrival order, the total and a sync, D2H.
+    pending process_begin_ordered_var(uint64_t nf, uint64_t used, batch_stats& st) {
+        auto t0 = clock::now();
+        auto mark = [&](const char* what) {
+            if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
+                                    (unsigned long long)nf, what, 1e3 * secs(t0));
+        };
+        const int K = static_cast<int>(_m.size());
+        check(hipMemcpyAsync(_d_in, _h_in, used, hipMemcpyHostToDevice, _s));
+        check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
+        mark("h2d");
+        ordered_var_decode(nf, used);
+        mark("decode");
+        st.classify_seconds += secs(t0);
+        uint64_t unknown = _h_counts[K];
+        bool mixed = false, any_var = false, sized = false;
+        for (int k = 0; k < K; ++k) {
+            const uint64_t n = _h_counts[k];
+            mixed |= n && n != nf;
+            any_var |= n && _m[static_cast<size_t>(k)]->var;
+            sized |= n && _m[static_cast<size_t>(k)]->var && _m[static_cast<size_t>(k)]->out_str();
+        }
+        if (_ovhandler) {
+            check_srpc(run_ordered_var_handler(nf), "ordered batch handler");
+        } else {
+            for (int k = 0; k < K; ++k)
+                if (_h_counts[k]) check_srpc(run_ordered_var_method(*_m[static_cast<size_t>(k)], _h_counts[k]), "batch handler");
+        }
+        mark("handler");
+        bool h_cls_valid = false;
+        if (sized) {
+            // the responses' sizes are checked on the host BEFORE anything reads the response chars: a
+            // method whose answers do not fit its columns is answered on the CPU server instead, in place
+            for (int k = 0; k < K; ++k) {
+                method_entry& m = *_m[static_cast<size_t>(k)];
+                const uint64_t n = _h_counts[k];
+                if (!m.var || !n) continue;
+                for (size_t f = 0; f < m.resp_offs.size(); ++f) {
+                    if (!m.resp_offs[f]) continue;
+                    check(hipMemcpyAsync(m.h_ends + 2 * f, m.resp_offs[f], 8, hipMemcpyDeviceToHost, _s));
+                    check(hipMemcpyAsync(m.h_ends + 2 * f + 1, m.resp_offs[f] + n, 8, hipMemcpyDeviceToHost, _s));
+                }
+            }
+            check(hipStreamSynchronize(_s));
+            bool demoted[SRPC_FRAMES_MAX_PLANS] = {};
+            bool any_demoted = false;
+            for (int k = 0; k < K; ++k) {
+                method_entry& m = *_m[static_cast<size_t>(k)];
+                if (!m.var || !_h_counts[k] || var_responses_fit(m)) continue;
+                demoted[k] = any_demoted = true;
+                st.overflow_batches += 1;
+            }
+            if (any_demoted) {
+                // its frames become unknown; the ranks are per method, so the other methods' elements stay
+                check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
+                check(hipStreamSynchronize(_s));
+                for (uint64_t i = 0; i < nf; ++i)
+                    if (_h_cls[i] != SRPC_FRAME_UNKNOWN && demoted[_h_cls[i]]) _h_cls[i] = SRPC_FRAME_UNKNOWN;
+                for (int k = 0; k < K; ++k)
+                    if (demoted[k]) {
+                        unknown += _h_counts[k];
+                        _h_counts[k] = 0;
+                    }
+                check(hipMemcpyAsync(_d_cls, _h_cls, nf, hipMemcpyHostToDevice, _s));
+                check_srpc(srpc_frames_mixed_index(static_cast<const uint8_t*>(_d_cls), nf, K, _d_mix_index,
+                                                   _mix_index_bytes, static_cast<uint64_t*>(_d_counts), nullptr, _s),
+                           "srpc_frames_mixed_index");
+                h_cls_valid = true;
+            }
+            mark("sizes");
+        }
+        ordered_var_pack(nf, unknown != 0);
+        check(hipStreamSynchronize(_s));  // the reply stream's size
+        const uint64_t total = _h_ov_total[0];
+        if (total > out_cap()) throw plan_error("batch_server: the replies overran the reply buffer", SRPC_E_INVALID);
+        mark("pack");
+        if (total) check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, _s));
+        if (unknown && !h_cls_valid) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
+        check(hipMemcpyAsync(_h_status, _d_status, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status),
+                             hipMemcpyDeviceToHost, _s));
+        mark("d2h");
+        pending pd;
+        for (int i = 0; i < _nslots; ++i)
+            if (_slots[i].h_in == _h_in) pd.slot = i;
+        check(hipEventRecord(_slots[pd.slot].done, _s));
+        pd.valid = true;
+        pd.nf = nf;
+        pd.used = used;
+        pd.unknown = unknown;
+        pd.total = total;
+        pd.any_var = any_var;
+        pd.mixed = mixed;
+        pd.ov = true;
+        pd.gpu_s = secs(t0);
+        return pd;
+    }
+
     /// Wait for a batch's last copy (its slot's buffers in use), check its
     /// statuses and send its answers: the GPU's in runs, the CPU's in their
     /// places.
@@ -1138,7 +1489,8 @@ private:
         if (st.gpu_batches == 0 && st.fallback_requests == 0) st.first_batch_seconds = dt;
         st.gpu_seconds += dt;
         st.h2d_bytes += used + 4 * nf;
-        st.d2h_bytes += total + (unknown || var_methods ? nf : 0) + (unknown && any_var ? 8 * (nf + 1) : 0);
+        st.d2h_bytes += pd.ov ? total + (unknown ? nf + 4 * (nf + 1) : 0)
+                              : total + (unknown || var_methods ? nf : 0) + (unknown && any_var ? 8 * (nf + 1) : 0);
         if (total) {
             st.gpu_batches += 1;
             st.mixed_batches += mixed ? 1 : 0;
@@ -1159,7 +1511,10 @@ private:
         for (uint64_t i = 0; i < nf; ++i) {
             const uint8_t c = _h_cls[i];
             if (c != SRPC_FRAME_UNKNOWN) {
-                run = any_var ? _h_out_off[i + 1] : run + _m[c]->fout;  // the end of frame i's answer
+                // the end of frame i's answer
+                run = pd.ov ? _h_ov_offs[i + 1] : any_var ? _h_out_off[i + 1] : run + _m[c]->fout;
+                if (pd.ov && _h_ov_offs[i + 1] == _h_ov_offs[i])
+                    throw plan_error("batch_server: a handler's response offsets decrease", SRPC_E_INVALID);
                 continue;
             }
             if (run > pos) _pieces.push_back({true, pos, run - pos});
@@ -1292,6 +1647,19 @@ private:
     std::vector<void* const*> _req_tbl, _resp_mut_tbl;    // per method: its request / response columns
     std::vector<std::vector<const void*>> _const_resp;
     std::vector<const void* const*> _resp_tbl;
+    // ordered mode with string methods
+    bool _ordered_var = false;
+    ordered_var_handler_t _ovhandler;
+    std::vector<const srpc_plan*> _ov_in_plans, _ov_out_plans;
+    std::vector<uint64_t* const*> _ov_req_offs;            // per method: its request leaves' offsets arrays
+    std::vector<const uint64_t* const*> _ov_c_req_offs, _ov_c_resp_offs;
+    std::vector<uint64_t* const*> _ov_resp_offs;
+    std::vector<const uint64_t*> _ov_req_scap, _ov_resp_cap;
+    uint32_t _ov_slots = 0;                                 // string leaves of all requests
+    void *_d_ov_ends = nullptr, *_d_ov_total = nullptr, *_d_ov_offs = nullptr, *_d_ov_scratch = nullptr;
+    uint64_t *_h_ov_ends = nullptr, *_h_ov_total = nullptr;
+    uint32_t* _h_ov_offs = nullptr;
+    uint64_t _ov_scratch_bytes = 0;
     // string methods
     std::vector<const uint64_t*> _var_rec;  // per method: its response index (nullptr: fixed)
     std::vector<size_t> _var_idx;           // the string methods' slots

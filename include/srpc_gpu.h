@@ -874,6 +874,90 @@ int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, in
                                          uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
                                          uint64_t scratch_bytes, void* stream);
 
+/* ---- batches of request frames of several methods with string bodies, in
+ * arrival order (server side; added within ABI 8) --------------------------------
+ * srpc_frames_unpack_requests_mixed with string plans allowed beside the
+ * fixed-size ones: the union of the two sections above, and the mirror of
+ * srpc_frames_pack_requests_mixed_var.  srpc_frames_unpack_requests_mixed keeps
+ * refusing string plans.
+ *
+ * Plans: K = nplans = 1..16 REQUEST plans, each of one of the two kinds the
+ * *_mixed_var calls take -- a fixed-size plan with the framed prefix `BE32(payload)
+ * | str(method) | str(Req::name)`, or a string plan (SRPC_PATH_VAR, at most
+ * SRPC_FRAMES_MAX_STRINGS strings) with the unframed prefix `str(method) |
+ * str(Req::name)`; at most SRPC_FRAMES_MIXED_MAX_FIELDS leaves in all; buf_len
+ * under 4 GiB, nframes under 2^32.
+ * Frames: frame i is bytes [d_offs[i], end_i) of d_buf, end_i = d_offs[i + 1], or
+ * buf_len for the last frame.
+ *   d_class[i] (u8, device, out) is exactly what srpc_frames_classify writes for
+ *     the same plans and input; the first matching plan wins.  A fixed plan
+ *     matches when the frame's length is F_k and its first prefix_len_k bytes are
+ *     the plan's prefix.  A string plan matches when the length is >= 4 + the
+ *     least payload (prefix, fixed fields, 8 per string), BE32 == len - 4, the
+ *     payload starts with the plan's prefix and the walk of its fields ends
+ *     exactly at end_i, each string's u64 length being read from the frame and
+ *     compared as `len > end - cursor`, so 2^63 and 2^64 - 1 cannot wrap.
+ *     Everything else is SRPC_FRAME_UNKNOWN: offsets out of order, an end past
+ *     buf_len, a frame under 4 bytes, a string that runs past the end, trailing
+ *     bytes after the walk.
+ *   rank(i) is the number of frames j < i with the same class.  A frame of class
+ *     k goes to element e = h_first[k] + rank(i): fixed leaves to d_cols[k][f][e],
+ *     a string leaf's chars back to back into d_cols[k][f] in element order.
+ *     d_cols, d_str_offs, h_str_cap, h_first (NULL = zeros) and h_cap are those
+ *     of srpc_frames_unpack_replies_mixed_var, and the string offsets follow its
+ *     rule: absolute in d_str_offs[k][f], entry 0 written as 0 when h_first[k] ==
+ *     0, otherwise continuing from entry h_first[k]; entries h_first[k] + 1 ..
+ *     h_first[k] + count_k are written, never past entry h_cap[k].  d_ends[s]
+ *     (device, one u64 per string slot, numbered over the plans and then their
+ *     string leaves) is the end offset of slot s.  No char at or past
+ *     h_str_cap[k][f] is written while the offsets still count every frame: an
+ *     overflow shows as d_ends[s] > capacity.
+ *   A frame whose element would be at or past h_cap[k] keeps its class and
+ *     writes no column or offsets element: SRPC_STATUS_BOUNDS, first_bad_record
+ *     the smallest such i.  Nothing is written for an unknown frame.
+ *   d_index (opaque, 8-byte aligned, srpc_frames_mixed_index_bytes(nframes, K))
+ *     receives the index srpc_frames_mixed_index builds over d_class: it serves
+ *     srpc_frames_mixed_ranks and the reply pack.  d_counts[0..K] are as in
+ *     srpc_frames_unpack_requests_mixed.
+ *   Scratch: srpc_frames_mixed_var_scratch_bytes(req_plans, K, nframes), 8-byte
+ *     aligned.
+ *   - no byte outside [d_buf, d_buf + buf_len) is read;
+ *   - no column, offsets or char byte is written but the frames' own; the last
+ *     partial 16-byte chunk of any output is written bytewise;
+ *   - *d_status (may be NULL) is reset by the call;
+ *   - the call is stream-ordered, allocates nothing and waits on no other
+ *     workgroup; its launches (status reset, the plans' description into
+ *     scratch, classify, the index's two, parse, the slot scan's three, copy)
+ *     depend neither on the data nor on K, so it can be captured.  The stream
+ *     is read twice: a frame's rank needs the class of every frame before it;
+ *   - work is bounded by buf_len + nframes * (K prefix compares + the largest
+ *     fixed part) on any input: a frame that does not lie whole inside its
+ *     tile's image window is judged and parsed from global memory by its lane,
+ *     which touches its fixed part and its length words only.
+ *
+ * Refused with nothing launched, in this order: a NULL required pointer
+ * (req_plans, d_cols, d_str_offs, h_str_cap, h_cap, d_index, d_counts, d_ends,
+ * d_scratch; d_buf, d_offs, d_class when nframes > 0), nplans outside 1..16,
+ * buf_len >= 4 GiB or nframes >= 2^32 (SRPC_E_INVALID; checked before any plan
+ * is read); a fixed plan with a prefix under 4 bytes, a string plan with a prefix
+ * under 1 byte or more than SRPC_FRAMES_MAX_STRINGS strings, more than
+ * SRPC_FRAMES_MIXED_MAX_FIELDS leaves (SRPC_E_UNSUPPORTED); a misaligned d_buf or
+ * column (16), offsets array, index, d_counts, d_ends or scratch (8), d_offs (4)
+ * (SRPC_E_ALIGN); an index or a scratch that is too small (SRPC_E_CAPACITY).
+ *
+ * The ordered reply pack is srpc_frames_pack_requests_mixed_var itself: called
+ * with the RESPONSE plans (of the same two kinds), the response columns,
+ * d_method = d_class and the d_index this call wrote, it writes the reply stream
+ * in arrival order, zero bytes for an unknown frame. */
+int srpc_frames_unpack_requests_mixed_var(
+    const srpc_plan* const* req_plans, int nplans,
+    const uint8_t* d_buf, uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+    void* const* const* d_cols, uint64_t* const* const* d_str_offs,
+    const uint64_t* const* h_str_cap, const uint64_t* h_first, const uint64_t* h_cap,
+    uint8_t* d_class /* nframes, out */, void* d_index, uint64_t index_bytes,
+    uint64_t* d_counts /* nplans + 1, out */, uint64_t* d_ends /* one per string slot, out */,
+    srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
 /* ---- utilities --------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
@@ -916,7 +1000,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
  * srpc_frames_unpack_replies / _unpack_replies_var / srpc_frames_mixed_index /
  * _pack_requests_mixed / _unpack_replies_mixed / _unpack_requests_mixed /
- * _pack_requests_mixed_var / _unpack_replies_mixed_var call made on this host
+ * _pack_requests_mixed_var / _unpack_replies_mixed_var /
+ * _unpack_requests_mixed_var call made on this host
  * thread record the begin timestamp of the first kernel into `start_event`
  * and the end timestamp of the last into `stop_event` (hipEvent_t handles
  * created with timing enabled; either may be NULL), taken from the dispatch

@@ -41,48 +41,6 @@ constexpr uint32_t kReqUnknown = SRPC_FRAME_UNKNOWN;
 __device__ __forceinline__ uint32_t req_lo_at(const MixArgs& a) { return a.img + 32; }
 __device__ __forceinline__ uint32_t req_tmpl_at(const MixArgs& a) { return a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u); }
 
-// lo[j] = the offset of frame c0 + j, buf_len past the last frame (the last
-// frame ends at buf_len).  Complete after the next barrier.
-__device__ __forceinline__ void req_offsets(uint32_t* lo, uint32_t T, const uint32_t* __restrict__ offs, uint64_t nframes,
-                                            uint64_t c0, uint64_t buf_len) {
-    for (uint32_t j = threadIdx.x; j <= T; j += kBlock)
-        lo[j] = c0 + j < nframes ? offs[c0 + j] : static_cast<uint32_t>(buf_len);
-}
-
-struct ReqSpan {
-    uint64_t s0;      // the image's first byte of the stream (16-byte aligned)
-    uint32_t staged;  // bytes of the stream in the image
-};
-
-// The span of the tile's nr frames -> image, from a 16-byte boundary; bytes of
-// [0, buf_len) only, at most cap of them.  lo[] is complete; ends with a barrier.
-__device__ __forceinline__ ReqSpan req_stage(uint8_t* img, const uint32_t* lo, uint32_t nr, uint32_t cap,
-                                             const uint8_t* __restrict__ buf, uint64_t buf_len) {
-    ReqSpan sp{0, 0};
-    if (nr) {
-        const uint64_t o0 = lo[0], oe = lo[nr];
-        sp.s0 = o0 & ~15ull;
-        if (o0 <= buf_len) {
-            const uint64_t end = oe >= o0 && oe <= buf_len ? oe : buf_len;
-            sp.staged = static_cast<uint32_t>(min<uint64_t>(end - sp.s0, cap));
-        }
-    }
-    const uint8_t* src = buf + sp.s0;
-    const uint32_t full = sp.staged >> 4;
-    constexpr int kLoads = 4;  // 16-byte loads in flight per lane
-    for (uint32_t cb = threadIdx.x; cb < full; cb += kBlock * kLoads) {
-        uint4 vv[kLoads];
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u) vv[u] = *reinterpret_cast<const uint4*>(src + 16 * min(cb + u * kBlock, full - 1));
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u)
-            if (cb + u * kBlock < full) *reinterpret_cast<uint4*>(img + 16 * (cb + u * kBlock)) = vv[u];
-    }
-    for (uint32_t b = full * 16 + threadIdx.x; b < sp.staged; b += kBlock) img[b] = src[b];
-    __syncthreads();
-    return sp;
-}
-
 __global__ __launch_bounds__(kBlock) void k_req_classify(MixArgs a, const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                          const uint32_t* __restrict__ offs, uint64_t nframes,
                                                          uint8_t* __restrict__ cls) {

@@ -1,0 +1,273 @@
+// mixed_req_var.hip -- a batch of request frames of several methods, string-
+// bodied ones included, decoded in arrival order (server side;
+// srpc_frames_unpack_requests_mixed_var of include/srpc_gpu.h): mixed_req.hip's
+// decode over the two plan kinds of mixed_var.hip, the mirror of that file's
+// request pack.
+//
+// The class of a frame is found from the frame itself (srpc_frames_classify's
+// rule); its fields go to element first[k] + rank(i) of plan k's columns, rank(i)
+// being the frames of the same class before it.  The ranks need the class of
+// every earlier frame, so the stream is read twice and nothing waits on another
+// workgroup:
+//
+//   k_mrv_classify  a workgroup per tile of T frames (MvDesc::T): the tile's span
+//       staged into the 32 KiB LDS image from a 16-byte boundary, the frame
+//       offsets beside it, the K prefixes as LDS templates.  A lane per frame:
+//       fixed plans are compared only where F_k is the frame's length, eight
+//       bytes at a time; for string plans BE32 == len - 4 is tested once, then
+//       per plan the least length, the prefix and the walk of the fields, which
+//       reads the length words only (at most 16 per plan).  A frame that does
+//       not lie whole inside the image is judged from global memory by its lane,
+//       reading no more than its fixed part.  Writes the class byte only.
+//   k_mixed_hist / k_mixed_scan (mixed.hip) over the class bytes: the index and
+//       the counts, unknown frames in column K.
+//   k_mrv_parse     the same tile and staging; the granule's ranks from the index
+//       (mix_ranks); a lane per frame stores its fixed leaves, each string's
+//       length into its offsets entry and its chars' stream offset to scratch.
+//       Every read is bounded by the frame's own extent again: the class is
+//       not trusted to keep the walk inside buf_len.
+//   the slot scan and the char copy of mixed_var.hip (mv_slots_launch,
+//       mv_copy_launch) with d_class as the method vector.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "mixed_common.h"
+#include "mixed_var_common.h"
+#include "plan.h"
+#include "srpc_gpu.h"
+
+namespace srpc_impl {
+namespace {
+
+constexpr uint32_t kMrvUnknown = SRPC_FRAME_UNKNOWN;
+
+// The frame of a lane: in the image when it lies whole inside it, else in
+// global memory.
+struct MrvFrame {
+    const uint8_t* img;  // the image
+    const uint8_t* g;    // the frame in global memory
+    uint32_t q;          // the frame's image offset
+    bool in_img;
+};
+
+// 8 bytes at frame byte c (c + 8 <= the frame's length).
+__device__ __forceinline__ uint64_t mrv_u64(const MrvFrame& fr, uint64_t c) {
+    return fr.in_img ? lds_u64(fr.img, fr.q + static_cast<uint32_t>(c)) : mv_get(fr.g + c, 8);
+}
+
+// The s <= 8 bytes at frame byte c.
+__device__ __forceinline__ uint64_t mrv_field(const MrvFrame& fr, uint64_t c, uint32_t s) {
+    if (!fr.in_img) return mv_get(fr.g + c, s);
+    const uint32_t at = fr.q + static_cast<uint32_t>(c);
+    return s == 1 ? fr.img[at] : lds_u64(fr.img, at) & (s == 8 ? ~0ull : (1ull << (8 * s)) - 1);
+}
+
+// Frame bytes [at, at + pl) == the template (8-byte aligned in LDS, pl > 0).
+__device__ __forceinline__ bool mrv_prefix_eq(const MrvFrame& fr, uint32_t at, const uint8_t* pre, uint32_t pl) {
+    bool eq = true;
+    if (fr.in_img) {
+        for (uint32_t b = 0; b < pl; b += 8) {
+            const uint64_t m = pl - b >= 8 ? ~0ull : (1ull << (8 * (pl - b))) - 1;
+            eq &= ((lds_u64(fr.img, fr.q + at + b) ^ *reinterpret_cast<const uint64_t*>(pre + b)) & m) == 0;
+        }
+    } else {
+        for (uint32_t b = 0; b < pl && eq; ++b) eq = fr.g[at + b] == pre[b];
+    }
+    return eq;
+}
+
+// LDS of k_mrv_classify: image[kMixImage + 16] | templates[tmpl_bytes] | 16 pad,
+// then the static tile offsets.
+__global__ __launch_bounds__(kBlock) void k_mrv_classify(const MvDesc* __restrict__ d, const uint8_t* __restrict__ buf,
+                                                         uint64_t buf_len, const uint32_t* __restrict__ offs,
+                                                         uint64_t nframes, uint8_t* __restrict__ cls) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t lo[kBlock + 1];
+    uint8_t* img = lds;
+    const uint8_t* tmpl = lds + kMixImage + 16;
+    const uint32_t K = d->nplans, T = d->T;
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * T;
+    const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(T, nframes - c0)) : 0;
+    mv_templates(lds + kMixImage + 16, d);
+    req_offsets(lo, T, offs, nframes, c0, buf_len);
+    __syncthreads();
+    const ReqSpan sp = req_stage(img, lo, nr, kMixImage, buf, buf_len);
+
+    const uint32_t j = threadIdx.x;
+    if (j >= nr) return;
+    const uint64_t o = lo[j], e = lo[j + 1];
+    uint32_t k = kMrvUnknown;
+    if (o <= e && e <= buf_len) {  // else: offsets out of order or past the buffer, no byte is read
+        const uint64_t len = e - o;
+        MrvFrame fr;
+        fr.img = img;
+        fr.g = buf + o;
+        fr.in_img = o >= sp.s0 && o - sp.s0 + len <= sp.staged;
+        fr.q = static_cast<uint32_t>(o - sp.s0);
+        // string plans: the BE32 is the payload's length, whichever the plan
+        const bool framed = len >= 4 && __builtin_bswap32(static_cast<uint32_t>(mrv_field(fr, 0, 4))) == len - 4;
+        for (uint32_t p = 0; p < K && k == kMrvUnknown; ++p) {
+            const uint32_t pl = d->prefix_len[p];
+            const uint8_t* pre = tmpl + d->tmpl[p];
+            if (!d->var[p]) {
+                // F_p >= pl: the prefix is inside the frame
+                if (d->F[p] == len && mrv_prefix_eq(fr, 0, pre, pl)) k = p;
+                continue;
+            }
+            // F_p = 4 + the least payload >= 4 + pl
+            if (!framed || len < d->F[p] || !mrv_prefix_eq(fr, 4, pre, pl)) continue;
+            // the walk of the fields ends exactly at the frame's end
+            uint64_t c = 4 + pl;
+            bool ok = true;
+            for (uint32_t f = d->field0[p]; ok && f < d->field0[p + 1]; ++f) {
+                const uint32_t s = d->size[f];
+                if (s) {
+                    ok = s <= len - c;
+                    c += s;
+                } else if (8 > len - c) {
+                    ok = false;
+                } else {
+                    const uint64_t sl = mrv_u64(fr, c);
+                    c += 8;
+                    ok = sl <= len - c;  // 2^63 or 2^64 - 1 cannot wrap
+                    if (ok) c += sl;
+                }
+            }
+            if (ok && c == len) k = p;
+        }
+    }
+    cls[c0 + j] = static_cast<uint8_t>(k);
+}
+
+// LDS of k_mrv_parse: image[kMixImage + 16], then static wcnt and the tile's
+// offsets.
+__global__ __launch_bounds__(kBlock) void k_mrv_parse(const MvDesc* __restrict__ d, const uint8_t* __restrict__ cls,
+                                                      const uint32_t* __restrict__ table, uint64_t rows,
+                                                      const uint8_t* __restrict__ buf, uint64_t buf_len,
+                                                      const uint32_t* __restrict__ offs, uint64_t nframes,
+                                                      uint32_t* __restrict__ srcs, uint32_t* __restrict__ counts,
+                                                      srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint32_t lo[kBlock + 1];
+    uint8_t* img = lds;
+    const uint32_t K = d->nplans, T = d->T;
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);  // the tile's first lane
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(T, nframes - c0)) : 0;
+    req_offsets(lo, T, offs, nframes, c0, buf_len);
+    const MixLane r = mix_ranks(cls, nframes, K, table, rows, g, wcnt);  // barrier: lo[] is complete
+    // the batch's frames per plan, for the slot scan: the last tile's granule is the last one
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < K) {
+        uint32_t v = wcnt[kMixWaves * kMixRow + threadIdx.x];
+        for (uint32_t w = 0; w < kMixWaves; ++w) v += wcnt[w * kMixRow + threadIdx.x];
+        counts[threadIdx.x] = v;
+    }
+    const ReqSpan sp = req_stage(img, lo, nr, kMixImage, buf, buf_len);
+
+    if (threadIdx.x < j0 || threadIdx.x >= j0 + nr || r.cls >= K) return;  // not this tile's, or nobody's frame
+    const uint32_t k = r.cls;
+    if (r.rank >= d->room[k]) {
+        if (st) report_bad(st, SRPC_STATUS_BOUNDS, i);
+        return;
+    }
+    const uint32_t j = threadIdx.x - j0;
+    const uint64_t o = lo[j], end = lo[j + 1];
+    // the class says the frame is one record of plan k; every read below is still
+    // bounded by the frame's own extent, and what does not fit decodes to zero / empty
+    bool ok = o <= end && end <= buf_len;
+    const uint64_t len = ok ? end - o : 0;
+    MrvFrame fr;
+    fr.img = img;
+    fr.g = buf + o;
+    fr.in_img = ok && o >= sp.s0 && o - sp.s0 + len <= sp.staged;
+    fr.q = static_cast<uint32_t>(o - sp.s0);
+    const uint64_t e = d->first[k] + r.rank;
+    uint64_t c = (d->var[k] ? 4 : 0) + d->prefix_len[k];
+    ok = ok && c <= len;
+    uint32_t t = 0;
+    for (uint32_t f = d->field0[k]; f < d->field0[k + 1]; ++f) {
+        const uint32_t s = d->size[f];
+        if (s) {
+            ok = ok && s <= len - c;
+            store_elem(d->col[f] + e * s, s, ok ? mrv_field(fr, c, s) : 0);
+            if (ok) c += s;
+        } else {
+            ok = ok && 8 <= len - c;
+            uint64_t sl = ok ? mrv_u64(fr, c) : 0;
+            if (ok) c += 8;
+            if (sl > len - c) {
+                sl = 0;
+                ok = false;
+            }
+            d->soffs[f][e + 1] = sl;  // its length: the slot scan turns lengths into offsets
+            srcs[t * nframes + i] = static_cast<uint32_t>(o + c);
+            c += sl;
+            ++t;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace srpc_impl
+
+using namespace srpc_impl;
+
+extern "C" {
+
+int srpc_frames_unpack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
+                                          uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                          void* const* const* d_cols, uint64_t* const* const* d_str_offs,
+                                          const uint64_t* const* h_str_cap, const uint64_t* h_first,
+                                          const uint64_t* h_cap, uint8_t* d_class, void* d_index, uint64_t index_bytes,
+                                          uint64_t* d_counts, uint64_t* d_ends, srpc_unpack_status* d_status,
+                                          void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    const TimedCall timed;
+    // the arguments themselves are checked before any plan is read
+    if (!req_plans || !d_cols || !d_str_offs || !h_str_cap || !h_cap || !d_index || !d_counts || !d_ends || !d_scratch ||
+        nplans <= 0 || nplans > kMixPlans || buf_len >= (1ull << 32) || nframes >= (1ull << 32) ||
+        (nframes && (!d_buf || !d_offs || !d_class)))
+        return SRPC_E_INVALID;
+    static thread_local MvDesc d;
+    d = MvDesc{};
+    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
+    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_counts, 8) || !aligned(d_ends, 8) ||
+        !aligned(d_scratch, 8) || !aligned(d_offs, 4))
+        return SRPC_E_ALIGN;
+    if (int rc = mv_cols(req_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
+                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d))
+        return rc;
+    const MvScratch sc = mv_scratch(d, nframes);
+    if (index_bytes < mix_index_bytes(nframes, nplans) || scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
+    auto s = static_cast<hipStream_t>(stream);
+    auto* base = static_cast<uint8_t*>(d_scratch);
+    const auto* dd = reinterpret_cast<const MvDesc*>(base);
+    auto* counts = reinterpret_cast<uint32_t*>(base + sc.counts);
+    auto* partial = reinterpret_cast<uint64_t*>(base + sc.partial);
+    auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
+    auto* table = static_cast<uint32_t*>(d_index);
+    const uint64_t rows = mix_rows(nframes);
+    const uint32_t grid = static_cast<uint32_t>((nframes + d.T - 1) / d.T);
+    if (d_status)
+        if (int rc = mix_status_reset_launch(d_status, s)) return rc;
+    if (int rc = mv_upload(d, d_scratch, s)) return rc;
+    if (nframes)
+        launch(k_mrv_classify, dim3(grid), dim3(kBlock), mv_lds(d), s, dd, d_buf, buf_len, d_offs, nframes, d_class);
+    // unknown frames (0xFF) are ids >= K: column K of the index; no status here
+    if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
+    if (nframes)
+        launch(k_mrv_parse, dim3(grid), dim3(kBlock), kMixImage + 16, s, dd, static_cast<const uint8_t*>(d_class),
+               static_cast<const uint32_t*>(table), rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status);
+    if (d.nslots) {
+        mv_slots_launch(d, dd, counts, nframes, partial, sc.nb, d_ends, s);
+        if (nframes)
+            mv_copy_launch(dd, d_class, static_cast<const uint32_t*>(table), rows, nframes, d_buf, srcs, s);
+    }
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+}  // extern "C"

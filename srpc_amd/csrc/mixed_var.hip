@@ -2,7 +2,9 @@
 // whose plans may have string fields (client side;
 // srpc_frames_pack_requests_mixed_var, srpc_frames_unpack_replies_mixed_var of
 // include/srpc_gpu.h).  The call index and mix_ranks are those of mixed.hip
-// (mixed_common.h).  Nothing here waits on another workgroup.
+// (mixed_common.h).  Nothing here waits on another workgroup.  The server-side
+// request decode (mixed_req_var.hip) uses this file's description of the plans,
+// its slot scan and its char copy through mixed_var_common.h.
 //
 // Both calls first put their description of the plans (MvDesc: columns, offsets
 // arrays, layouts, 5.8 KiB -- more than kernel arguments hold) into scratch with
@@ -39,46 +41,17 @@
 #include <cstring>
 
 #include "mixed_common.h"
+#include "mixed_var_common.h"
 #include "plan.h"
 #include "srpc_gpu.h"
 
 namespace srpc_impl {
 namespace {
 
-constexpr int kMvStr = SRPC_FRAMES_MAX_STRINGS;
 constexpr uint64_t kMvSat = 1ull << 32;        // a frame length saturates here: past any out_cap
 constexpr uint32_t kMvScanBlock = 1024;
-constexpr uint32_t kMvSlotItems = 8;
-constexpr uint32_t kMvSlotBlock = kBlock * kMvSlotItems;  // offsets entries per workgroup of the slot scan
 constexpr uint64_t kMvInImage = 1ull << 63;    // run destination: an image offset
 
-struct alignas(16) MvDesc {
-    uint8_t* col[kMixFields];         // plan k's leaves: [field0[k], field0[k + 1])
-    uint64_t* soffs[kMixFields];      // a string leaf's offsets, else nullptr
-    uint64_t scap[kMixFields];        // decode: bytes a string column has
-    uint8_t size[kMixFields];         // 0: a string
-    uint8_t leaf_plan[kMixFields];
-    uint8_t slot_leaf[kMixFields];    // string slot -> leaf
-    uint8_t str_leaf[kMixPlans * kMvStr];  // plan k's t-th string -> leaf
-    const uint8_t* prefix[kMixPlans];
-    uint64_t first[kMixPlans];
-    uint32_t room[kMixPlans];
-    uint32_t F[kMixPlans];            // fixed plan: frame bytes; string plan: the frame without its chars
-    uint16_t prefix_len[kMixPlans];
-    uint16_t tmpl[kMixPlans];         // LDS offset of plan k's prefix template
-    uint16_t field0[kMixPlans + 1];
-    uint8_t var[kMixPlans];
-    uint8_t nstr[kMixPlans];
-    uint32_t nplans;
-    uint32_t nslots;
-    uint32_t maxstr;                  // max_k nstr[k]
-    uint32_t T;                       // calls per tile (divides kMixGranule)
-    uint32_t tmpl_bytes;
-};
-static_assert(sizeof(MvDesc) % 16 == 0, "uploaded in 16-byte words");
-
-constexpr uint32_t kMvChunk = 2048;
-constexpr uint32_t kMvChunks = (sizeof(MvDesc) + kMvChunk - 1) / kMvChunk;
 struct MvChunk {
     uint4 w[kMvChunk / 16];
 };
@@ -177,14 +150,6 @@ __global__ __launch_bounds__(kMvScanBlock) void k_mv_scan(uint64_t* __restrict__
         const uint64_t v = gsum[r];
         gsum[r] = run;
         run += v;
-    }
-}
-
-// The K prefixes into LDS at dst + d->tmpl[k].
-__device__ __forceinline__ void mv_templates(uint8_t* dst, const MvDesc* __restrict__ d) {
-    for (uint32_t k = 0; k < d->nplans; ++k) {
-        const uint8_t* src = d->prefix[k];
-        for (uint32_t b = threadIdx.x; b < d->prefix_len[k]; b += kBlock) dst[d->tmpl[k] + b] = src[b];
     }
 }
 
@@ -340,13 +305,6 @@ __global__ __launch_bounds__(kBlock) void k_mv_pack(const MvDesc* __restrict__ d
                 if (b0 + b >= lo && b0 + b < hi) out[b0 + b] = lds[16 * c + b];
         }
     }
-}
-
-// u64 of the k <= 8 bytes at p (LDS or global: a generic pointer), little-endian.
-__device__ __forceinline__ uint64_t mv_get(const uint8_t* p, uint32_t k) {
-    uint64_t v = 0;
-    for (uint32_t b = 0; b < k; ++b) v |= static_cast<uint64_t>(p[b]) << (8 * b);
-    return v;
 }
 
 // LDS of k_mv_parse: image[kMixImage + 16] | templates[tmpl_bytes], then static
@@ -621,6 +579,8 @@ inline uint32_t mv_tile(uint32_t fmax) {
     return t;
 }
 
+}  // namespace
+
 // The plans of one side into d's layout part.  min_fixed_prefix: 4 (request) or
 // 5 (reply).
 int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefix, MvDesc* d) {
@@ -696,30 +656,6 @@ int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const*
     return SRPC_OK;
 }
 
-// Scratch: desc | gsum[rows + 1] | counts[kMixPlans] | partial[nslots * nb] | srcs[maxstr * ncalls]
-struct MvScratch {
-    uint64_t gsum, counts, partial, srcs, bytes;
-    uint32_t nb;
-};
-
-inline MvScratch mv_scratch(const MvDesc& d, uint64_t ncalls) {
-    MvScratch s;
-    s.nb = static_cast<uint32_t>(std::max<uint64_t>(1, (ncalls + kMvSlotBlock - 1) / kMvSlotBlock));
-    uint64_t at = kMvChunks * kMvChunk;
-    s.gsum = at;
-    at += 8 * (mix_rows(ncalls) + 1);
-    s.counts = at;
-    at += 4 * kMixPlans;
-    s.partial = at;
-    at += 8ull * d.nslots * s.nb;
-    s.srcs = at;
-    at += (4ull * d.maxstr * ncalls + 7) & ~7ull;
-    s.bytes = at;
-    return s;
-}
-
-inline size_t mv_lds(const MvDesc& d) { return kMixImage + 16 + d.tmpl_bytes + 16; }
-
 int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) {
     for (uint32_t c = 0; c < kMvChunks; ++c) {
         MvChunk ch;
@@ -733,7 +669,19 @@ int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
 
-}  // namespace
+void mv_slots_launch(const MvDesc& d, const MvDesc* dd, const uint32_t* counts, uint64_t ncalls, uint64_t* partial,
+                     uint32_t nb, uint64_t* d_ends, hipStream_t s) {
+    launch(k_mv_slot_reduce, dim3(nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb);
+    launch(k_mv_slot_partials, dim3(d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb, d_ends);
+    launch(k_mv_slot_apply, dim3(nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb);
+}
+
+void mv_copy_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
+                    const uint8_t* d_buf, const uint32_t* srcs, hipStream_t s) {
+    launch(k_mv_copy, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, dd, d_method, table, rows, ncalls, d_buf,
+           srcs);
+}
+
 }  // namespace srpc_impl
 
 using namespace srpc_impl;
@@ -833,12 +781,8 @@ int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, in
                table, rows, ncalls, d_buf, buf_len, d_offs, nframes, static_cast<uint32_t>(unanswered_code), d_codes, srcs,
                counts, d_status);
     if (d.nslots) {
-        launch(k_mv_slot_reduce, dim3(sc.nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb);
-        launch(k_mv_slot_partials, dim3(d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb, d_ends);
-        launch(k_mv_slot_apply, dim3(sc.nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, sc.nb);
-        if (ncalls)
-            launch(k_mv_copy, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, dd, d_method, table, rows, ncalls,
-                   d_buf, srcs);
+        mv_slots_launch(d, dd, counts, ncalls, partial, sc.nb, d_ends, s);
+        if (ncalls) mv_copy_launch(dd, d_method, table, rows, ncalls, d_buf, srcs, s);
     }
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }

@@ -1,0 +1,109 @@
+// mixed_var_common.h -- internal: what mixed_var.hip (client side: request pack,
+// reply decode) and mixed_req_var.hip (server side: request decode) share: the
+// description of the plans that both put into scratch (MvDesc), its host-side
+// builders, the scratch layout, and the launches of the kernels that stay in
+// mixed_var.hip -- the description upload, the segmented scan over the string
+// slots and the char copy.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+
+#include "mixed_common.h"
+#include "plan.h"
+#include "srpc_gpu.h"
+
+namespace srpc_impl {
+
+constexpr int kMvStr = SRPC_FRAMES_MAX_STRINGS;
+constexpr uint32_t kMvSlotItems = 8;
+constexpr uint32_t kMvSlotBlock = kBlock * kMvSlotItems;  // offsets entries per workgroup of the slot scan
+
+struct alignas(16) MvDesc {
+    uint8_t* col[kMixFields];         // plan k's leaves: [field0[k], field0[k + 1])
+    uint64_t* soffs[kMixFields];      // a string leaf's offsets, else nullptr
+    uint64_t scap[kMixFields];        // decode: bytes a string column has
+    uint8_t size[kMixFields];         // 0: a string
+    uint8_t leaf_plan[kMixFields];
+    uint8_t slot_leaf[kMixFields];    // string slot -> leaf
+    uint8_t str_leaf[kMixPlans * kMvStr];  // plan k's t-th string -> leaf
+    const uint8_t* prefix[kMixPlans];
+    uint64_t first[kMixPlans];
+    uint32_t room[kMixPlans];
+    uint32_t F[kMixPlans];            // fixed plan: frame bytes; string plan: the frame without its chars
+    uint16_t prefix_len[kMixPlans];
+    uint16_t tmpl[kMixPlans];         // LDS offset of plan k's prefix template
+    uint16_t field0[kMixPlans + 1];
+    uint8_t var[kMixPlans];
+    uint8_t nstr[kMixPlans];
+    uint32_t nplans;
+    uint32_t nslots;
+    uint32_t maxstr;                  // max_k nstr[k]
+    uint32_t T;                       // calls per tile (divides kMixGranule)
+    uint32_t tmpl_bytes;
+};
+static_assert(sizeof(MvDesc) % 16 == 0, "uploaded in 16-byte words");
+
+constexpr uint32_t kMvChunk = 2048;
+constexpr uint32_t kMvChunks = (sizeof(MvDesc) + kMvChunk - 1) / kMvChunk;
+
+// The K prefixes into LDS at dst + d->tmpl[k].
+__device__ __forceinline__ void mv_templates(uint8_t* dst, const MvDesc* __restrict__ d) {
+    for (uint32_t k = 0; k < d->nplans; ++k) {
+        const uint8_t* src = d->prefix[k];
+        for (uint32_t b = threadIdx.x; b < d->prefix_len[k]; b += kBlock) dst[d->tmpl[k] + b] = src[b];
+    }
+}
+
+// u64 of the k <= 8 bytes at p (LDS or global: a generic pointer), little-endian.
+__device__ __forceinline__ uint64_t mv_get(const uint8_t* p, uint32_t k) {
+    uint64_t v = 0;
+    for (uint32_t b = 0; b < k; ++b) v |= static_cast<uint64_t>(p[b]) << (8 * b);
+    return v;
+}
+
+// Scratch: desc | gsum[rows + 1] | counts[kMixPlans] | partial[nslots * nb] | srcs[maxstr * ncalls]
+struct MvScratch {
+    uint64_t gsum, counts, partial, srcs, bytes;
+    uint32_t nb;
+};
+
+inline MvScratch mv_scratch(const MvDesc& d, uint64_t ncalls) {
+    MvScratch s;
+    s.nb = static_cast<uint32_t>(std::max<uint64_t>(1, (ncalls + kMvSlotBlock - 1) / kMvSlotBlock));
+    uint64_t at = kMvChunks * kMvChunk;
+    s.gsum = at;
+    at += 8 * (mix_rows(ncalls) + 1);
+    s.counts = at;
+    at += 4 * kMixPlans;
+    s.partial = at;
+    at += 8ull * d.nslots * s.nb;
+    s.srcs = at;
+    at += (4ull * d.maxstr * ncalls + 7) & ~7ull;
+    s.bytes = at;
+    return s;
+}
+
+// Dynamic LDS of a kernel with the image and the templates.
+inline size_t mv_lds(const MvDesc& d) { return kMixImage + 16 + d.tmpl_bytes + 16; }
+
+// ---- mixed_var.hip ----
+// The plans of one side into d's layout part.  min_fixed_prefix: 4 (request) or
+// 5 (reply).
+int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefix, MvDesc* d);
+// Columns, offsets arrays and rooms.
+int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
+            const uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap, const uint64_t* h_first,
+            const uint64_t* h_cap, MvDesc* d);
+// d -> the head of d_scratch, in kMvChunks launches.
+int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s);
+// The segmented scan over all string slots (three launches whatever K): the
+// lengths the parse left in the offsets arrays become offsets, d_ends[s] each
+// slot's end.  counts: the chunk's calls per plan (device, u32).
+void mv_slots_launch(const MvDesc& d, const MvDesc* dd, const uint32_t* counts, uint64_t ncalls, uint64_t* partial,
+                     uint32_t nb, uint64_t* d_ends, hipStream_t s);
+// The chars of every good call, from buf + srcs[t * ncalls + i] into the columns.
+void mv_copy_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
+                    const uint8_t* d_buf, const uint32_t* srcs, hipStream_t s);
+
+}  // namespace srpc_impl

@@ -607,6 +607,22 @@ class MixedVarFrames:
                                                                _dptr(ends), _dptr(status), _dptr(scratch),
                                                                scratch_bytes, _stream(stream))
 
+    def unpack_requests(self, buf, buf_len: int, offs, nframes: int, cols, str_offs, str_cap, first, cap, cls, index,
+                        index_bytes: int, counts, ends, status, scratch, scratch_bytes: int, stream=None) -> int:
+        """Server side (srpc_frames_unpack_requests_mixed_var): classify the
+        frames against these request plans and decode each into its plan's
+        columns at its arrival rank; ``cls``, ``index``, ``counts`` and ``ends``
+        are outputs.  The ordered reply pack is ``pack`` of the response plans'
+        MixedVarFrames with ``method=cls`` and this ``index``."""
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        cap_arr, k3 = self._table(str_cap, lambda x: 0 if x is None else int(x), C.c_uint64)
+        self._keep += (k3,)
+        return _lib.lib().srpc_frames_unpack_requests_mixed_var(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                                nframes, c_arr, s_arr, cap_arr, h_first, h_cap,
+                                                                _dptr(cls), _dptr(index), index_bytes, _dptr(counts),
+                                                                _dptr(ends), _dptr(status), _dptr(scratch),
+                                                                scratch_bytes, _stream(stream))
+
 
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
            "fill_splitmix_i32", "time_next_call", "framed_request_prefix", "framed_response_prefix",

@@ -1,0 +1,25 @@
+"""srpc::gpu::batch_server in ordered mode with string-bodied methods
+(include/srpc/gpu_server.hpp: set_ordered_var, set_ordered_var_handler) against
+srpc::gpu::batch_client::call_mixed with leg_var legs over a socketpair:
+tests/cpp/gpu_server_ordered_var_test.cpp."""
+import os
+import subprocess
+
+import pytest
+
+from tests.cpp import build_cpp
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def test_cpp_batch_server_ordered_var_mode():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from srpc_amd import build
+    build.build()
+    exe = build_cpp.build_one(os.path.join(HERE, "cpp", "gpu_server_ordered_var_test.cpp"))
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and " 0 failed" in out.stdout, out.stdout + out.stderr

@@ -708,6 +708,222 @@ def main():
                      "new_name": "unpack_requests_mixed",
                      "route_name": f"classify + {K if K > 1 else 0} x gather + {K} x srpc_gpu_unpack"})
 
+    def requests_var_case(name, methods, n, maxlen):
+        """Server side with string-bodied methods: a stream of n request frames
+        over the methods in a uniformly random order, string lengths uniform in
+        0..maxlen, classified and decoded into the methods' columns, chars and
+        offsets in arrival order by one srpc_frames_unpack_requests_mixed_var.
+        The stream is srpc_frames_pack_requests_mixed_var's (its first 4096
+        frames checked against the CPU oracle); the decode is checked against the
+        method vector and the columns the frames were packed from.  Algorithmic
+        bytes: frames + fields + chars + 8 per string offset + 1 class byte + 4
+        offset bytes per frame + the index.  Beside it, timed alternately on
+        stream events, the bucket route of batch_server: srpc_frames_classify,
+        then per string method srpc_frames_gather_var + srpc_gpu_unpack_var, per
+        fixed method srpc_frames_gather + srpc_gpu_unpack (the route's host sync
+        for the bucket counts is not in its time)."""
+        if args.only not in name:
+            return
+        from srpc_amd import FrameClassifier, MixedFrames, MixedVarFrames, framed_request_prefix
+        STRING = oracle.STRING
+        K = len(methods)
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(11)
+        d_method = torch.randint(0, K, (n,), dtype=torch.uint8, device=dev, generator=gen)
+        counts = torch.bincount(d_method.to(torch.int64), minlength=K).cpu().numpy()
+        var = [STRING in rq.kinds for _, rq, _ in methods]
+        req = [GpuPacker.for_request(rq, m) if v else GpuPacker(rq, framed_request_prefix(rq, m))
+               for (m, rq, _), v in zip(methods, var)]
+        qcols, qoffs, fixed_part = [], [], []
+        for k, (_, rq, _) in enumerate(methods):
+            c_k = int(counts[k])
+            cs, os_ = [], []
+            for kind in rq.kinds:
+                if kind == STRING:
+                    lens = torch.randint(0, maxlen + 1, (c_k,), dtype=torch.int64, device=dev, generator=gen)
+                    o = torch.zeros(c_k + 1, dtype=torch.int64, device=dev)
+                    o[1:] = torch.cumsum(lens, 0)
+                    cs.append(torch.randint(0, 256, (int(o[c_k]) + 16,), dtype=torch.uint8, device=dev, generator=gen))
+                    os_.append(o)
+                else:
+                    c = torch.randint(0, 256, (c_k * oracle.KIND_SIZE[kind] + 16,), dtype=torch.uint8, device=dev,
+                                      generator=gen)
+                    cs.append(c & 1 if kind == oracle.BOOL else c)
+                    os_.append(None)
+            qcols.append(cs)
+            qoffs.append(os_ if var[k] else None)
+            fixed_part.append((4 if var[k] else 0) + len(req[k].prefix) +
+                              sum(8 if kind == STRING else oracle.KIND_SIZE[kind] for kind in rq.kinds))
+        chars = sum(int(o[-1]) for os_ in qoffs if os_ for o in os_ if o is not None)
+        total = sum(int(c) * f for c, f in zip(counts, fixed_part)) + chars
+        assert total < 1 << 32, "the stream must stay under 4 GiB"
+        mq = MixedVarFrames(req)
+        cap = [int(c) for c in counts]
+        nb = MixedFrames.index_bytes(n, K)
+        d_index = torch.empty(nb, dtype=torch.uint8, device=dev)
+        d_counts = torch.empty(8 * (K + 1), dtype=torch.uint8, device=dev)
+        st = torch.zeros(16, dtype=torch.uint8, device=dev)
+        assert MixedFrames.index(d_method, n, K, d_index, nb, d_counts, st, stream=s) == 0
+        sb = mq.scratch_bytes(n)
+        scratch = torch.empty(sb + 16, dtype=torch.uint8, device=dev)
+        buf = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        offs = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        d_total = torch.zeros(1, dtype=torch.int64, device=dev)
+        assert mq.pack(qcols, qoffs, None, cap, d_method, d_index, n, buf, total, offs, d_total, st, scratch, sb,
+                       stream=s) == 0
+        torch.cuda.synchronize()
+        ok = int(d_total[0]) == total and not bool(st[:4].any())
+        # the stream's first 4096 frames against the oracle's, interleaved on the host
+        m = min(4096, n)
+        hm = d_method[:m].cpu().numpy()
+        per = []
+        for k, (p, cs) in enumerate(zip(req, qcols)):
+            mk = int((hm == k).sum())
+            kinds = p.schema.kinds
+            hc, ho = [], []
+            for c, kind, f in zip(cs, kinds, range(len(kinds))):
+                if kind == STRING:
+                    o = qoffs[k][f][: mk + 1].cpu().numpy().astype(np.uint64)
+                    hc.append(c[: max(int(o[mk]), 1)].cpu().numpy())
+                    ho.append(o)
+                else:
+                    hc.append(c[: max(mk, 1) * oracle.KIND_SIZE[kind]].cpu().numpy().view(oracle.KIND_DTYPE[kind])[:mk])
+                    ho.append(None)
+            body = len(p.prefix) + sum(8 if kind == STRING else oracle.KIND_SIZE[kind] for kind in kinds)
+            rec = np.full(mk, body, np.int64)
+            for o in ho:
+                if o is not None:
+                    rec = rec + np.diff(o.astype(np.int64))
+            ends = np.concatenate([[0], np.cumsum(rec)])
+            w = oracle.pack(kinds, hc, mk, p.prefix, ho if var[k] else None) if mk else b""
+            per.append([(int(e - b).to_bytes(4, "big") if var[k] else b"") + w[int(b):int(e)]
+                        for b, e in zip(ends[:-1], ends[1:])])
+        seen = [0] * K
+        want = []
+        for i in range(m):
+            want.append(per[hm[i]][seen[hm[i]]])
+            seen[hm[i]] += 1
+        want = b"".join(want)
+        ok = ok and buf[: len(want)].cpu().numpy().tobytes() == want
+
+        back = [[torch.empty(total + 16 if kind == STRING else c.numel(), dtype=torch.uint8, device=dev)
+                 for c, kind in zip(cs, p.schema.kinds)] for cs, p in zip(qcols, req)]
+        boffs = [[torch.empty(int(counts[k]) + 1, dtype=torch.int64, device=dev) if kind == STRING else None
+                  for kind in p.schema.kinds] if var[k] else None for k, p in enumerate(req)]
+        scap = [[total if kind == STRING else None for kind in p.schema.kinds] if var[k] else None
+                for k, p in enumerate(req)]
+        nslots = sum(kind == STRING for p in req for kind in p.schema.kinds)
+        ends = torch.empty(8 * max(nslots, 1), dtype=torch.uint8, device=dev)
+        cls = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+
+        def clear():
+            for k, b in enumerate(back):
+                for f, c in enumerate(b):
+                    (c[: int(qoffs[k][f][-1]) + 16] if var[k] and qoffs[k][f] is not None else c).fill_(0xA5)
+            cls.fill_(0xA5)
+
+        def same():
+            good = torch.equal(cls[:n], d_method)
+            for k, p in enumerate(req):
+                for f, kind in enumerate(p.schema.kinds):
+                    if kind == STRING:
+                        used = int(qoffs[k][f][-1])
+                        good = good and torch.equal(boffs[k][f], qoffs[k][f])
+                        good = good and torch.equal(back[k][f][:used], qcols[k][f][:used])
+                    else:
+                        used = int(counts[k]) * oracle.KIND_SIZE[kind]
+                        good = good and torch.equal(qcols[k][f][:used], back[k][f][:used])
+            return bool(good)
+
+        def decode():
+            assert mq.unpack_requests(buf, total, offs, n, back, boffs, scap, None, cap, cls, d_index, nb, d_counts, ends,
+                                      st, scratch, sb, stream=s) == 0
+
+        clear()
+        decode()
+        torch.cuda.synchronize()
+        ok = ok and same() and not bool(st[:4].any())
+        ok = ok and np.array_equal(d_counts.cpu().numpy().view(np.uint64), np.append(counts, 0).astype(np.uint64))
+
+        # the bucket route
+        fc = FrameClassifier([(p, 0 if v else 23) for p, v in zip(req, var)])
+        r_cls = torch.empty(n + 16, dtype=torch.uint8, device=dev)
+        r_idx = torch.empty(4 * K * n + 16, dtype=torch.uint8, device=dev)
+        r_counts = torch.empty(8 * (K + 2), dtype=torch.uint8, device=dev)
+        r_out_off = torch.empty(8 * (n + 1), dtype=torch.uint8, device=dev)
+        csb = fc.scratch_bytes(n)
+        cscratch = torch.empty(csb, dtype=torch.uint8, device=dev)
+        gathered = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        grec = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        payload = [int(counts[k]) * (fixed_part[k] - 4) + sum(int(o[-1]) for o in qoffs[k] if o is not None) if var[k] else 0
+                   for k in range(K)]
+        vsb = max([p.var_scratch_bytes(int(counts[k]), payload[k]) for k, p in enumerate(req) if var[k]])
+        vscratch = torch.empty(vsb + 16, dtype=torch.uint8, device=dev)
+
+        def route():
+            fc.classify(buf, total, offs, n, r_cls, r_idx, r_counts, r_out_off, cscratch, csb, stream=s)
+            for k, p in enumerate(req):
+                c = int(counts[k])
+                if not c:
+                    continue
+                idx = r_idx.data_ptr() + 4 * k * n
+                if var[k]:
+                    FrameClassifier.gather_var(buf, offs, idx, c, gathered, grec, cscratch, csb, stream=s)
+                    p.unpack_var(gathered, payload[k], c, grec, back[k], boffs[k], vscratch, vsb, st, stream=s)
+                    continue
+                src = buf
+                if c != n:
+                    FrameClassifier.gather(buf, offs, idx, c, p.record_bytes, gathered, stream=s)
+                    src = gathered
+                p.unpack(src, c * p.record_bytes, c, back[k], stream=s)
+
+        clear()
+        route()
+        torch.cuda.synchronize()
+        route_ok = torch.equal(r_cls[:n], d_method) and not bool(st[:4].any())
+        for k, p in enumerate(req):  # the buckets' order is unspecified: lengths and fixed columns as multisets
+            for f, kind in enumerate(p.schema.kinds):
+                if kind == STRING:
+                    a, b = qoffs[k][f], boffs[k][f]
+                    route_ok = route_ok and int(b[-1]) == int(a[-1])
+                    route_ok = route_ok and torch.equal((a[1:] - a[:-1]).sort().values, (b[1:] - b[:-1]).sort().values)
+                else:
+                    used = int(counts[k]) * oracle.KIND_SIZE[kind]
+                    dt = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[oracle.KIND_SIZE[kind]]
+                    route_ok = route_ok and torch.equal(qcols[k][f][:used].view(dt).sort().values,
+                                                        back[k][f][:used].view(dt).sort().values)
+
+        def ev(fn):
+            a = torch.cuda.Event(enable_timing=True)
+            b = torch.cuda.Event(enable_timing=True)
+            a.record(s)
+            fn()
+            b.record(s)
+            torch.cuda.synchronize()
+            return a.elapsed_time(b) / 1e3
+
+        for _ in range(3):
+            route()
+            decode()
+        t_new, t_route = [], []
+        for _ in range(args.reps):
+            t_new.append(ev(decode))
+            t_route.append(ev(route))
+        clear()
+        t = timeit(decode)
+        torch.cuda.synchronize()
+        ok = ok and same()
+        fields = sum(int(c) * sum(oracle.KIND_SIZE[kind] for kind in p.schema.kinds) for c, p in zip(counts, req))
+        nstr_total = sum(int(counts[k]) + 1 for k, p in enumerate(req) for kind in p.schema.kinds if kind == STRING)
+        alg = total + fields + chars + 8 * nstr_total + 5 * n + nb
+        nv = sum(var)
+        rows.append({"case": f"{name}_decode", "mixed": True, "calls": n, "plans": K, "alg_bytes": alg,
+                     "us": round(t * 1e6, 2), "GBps": round(alg / t / 1e9, 1), "frac": round(alg / t / 8e12, 4),
+                     "parity_ok": bool(ok), "route_parity_ok": bool(route_ok), "frame_bytes": round(total / n, 1),
+                     "index_bytes": nb, "ab_new": spread(t_new), "ab_route": spread(t_route),
+                     "new_name": "unpack_requests_mixed_var",
+                     "route_name": f"classify + {nv} x (gather_var + unpack_var) + {K - nv} x (gather + unpack)"})
+
     def aos_case(name, sch, n, vptr=True):
         """Records as C-aligned structs behind an 8-byte vtable slot (a C++
         std::vector<T> of srpc messages copied to the device; vptr=False: a
@@ -882,6 +1098,13 @@ def main():
     requests_case(f"requests_k1_square_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER)], NM)
     requests_case(f"requests_k4_calculator_{mtag}", [(SQUARE_METHOD, NUMBER, NUMBER), (svc + "add", two, NUMBER),
                                                      (svc + "subtract", two, NUMBER), (svc + "multiply", two, NUMBER)], NM)
+    mp = Schema.of("multiple_primitives", ("arg1", "int8"), ("arg2", "char"), ("arg3", "int64"), ("arg4", "string"))
+    echo = ("Echo_servicer::echo", mp, mp)
+    calc = [(SQUARE_METHOD, NUMBER, NUMBER), (svc + "add", two, NUMBER), (svc + "subtract", two, NUMBER),
+            (svc + "multiply", two, NUMBER)]
+    for maxlen in (16, 300):
+        requests_var_case(f"requests_var_k1_echo_0-{maxlen}_{mtag}", [echo], NM, maxlen)
+        requests_var_case(f"requests_var_k5_calculator_echo_0-{maxlen}_{mtag}", calc + [echo], NM, maxlen)
     aos_case("quad_aos_16M", QUAD, N)
     aos_case("quad_aos_plain_16M", QUAD, N, vptr=False)
     aos_case("all_kinds_aos_16M", Schema.of("all_kinds", ("a", "bool"), ("b", "int8"), ("c", "char"),
