@@ -33,6 +33,11 @@
 // the case where neither has.  A method's plans are built once (one entry, one
 // cache) whichever form uses it.
 //
+// `call_records` is `call` from and into device arrays of the caller's own
+// structs (fixed-size Req and Resp, sizeof(Resp) <= 256): the same chunk loop
+// with srpc_gpu_pack_aos as its pack call and srpc_frames_unpack_replies_aos as
+// its decode call, so nothing is transposed on the host or on the device.
+//
 // `call_mixed` takes an ordered sequence of calls over up to 16 fixed-size
 // methods (a trace replayed against a stateful service, a pipeline whose calls
 // depend on their order): d_method[i] names call i's leg (its method, columns
@@ -165,7 +170,32 @@ public:
     std::vector<response_t<Resp>> call(std::string const& method, std::vector<Req> const& reqs) {
         check(hipSetDevice(_dev));
         // string schemas are refused before anything is allocated
-        return call_records<Req, Resp>(plans<Req, Resp>(method), method, reqs, nullptr);
+        return call_host_records<Req, Resp>(plans<Req, Resp>(method), method, reqs, nullptr);
+    }
+
+    /// n calls of `method` from and into device arrays of the caller's own
+    /// structs (fixed-size Req and Resp; a string schema or sizeof(Resp) > 256
+    /// throws plan_error SRPC_E_UNSUPPORTED before anything is allocated):
+    /// call i takes its request from d_reqs[i] (srpc_gpu_pack_aos over
+    /// leaf_offsets<Req>()) and leaves its reply in d_resps[i], written whole by
+    /// srpc_frames_unpack_replies_aos -- the reply's leaves (zero unless the
+    /// reply is a full frame, as `call` gives zero fields; unanswered calls
+    /// likewise, with RPC_ERR_RECV_TIMEOUT), every other byte from `proto`.
+    /// d_resps is 16-byte aligned, d_reqs naturally.  No transpose, on the host
+    /// or on the device; chunks, hooks and counts are `call`'s.  Device code
+    /// must not call a virtual function on a d_resps[i]: its vtable slot holds
+    /// proto's host pointer.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    call_stats call_records(std::string const& method, const Req* d_reqs, uint64_t n, Resp* d_resps, uint8_t* d_codes,
+                            const Resp& proto = Resp{}, hipStream_t stream = nullptr) {
+        check(hipSetDevice(_dev));
+        if (sizeof(Resp) > 256) throw plan_error("batch_client::call_records (sizeof(Resp) > 256)", SRPC_E_UNSUPPORTED);
+        entry& e = plans<Req, Resp>(method);  // string schemas are refused here, before a plan is built
+        ensure(e.fin, e.fout);
+        const std::vector<uint32_t> qo = leaf_offsets<Req>(), so = leaf_offsets<Resp>();
+        const record_io rec{reinterpret_cast<const uint8_t*>(d_reqs), sizeof(Req), qo.data(),
+                            reinterpret_cast<uint8_t*>(d_resps), sizeof(Resp), so.data(), &proto};
+        return run_calls(e, nullptr, nullptr, n, nullptr, nullptr, nullptr, d_codes, stream, &rec);
     }
 
     /// n calls of a method whose Req and/or Resp has string fields.  The
@@ -204,7 +234,7 @@ public:
     std::vector<response_t<Resp>> call_var(std::string const& method, std::vector<Req> const& reqs,
                                            var_call_limits lim = {}) {
         check(hipSetDevice(_dev));
-        return call_records<Req, Resp>(any_plans<Req, Resp>(method), method, reqs, &lim);
+        return call_host_records<Req, Resp>(any_plans<Req, Resp>(method), method, reqs, &lim);
     }
 
     /// One method of a call_mixed batch: `calls` calls of `method`, call r of
@@ -572,14 +602,28 @@ private:
         return l;
     }
 
-    /// The chunk loop of call and call_var over a staging already sized.  A
-    /// side without strings (for `call`, both) is packed by srpc_gpu_pack and
-    /// decoded by srpc_frames_unpack_replies; the string arguments of such a
-    /// side are not read.
+    /// call_records' struct arrays, in place of run_calls' columns.
+    struct record_io {
+        const uint8_t* d_reqs;
+        uint64_t req_stride;
+        const uint32_t* req_offs;  // leaf_offsets<Req>()
+        uint8_t* d_resps;
+        uint64_t resp_stride;
+        const uint32_t* resp_offs;
+        const void* fill;          // resp_stride host bytes: the proto
+    };
+
+    /// The chunk loop of call, call_var and call_records over a staging already
+    /// sized.  A side without strings (for `call`, both) is packed by
+    /// srpc_gpu_pack and decoded by srpc_frames_unpack_replies; the string
+    /// arguments of such a side are not read.  With `rec` (fixed sides only) the
+    /// columns are not read either: the pack call is srpc_gpu_pack_aos over the
+    /// chunk's slice of the request structs and the decode call
+    /// srpc_frames_unpack_replies_aos over its slice of the reply structs.
     call_stats run_calls(entry& e, void* const* d_req_cols, const uint64_t* const* d_req_str_offs, uint64_t n,
                          void* const* d_resp_cols, uint64_t* const* d_resp_str_offs, const uint64_t* resp_cap,
-                         uint8_t* d_codes, hipStream_t stream) {
-        const size_t nq = e.req_size.size(), ns = e.resp_size.size();
+                         uint8_t* d_codes, hipStream_t stream, const record_io* rec = nullptr) {
+        const size_t nq = rec ? 0 : e.req_size.size(), ns = rec ? 0 : e.resp_size.size();
         call_stats st;
         st.calls = n;
         std::vector<const void*> rq(nq);
@@ -611,6 +655,11 @@ private:
                     total = _s.h_ends[0] + 4 * m;
                     if (total > _out_cap || _s.h_status->flags)
                         throw plan_error("batch_client::call_var (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
+                } else if (rec) {
+                    total = m * e.fin;
+                    check_srpc(srpc_gpu_pack_aos(e.req->get(), rec->d_reqs + lo * rec->req_stride, rec->req_stride,
+                                                 rec->req_offs, m, _s.d_out, total, stream),
+                               "srpc_gpu_pack_aos");
                 } else {
                     total = m * e.fin;
                     check_srpc(srpc_gpu_pack(e.req->get(), rq.data(), m, _s.d_out, total, stream), "srpc_gpu_pack");
@@ -643,6 +692,12 @@ private:
                     for (uint32_t t = 0; t < e.resp_nstr; ++t)
                         check(hipMemcpyAsync(_s.h_soffs + t * (_max + 1), _s.d_soffs[t], 8 * (nf + 1), hipMemcpyDeviceToHost,
                                              stream));
+                } else if (rec) {
+                    check_srpc(srpc_frames_unpack_replies_aos(e.resp->get(), _s.d_in, w.walked,
+                                                              uniform ? nullptr : _s.d_offs.p, nf,
+                                                              rec->d_resps + lo * rec->resp_stride, rec->resp_stride,
+                                                              rec->resp_offs, rec->fill, d_codes + lo, _s.d_status, stream),
+                               "srpc_frames_unpack_replies_aos");
                 } else {
                     check_srpc(srpc_frames_unpack_replies(e.resp->get(), _s.d_in, w.walked, uniform ? nullptr : _s.d_offs.p,
                                                           nf, rs.data(), d_codes + lo, _s.d_status, stream),
@@ -652,6 +707,7 @@ private:
                 check(hipMemcpyAsync(_s.h_status, _s.d_status, sizeof(srpc_unpack_status), hipMemcpyDeviceToHost, stream));
             }
             if (nf < m) {  // no reply: RPC_ERR_RECV_TIMEOUT, zero fields (empty strings: below)
+                if (rec) unanswered_records(e, *rec, lo + nf, m - nf, d_codes, stream);  // writes their codes too: first
                 check(hipMemsetAsync(d_codes + lo + nf, RPC_ERR_RECV_TIMEOUT, m - nf, stream));
                 for (size_t f = 0; f < ns; ++f)
                     if (e.resp_size[f])
@@ -706,11 +762,38 @@ private:
         return st;
     }
 
+    /// call_records' structs of calls [first, first + k) the peer never answered:
+    /// the proto with zero leaves.  That struct is what the decode makes of a
+    /// frame that is not there (a BOUNDS row of its table), so it runs in its
+    /// uniform mode over an empty stream, without a status; the codes it writes
+    /// are overwritten by the caller.  The decode wants a 16-byte
+    /// aligned array: the structs before the first aligned one (fewer than 16)
+    /// are assembled on the host.
+    void unanswered_records(entry& e, record_io const& rec, uint64_t first, uint64_t k, uint8_t* d_codes,
+                            hipStream_t stream) {
+        const uint64_t S = rec.resp_stride;
+        std::vector<uint8_t> one(static_cast<const uint8_t*>(rec.fill), static_cast<const uint8_t*>(rec.fill) + S);
+        for (size_t f = 0; f < e.resp_size.size(); ++f) std::memset(one.data() + rec.resp_offs[f], 0, e.resp_size[f]);
+        uint64_t head = 0;  // structs before the first 16-byte aligned one
+        while (head < k && ((first + head) * S) % 16) ++head;
+        if (head) {
+            _unanswered.resize(head * S);
+            for (uint64_t i = 0; i < head; ++i) std::memcpy(_unanswered.data() + i * S, one.data(), S);
+            check(hipMemcpyAsync(rec.d_resps + first * S, _unanswered.data(), head * S, hipMemcpyHostToDevice, stream));
+        }
+        if (head < k) {
+            check_srpc(srpc_frames_unpack_replies_aos(e.resp->get(), _s.d_in, 0, nullptr, k - head,
+                                                      rec.d_resps + (first + head) * S, S, rec.resp_offs, one.data(),
+                                                      d_codes + first + head, nullptr, stream),
+                       "srpc_frames_unpack_replies_aos");
+        }
+    }
+
     /// The host-record forms: the records' columns to the device, the call
     /// (`call` without limits, `call_var` with), the reply columns back.
     template <SrpcMessage Req, SrpcMessage Resp>
-    std::vector<response_t<Resp>> call_records(entry& e, std::string const& method, std::vector<Req> const& reqs,
-                                               const var_call_limits* lim) {
+    std::vector<response_t<Resp>> call_host_records(entry& e, std::string const& method,
+                                                    std::vector<Req> const& reqs, const var_call_limits* lim) {
         const uint64_t n = reqs.size();
         host_columns<Req> in;
         in.scatter(reqs);
@@ -928,6 +1011,7 @@ private:
     std::map<std::string, entry> _plans;
     std::vector<uint8_t> _kept;
     call_stats _last;
+    std::vector<uint8_t> _unanswered;  // call_records: the first structs of an unanswered tail, until they are copied
     uint64_t _out_cap = 0, _in_cap = 0, _have = 0;
     staging _s;
 };

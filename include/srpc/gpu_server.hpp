@@ -25,6 +25,10 @@
 // field) -> srpc_gpu_pack_var -> srpc_frames_offsets (the reply stream's
 // offsets, now that the responses' sizes are known) ->
 // srpc_frames_scatter_var (`BE32 len | response` into request order).
+// Methods registered with register_record_method take the same steps with a
+// handler over arrays of the caller's own structs: srpc_gpu_unpack_aos_fill into
+// a Req array -> handler -> srpc_gpu_pack_aos from a Resp array (bucket route
+// only).
 // A frame no registered method matches (another method, a corrupt header or
 // string length, trailing bytes) is answered on the CPU by an ordinary
 // srpc::server, in its place in the reply order; only those frames leave the
@@ -256,6 +260,8 @@ public:
             if (m->var) continue;  // released with the batch buffers
             for (void* p : m->req_cols) (void)hipFree(p);
             for (void* p : m->resp_cols) (void)hipFree(p);
+            if (m->d_reqs) (void)hipFree(m->d_reqs);
+            if (m->d_resps) (void)hipFree(m->d_resps);
         }
         (void)hipStreamDestroy(_s);
     }
@@ -288,6 +294,63 @@ public:
         });
         _m.push_back(std::move(m));
         release();  // buffers are sized for the largest frames on the next serve
+    }
+
+    /// handler(d_reqs, d_resps, n, stream): a method over a batch of the
+    /// caller's own structs on the device -- d_reqs is n Req objects, d_resps n
+    /// Resp objects (the kernel a servicer ported from the reference wants: one
+    /// thread per Req, write one Resp).
+    using record_handler_t = std::function<int(const void* d_reqs, void* d_resps, uint64_t n, hipStream_t)>;
+
+    /// register_method for a handler over struct arrays (fixed-size Req and
+    /// Resp; a string schema throws plan_error SRPC_E_UNSUPPORTED).  The same
+    /// frames on the wire and the same bucket route, with the AoS kernels in
+    /// place of the column ones: classify -> gather -> srpc_gpu_unpack_aos_fill
+    /// (framed request plan) into a Req array -> handler ->
+    /// srpc_gpu_pack_aos (framed response plan) from a Resp array -> scatter.
+    /// Every byte of a d_reqs[i] that no leaf covers is a Req{}'s (for
+    /// sizeof(Req) > 256 the array is filled with Req{} once and
+    /// srpc_gpu_unpack_aos writes the leaves); the Resp array is zeroed when it
+    /// is allocated and only its leaves are read, so the handler writes the
+    /// leaves and nothing else matters.  Handlers must not call a virtual
+    /// function on these objects: a vtable slot holds a host pointer (Req) or
+    /// zero (Resp).  Record methods and column methods mix freely in one server.
+    /// Bucket route only: with a record method registered, serve_connection
+    /// throws plan_error(SRPC_E_UNSUPPORTED) in either ordered mode.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    void register_record_method(std::string method, record_handler_t handler) {
+        if (_m.size() >= SRPC_FRAMES_MAX_PLANS) throw plan_error("batch_server::register_record_method", SRPC_E_UNSUPPORTED);
+        for (const auto& kinds : {flat_kinds<Req>(), flat_kinds<Resp>()})
+            for (int32_t k : kinds)
+                if (k == SRPC_KIND_STRING)
+                    throw plan_error("batch_server::register_record_method (string schema)", SRPC_E_UNSUPPORTED);
+        check(hipSetDevice(_dev));
+        auto m = std::make_unique<method_entry>();
+        m->rec = true;
+        m->name = std::move(method);
+        m->rhandler = std::move(handler);
+        m->in = std::make_unique<raw_plan>(flat_kinds<Req>(), framed_request_prefix<Req>(m->name), _dev);
+        m->out = std::make_unique<raw_plan>(flat_kinds<Resp>(), framed_response_prefix<Resp>(RPC_SUCCESS), _dev);
+        m->fin = m->in->record_bytes();
+        m->fout = m->out->record_bytes();
+        m->in_kinds = flat_kinds<Req>();
+        m->out_kinds = flat_kinds<Resp>();
+        m->req_stride = sizeof(Req);
+        m->resp_stride = sizeof(Resp);
+        m->req_loffs = leaf_offsets<Req>();
+        m->resp_loffs = leaf_offsets<Resp>();
+        const Req proto{};
+        m->req_fill.assign(reinterpret_cast<const uint8_t*>(&proto), reinterpret_cast<const uint8_t*>(&proto) + sizeof(Req));
+        m->d_reqs = alloc(_max * sizeof(Req) + 16);
+        m->d_resps = alloc(_max * sizeof(Resp) + 16);
+        check(hipMemset(m->d_resps, 0, _max * sizeof(Resp) + 16));
+        if (sizeof(Req) > kRecordFillMax) {  // past the fill call's limit: every struct a Req{} once, leaves per batch
+            std::vector<uint8_t> all(_max * sizeof(Req));
+            for (uint64_t i = 0; i < _max; ++i) std::memcpy(all.data() + i * sizeof(Req), &proto, sizeof(Req));
+            check(hipMemcpy(m->d_reqs, all.data(), all.size(), hipMemcpyHostToDevice));
+        }
+        _m.push_back(std::move(m));
+        release();
     }
 
     /// Serve `method` whose request and/or response has string fields: frames
@@ -424,6 +487,8 @@ public:
         if (_ordered && !_ordered_var && any_var_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a string-bodied method)",
                              SRPC_E_UNSUPPORTED);
+        if (_ordered && any_record_method())
+            throw plan_error("batch_server::serve_connection (ordered mode with a record method)", SRPC_E_UNSUPPORTED);
         check(hipSetDevice(_dev));
         ensure();
         batch_stats st;
@@ -548,6 +613,14 @@ private:
         std::unique_ptr<raw_plan> ord_in, ord_out;
         std::vector<const uint64_t*> c_req_offs, c_resp_offs;
         std::vector<uint64_t> req_scap;             // bytes of every request column
+        // struct-array methods (register_record_method): no columns; one array per side
+        bool rec = false;
+        record_handler_t rhandler;
+        uint64_t req_stride = 0, resp_stride = 0;   // sizeof(Req), sizeof(Resp)
+        std::vector<uint32_t> req_loffs, resp_loffs; // leaf_offsets<Req>(), <Resp>()
+        std::vector<uint8_t> req_fill;              // a Req{}'s bytes
+        void* d_reqs = nullptr;
+        void* d_resps = nullptr;
         bool in_str() const { return std::find(req_string.begin(), req_string.end(), true) != req_string.end(); }
         bool out_str() const { return std::find(resp_string.begin(), resp_string.end(), true) != resp_string.end(); }
     };
@@ -596,6 +669,30 @@ private:
         for (auto const& m : _m)
             if (m->var) return true;
         return false;
+    }
+    bool any_record_method() const {
+        for (auto const& m : _m)
+            if (m->rec) return true;
+        return false;
+    }
+    static constexpr uint64_t kRecordFillMax = 256;  // struct bytes srpc_gpu_unpack_aos_fill takes
+
+    /// A record method's three steps on n contiguous request frames at src:
+    /// decode into its Req array (status slot st), handler, framed responses from
+    /// its Resp array to dst.  Returns the decode's status (positive for the
+    /// warm-up's zero frame); the handler and the pack throw.
+    int run_record_method(method_entry& m, const uint8_t* src, uint64_t n, srpc_unpack_status* st, uint8_t* dst,
+                          const char* what) {
+        const int rc = m.req_stride <= kRecordFillMax
+                           ? srpc_gpu_unpack_aos_fill(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
+                                                      m.req_loffs.data(), m.req_fill.data(), st, _s)
+                           : srpc_gpu_unpack_aos(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
+                                                 m.req_loffs.data(), st, _s);
+        if (rc < 0) return rc;
+        check_srpc(m.rhandler(m.d_reqs, m.d_resps, n, _s), what);
+        check_srpc(srpc_gpu_pack_aos(m.out->get(), m.d_resps, m.resp_stride, m.resp_loffs.data(), n, dst, n * m.fout, _s),
+                   "srpc_gpu_pack_aos");
+        return rc;
     }
 
     /// A string method's device buffers for batches of _max frames in _cap bytes.
@@ -779,17 +876,24 @@ private:
                                               static_cast<const uint32_t*>(_d_index), 1, static_cast<uint32_t>(m->fin),
                                               static_cast<uint8_t*>(_d_gather), _s),
                            "srpc_frames_gather");
-                (void)srpc_gpu_unpack(m->in->get(), static_cast<const uint8_t*>(_d_gather), m->fin, 1,
-                                      m->req_cols.data(), _d_status + k, _s);  // a prefix error on the zero frame: expected
-                // the handler's own kernels load their code object on first use
-                // too: it runs on the one zero record (its output is never sent)
-                check_srpc(m->handler(m->req_cols.data(), m->resp_cols.data(), 1, _s), "batch handler (warm-up)");
-                check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_out), m->fout,
-                                         _s),
-                           "srpc_gpu_pack");
-                check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_resp), m->fout,
-                                         _s),
-                           "srpc_gpu_pack");
+                if (m->rec) {  // the same on its struct arrays, both destinations
+                    for (void* dst : {_d_out, _d_resp})
+                        check_srpc(run_record_method(*m, static_cast<const uint8_t*>(_d_gather), 1, _d_status + k,
+                                                     static_cast<uint8_t*>(dst), "batch handler (warm-up)"),
+                                   "srpc_gpu_unpack_aos");
+                } else {
+                    (void)srpc_gpu_unpack(m->in->get(), static_cast<const uint8_t*>(_d_gather), m->fin, 1,
+                                          m->req_cols.data(), _d_status + k, _s);  // a prefix error on the zero frame: expected
+                    // the handler's own kernels load their code object on first use
+                    // too: it runs on the one zero record (its output is never sent)
+                    check_srpc(m->handler(m->req_cols.data(), m->resp_cols.data(), 1, _s), "batch handler (warm-up)");
+                    check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_out), m->fout,
+                                             _s),
+                               "srpc_gpu_pack");
+                    check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_resp), m->fout,
+                                             _s),
+                               "srpc_gpu_pack");
+                }
                 check_srpc(srpc_frames_scatter(static_cast<const uint8_t*>(_d_resp),
                                                static_cast<const uint32_t*>(_d_index), 1, static_cast<uint32_t>(m->fout),
                                                static_cast<const uint64_t*>(_d_out_off), static_cast<uint8_t*>(_d_out),
@@ -1256,14 +1360,19 @@ private:
                            "srpc_frames_gather");
                 src = static_cast<const uint8_t*>(_d_gather);
             }
-            check_srpc(srpc_gpu_unpack(m.in->get(), src, n * m.fin, n, m.req_cols.data(), _d_status + k, _s),
-                       "srpc_gpu_unpack");
-            mark("unpack");
-            check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s), "batch handler");
-            mark("handler");
             auto* dst = static_cast<uint8_t*>(whole ? _d_out : _d_resp);
-            check_srpc(srpc_gpu_pack(m.out->get(), m.resp_cols.data(), n, dst, n * m.fout, _s), "srpc_gpu_pack");
-            mark("pack");
+            if (m.rec) {
+                check_srpc(run_record_method(m, src, n, _d_status + k, dst, "batch handler"), "srpc_gpu_unpack_aos");
+                mark("record method");
+            } else {
+                check_srpc(srpc_gpu_unpack(m.in->get(), src, n * m.fin, n, m.req_cols.data(), _d_status + k, _s),
+                           "srpc_gpu_unpack");
+                mark("unpack");
+                check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s), "batch handler");
+                mark("handler");
+                check_srpc(srpc_gpu_pack(m.out->get(), m.resp_cols.data(), n, dst, n * m.fout, _s), "srpc_gpu_pack");
+                mark("pack");
+            }
             if (!whole)
                 check_srpc(srpc_frames_scatter(dst, d_idx + static_cast<uint64_t>(k) * nf, n,
                                                static_cast<uint32_t>(m.fout), d_out_off, static_cast<uint8_t*>(_d_out),

@@ -523,6 +523,58 @@ int srpc_frames_unpack_replies(const srpc_plan* reply_plan, const uint8_t* d_buf
 /* Testing hook: frames per workgroup tile for this reply plan. */
 int srpc_frames_replies_per_tile(const srpc_plan* reply_plan, uint32_t* out);
 
+/* ---- framed reply batches into structs (client side; added within ABI 8) ------
+ * srpc_frames_unpack_replies with an array of the caller's own structs in place
+ * of the columns: the reply of call i is decoded straight into struct i, as a
+ * generated stub of the reference returns a response_t<Resp>.
+ *
+ * Frames: the contract of srpc_frames_unpack_replies, unchanged -- the same
+ * reply_plan (a fixed-size plan behind a framed response prefix, code byte
+ * ignored), the same frame convention, d_offs == NULL the uniform mode, the
+ * per-frame table above, SRPC_REPLY_NO_CODE, and SRPC_ERR_BOUNDS for a short
+ * uniform stream.  d_codes[i], the status flags and first_bad_record are
+ * identical to the column call's on the same input.
+ *
+ * Structs: field_offsets and record_stride as for srpc_gpu_unpack_aos_fill
+ * (leaf f of struct i at d_records + i * record_stride + field_offsets[f];
+ * natural alignment, no two leaves sharing a byte, record_stride <= 256).
+ * h_fill is record_stride host bytes (e.g. the image of a Resp{}), copied
+ * during the call.  Every one of the nframes structs is written whole: a full
+ * frame gives its leaf fields the frame's values, any other frame gives zero
+ * leaf fields (as the column call gives zero fields), and in both cases every
+ * byte no leaf covers comes from h_fill.  No byte at or past d_records +
+ * nframes * record_stride is written, and the old array is never read.
+ *
+ * Refused with nothing launched, in this order:
+ *   1. SRPC_E_INVALID: a NULL reply_plan, d_records (nframes > 0),
+ *      field_offsets, h_fill or d_codes; record_stride == 0; buf_len >= 4 GiB
+ *      (checked before the plan is read);
+ *   2. SRPC_E_UNSUPPORTED: a string plan, a prefix under 5 bytes, or
+ *      record_stride > 256;
+ *   3. SRPC_E_INVALID: overlapping leaves, or a leaf past the stride;
+ *   4. SRPC_E_ALIGN: a misaligned d_buf (16) or d_records (16), or an offset or
+ *      the stride against its field's size.
+ * No byte outside [d_buf, d_buf + buf_len) is read; the call is stream-ordered,
+ * allocates nothing, waits on nothing and can be captured.
+ *
+ * One kernel, the column call's with its last step replaced: a workgroup
+ * stages the span of R consecutive frames into LDS and judges one frame per
+ * lane; then one lane per 16-byte piece of the tile's structs assembles that
+ * piece -- leaf bytes from the image or zero, the rest from an LDS copy of
+ * h_fill, through a per-struct-byte source table in LDS -- and stores it whole
+ * (the array's last piece bytewise when nframes * record_stride is no multiple
+ * of 16).  R = 16 * max(1, (16384 - 4 * S16) / (16 F)), S16 = record_stride
+ * rounded up to 16: the column call's rule with the table and the fill taken
+ * out of the image's bytes, so image + table + fill stay within the 16 KiB the
+ * column kernel's image may take and as many workgroups are resident. */
+int srpc_frames_unpack_replies_aos(const srpc_plan* reply_plan, const uint8_t* d_buf, uint64_t buf_len,
+                                   const uint32_t* d_offs, uint64_t nframes,
+                                   void* d_records, uint64_t record_stride, const uint32_t* field_offsets,
+                                   const void* h_fill, uint8_t* d_codes,
+                                   srpc_unpack_status* d_status, void* stream);
+/* Testing hook: frames per workgroup tile for this plan and stride. */
+int srpc_frames_replies_aos_per_tile(const srpc_plan* reply_plan, uint64_t record_stride, uint32_t* out);
+
 /* ---- framed reply batches with string fields (client side; added within ABI 8) --
  * The reply stream of a batch of calls to a method whose response has
  * std::string members (the reference's stub: unpack_response<R> over a string
@@ -998,7 +1050,8 @@ int srpc_gpu_unpack_host(const srpc_plan* plan, const uint8_t* h_wire, uint64_t 
 
 /* Measurement hook (bench.py): the data-path kernels launched by the NEXT
  * srpc_gpu_pack / _unpack / _pack_var / _unpack_var /
- * srpc_frames_unpack_replies / _unpack_replies_var / srpc_frames_mixed_index /
+ * srpc_frames_unpack_replies / _unpack_replies_aos / _unpack_replies_var /
+ * srpc_frames_mixed_index /
  * _pack_requests_mixed / _unpack_replies_mixed / _unpack_requests_mixed /
  * _pack_requests_mixed_var / _unpack_replies_mixed_var /
  * _unpack_requests_mixed_var call made on this host

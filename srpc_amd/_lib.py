@@ -86,6 +86,8 @@ SIGNATURES = {
     "srpc_frames_offsets": (C.c_int, [_vp, _vp, C.c_int, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_unpack_replies": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "srpc_frames_replies_per_tile": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "srpc_frames_unpack_replies_aos": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "srpc_frames_replies_aos_per_tile": (C.c_int, [_vp, _u64, C.POINTER(C.c_uint32)]),
     "srpc_frames_replies_var_scratch_bytes": (C.c_int, [_vp, _u64, C.POINTER(_u64)]),
     "srpc_frames_unpack_replies_var": (C.c_int, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_replies_var_tile": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

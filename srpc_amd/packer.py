@@ -197,6 +197,29 @@ class GpuPacker:
         check(_lib.lib().srpc_frames_replies_per_tile(self._h, C.byref(out)), "srpc_frames_replies_per_tile")
         return out.value
 
+    def unpack_replies_aos(self, buf, buf_len: int, offs, nframes: int, records, record_stride: int,
+                           field_offsets: Sequence[int], fill: bytes, codes, status=None, stream=None) -> int:
+        """As unpack_replies, straight into a device array of structs (async):
+        every one of the nframes structs is written whole, its leaf fields from
+        the frame (zero unless the frame is full), every other byte from `fill`
+        (record_stride bytes, e.g. a T{} image; at most 256).  Returns SRPC_OK
+        or SRPC_ERR_BOUNDS."""
+        if len(fill) != record_stride:
+            raise ValueError("fill must be record_stride bytes")
+        hb = C.create_string_buffer(bytes(fill), record_stride)
+        return check(_lib.lib().srpc_frames_unpack_replies_aos(self._h, _dptr(buf), buf_len, _dptr(offs), nframes,
+                                                               _dptr(records), record_stride,
+                                                               self._offsets(field_offsets), hb, _dptr(codes),
+                                                               _dptr(status), _stream(stream)),
+                     "srpc_frames_unpack_replies_aos")
+
+    def replies_aos_per_tile(self, record_stride: int) -> int:
+        """Frames one workgroup of unpack_replies_aos takes for this stride (testing hook)."""
+        out = C.c_uint32()
+        check(_lib.lib().srpc_frames_replies_aos_per_tile(self._h, record_stride, C.byref(out)),
+              "srpc_frames_replies_aos_per_tile")
+        return out.value
+
     # -- framed reply streams with string fields (client side) ----------------
     def replies_var_scratch_bytes(self, nframes: int) -> int:
         """Device scratch for unpack_replies_var (8-byte aligned)."""
