@@ -304,3 +304,45 @@ private:
 };
 
 }  // namespace srpc::gpu
+
+// Programs built against HIP (batch_client, batch_server) own their device and
+// pinned memory through `buffer`; host-only programs include this header
+// without the HIP headers and do not see it.
+#ifdef __HIP_PLATFORM_AMD__
+#include <hip/hip_runtime_api.h>
+
+#include <utility>
+
+namespace srpc::gpu {
+
+/// Device (or pinned host) memory that frees itself; reads as its pointer.
+template <class T, bool Pinned>
+struct buffer {
+    T* p = nullptr;
+    buffer() = default;
+    buffer(buffer&& o) noexcept : p(o.p) { o.p = nullptr; }
+    buffer& operator=(buffer&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~buffer() { reset(); }
+    void reset() {
+        if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+    }
+    void alloc(uint64_t bytes) {
+        reset();
+        const hipError_t e =
+            Pinned ? hipHostMalloc(reinterpret_cast<void**>(&p), bytes) : hipMalloc(reinterpret_cast<void**>(&p), bytes);
+        if (e != hipSuccess) throw plan_error(hipGetErrorString(e), SRPC_E_HIP);
+    }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+template <class T>
+using device_buffer = buffer<T, false>;
+template <class T>
+using pinned_buffer = buffer<T, true>;
+
+}  // namespace srpc::gpu
+#endif

@@ -485,35 +485,9 @@ private:
         if (rc < 0) throw plan_error(what, rc);
     }
 
-    /// Device (or pinned host) memory that frees itself; reads as its pointer.
-    template <class T, bool Pinned>
-    struct buffer {
-        T* p = nullptr;
-        buffer() = default;
-        buffer(buffer&& o) noexcept : p(o.p) { o.p = nullptr; }
-        buffer& operator=(buffer&& o) noexcept {
-            std::swap(p, o.p);
-            return *this;
-        }
-        ~buffer() { reset(); }
-        void reset() {
-            if (p) (void)(Pinned ? hipHostFree(p) : hipFree(p));
-            p = nullptr;
-        }
-        void alloc(uint64_t bytes) {
-            reset();
-            check(Pinned ? hipHostMalloc(reinterpret_cast<void**>(&p), bytes) : hipMalloc(reinterpret_cast<void**>(&p), bytes));
-        }
-        operator T*() const { return p; }
-        T* operator->() const { return p; }
-    };
-    template <class T>
-    using device_buffer = buffer<T, false>;
-    template <class T>
-    using pinned_buffer = buffer<T, true>;
-
-    /// All of the staging: ensure_bytes sizes the first group, the others are
-    /// created by the forms that need them, and a grow starts from an empty one.
+    /// All of the staging (self-freeing buffers, gpu.hpp): ensure_bytes
+    /// sizes the first group, the others are created by the forms that need
+    /// them, and a grow starts from an empty one.
     struct staging {
         device_buffer<uint8_t> d_out, d_in;
         pinned_buffer<uint8_t> h_out, h_in, h_codes;

@@ -5,15 +5,31 @@
 // pack_response -> send_data.  For streams of requests of methods with
 // fixed-size bodies (Calculator.square: 57-byte frames = u32 BE 53 | 53-byte
 // request), batch_server serves whole batches on the GPU with the same frames
-// on the wire:
+// on the wire.
+//
+// Every batch goes through one skeleton (process_begin / process_end):
 //
 //   socket -> pinned host buffer (the CPU only walks the BE32 frame lengths)
-//   -> H2D -> srpc_frames_classify (each frame against every registered
-//   method's constant `BE32 len | str(method) | str(Req::name)` prefix and
-//   length; per-method buckets; each response's offset in the reply stream)
+//   -> H2D of the frames and their offsets -> the route's steps, which leave
+//   the reply stream in the device's reply buffer, the number of frames that
+//   go to the CPU and where each answer ends -> D2H of the replies (the class
+//   bytes when a frame goes to the CPU, the statuses) -> an event; once it
+//   fired, the GPU's answers are sent in runs with the CPU's in their places.
+//
+// A frame no registered method matches (another method, a corrupt header or
+// string length, trailing bytes) is answered on the CPU by an ordinary
+// srpc::server, in its place in the reply order; only those frames leave the
+// GPU path.  A frame longer than the batch buffer is read on its own and
+// answered the same way.  The routes are the skeleton's middle:
+//
+// The bucket route (the default):
+//
+//   srpc_frames_classify (each frame against every registered method's
+//   constant `BE32 len | str(method) | str(Req::name)` prefix and length;
+//   per-method buckets; each response's offset in the reply stream)
 //   -> per method: srpc_frames_gather -> srpc_gpu_unpack -> user device
 //   handler -> srpc_gpu_pack (`BE32 len | code | str(Resp::name) | body`
-//   frames) -> srpc_frames_scatter into request order -> D2H -> socket.
+//   frames) -> srpc_frames_scatter into request order.
 //
 // A batch of one method skips the gather and scatter (its frames are already
 // the plan's contiguous records).  Methods with string fields
@@ -29,36 +45,34 @@
 // handler over arrays of the caller's own structs: srpc_gpu_unpack_aos_fill into
 // a Req array -> handler -> srpc_gpu_pack_aos from a Resp array (bucket route
 // only).
-// A frame no registered method matches (another method, a corrupt header or
-// string length, trailing bytes) is answered on the CPU by an ordinary
-// srpc::server, in its place in the reply order; only those frames leave the
-// GPU path.  A frame longer than the batch buffer is read on its own and
-// answered the same way.
 //
 // The buckets are filled with atomics: a handler sees its requests in an order
 // that differs from run to run, and no handler sees the order across methods.
-// Ordered mode (set_ordered / set_ordered_handler; fixed-size methods only)
-// serves a batch in arrival order instead:
+// The ordered route (set_ordered / set_ordered_handler; fixed-size methods
+// only) serves a batch in arrival order instead:
 //
-//   H2D -> srpc_frames_unpack_requests_mixed (every frame classified as above
-//   and decoded straight into its method's request columns at its arrival
-//   rank) -> the handlers, or the one ordered handler with each frame's method
-//   and rank -> srpc_frames_pack_requests_mixed over the framed response plans
-//   (the replies in arrival order, nothing for an unknown frame) -> D2H.
+//   srpc_frames_unpack_requests_mixed (every frame classified as above and
+//   decoded straight into its method's request columns at its arrival rank)
+//   -> the handlers, or the one ordered handler with each frame's method and
+//   rank -> srpc_frames_pack_requests_mixed over the framed response plans
+//   (the replies in arrival order, nothing for an unknown frame).
 //
 // No gather, no scatter and no second response buffer, whatever the mix.
 //
-// Ordered mode over string-bodied methods too (set_ordered_var /
-// set_ordered_var_handler) is the same route through the calls that take both
-// plan kinds:
+// The ordered route over string-bodied methods too (set_ordered_var /
+// set_ordered_var_handler) is the same decode, handlers and pack through the
+// calls that take both plan kinds:
 //
-//   H2D -> srpc_frames_unpack_requests_mixed_var (fixed leaves, chars and
-//   offsets of every method at their arrival ranks) -> the handlers (a string
-//   method's var_handler_t on its n = counts[k] requests), or the one ordered
-//   handler -> the string responses' sizes checked on the host against their
-//   columns (a method that overflows is answered on the CPU for this batch) ->
-//   srpc_frames_pack_requests_mixed_var over the response plans with d_method =
-//   d_class -> the total (and, with unknown frames, the offsets) -> D2H.
+//   srpc_frames_unpack_requests_mixed_var (fixed leaves, chars and offsets of
+//   every method at their arrival ranks) -> the handlers (a string method's
+//   var_handler_t on its n = counts[k] requests), or the one ordered handler
+//   -> srpc_frames_pack_requests_mixed_var over the response plans with
+//   d_method = d_class -> the total (and, with unknown frames, the offsets).
+//
+// On both routes that serve string methods the string responses' sizes are
+// checked on the host against their columns before anything reads the chars:
+// a method that overflows is answered on the CPU for this batch, its frames
+// turned into unknown ones (demote_overflowing).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -256,13 +270,6 @@ public:
     batch_server& operator=(batch_server const&) = delete;
     ~batch_server() {
         release();
-        for (auto& m : _m) {
-            if (m->var) continue;  // released with the batch buffers
-            for (void* p : m->req_cols) (void)hipFree(p);
-            for (void* p : m->resp_cols) (void)hipFree(p);
-            if (m->d_reqs) (void)hipFree(m->d_reqs);
-            if (m->d_resps) (void)hipFree(m->d_resps);
-        }
         (void)hipStreamDestroy(_s);
     }
 
@@ -271,29 +278,7 @@ public:
     /// str(Resp::name) | Resp body` frames.  Up to SRPC_FRAMES_MAX_PLANS methods.
     template <SrpcMessage Req, SrpcMessage Resp>
     void register_method(std::string method, handler_t handler) {
-        if (_m.size() >= SRPC_FRAMES_MAX_PLANS) throw plan_error("batch_server::register_method", SRPC_E_UNSUPPORTED);
-        check(hipSetDevice(_dev));
-        auto m = std::make_unique<method_entry>();
-        m->name = std::move(method);
-        m->handler = std::move(handler);
-        m->in = std::make_unique<raw_plan>(flat_kinds<Req>(), framed_request_prefix<Req>(m->name), _dev);
-        m->out = std::make_unique<raw_plan>(flat_kinds<Resp>(), framed_response_prefix<Resp>(RPC_SUCCESS), _dev);
-        m->fin = m->in->record_bytes();
-        m->fout = m->out->record_bytes();
-        m->in_kinds = flat_kinds<Req>();
-        m->out_kinds = flat_kinds<Resp>();
-        Req rq{};
-        for_each_leaf<Req>(rq, [&](const auto& v) {
-            m->req_bytes.push_back(_max * sizeof(v) + 16);
-            m->req_cols.push_back(alloc(m->req_bytes.back()));
-        });
-        Resp rs{};
-        for_each_leaf<Resp>(rs, [&](const auto& v) {
-            m->resp_bytes.push_back(_max * sizeof(v) + 16);
-            m->resp_cols.push_back(alloc(m->resp_bytes.back()));
-        });
-        _m.push_back(std::move(m));
-        release();  // buffers are sized for the largest frames on the next serve
+        add_method<Req, Resp>("batch_server::register_method", std::move(method), false).handler = std::move(handler);
     }
 
     /// handler(d_reqs, d_resps, n, stream): a method over a batch of the
@@ -319,38 +304,15 @@ public:
     /// throws plan_error(SRPC_E_UNSUPPORTED) in either ordered mode.
     template <SrpcMessage Req, SrpcMessage Resp>
     void register_record_method(std::string method, record_handler_t handler) {
-        if (_m.size() >= SRPC_FRAMES_MAX_PLANS) throw plan_error("batch_server::register_record_method", SRPC_E_UNSUPPORTED);
-        for (const auto& kinds : {flat_kinds<Req>(), flat_kinds<Resp>()})
-            for (int32_t k : kinds)
-                if (k == SRPC_KIND_STRING)
-                    throw plan_error("batch_server::register_record_method (string schema)", SRPC_E_UNSUPPORTED);
-        check(hipSetDevice(_dev));
-        auto m = std::make_unique<method_entry>();
-        m->rec = true;
-        m->name = std::move(method);
-        m->rhandler = std::move(handler);
-        m->in = std::make_unique<raw_plan>(flat_kinds<Req>(), framed_request_prefix<Req>(m->name), _dev);
-        m->out = std::make_unique<raw_plan>(flat_kinds<Resp>(), framed_response_prefix<Resp>(RPC_SUCCESS), _dev);
-        m->fin = m->in->record_bytes();
-        m->fout = m->out->record_bytes();
-        m->in_kinds = flat_kinds<Req>();
-        m->out_kinds = flat_kinds<Resp>();
-        m->req_stride = sizeof(Req);
-        m->resp_stride = sizeof(Resp);
-        m->req_loffs = leaf_offsets<Req>();
-        m->resp_loffs = leaf_offsets<Resp>();
+        method_entry& m = add_method<Req, Resp>("batch_server::register_record_method", std::move(method), false, true);
+        m.rec = true;
+        m.rhandler = std::move(handler);
+        m.req_stride = sizeof(Req);
+        m.resp_stride = sizeof(Resp);
+        m.req_loffs = leaf_offsets<Req>();
+        m.resp_loffs = leaf_offsets<Resp>();
         const Req proto{};
-        m->req_fill.assign(reinterpret_cast<const uint8_t*>(&proto), reinterpret_cast<const uint8_t*>(&proto) + sizeof(Req));
-        m->d_reqs = alloc(_max * sizeof(Req) + 16);
-        m->d_resps = alloc(_max * sizeof(Resp) + 16);
-        check(hipMemset(m->d_resps, 0, _max * sizeof(Resp) + 16));
-        if (sizeof(Req) > kRecordFillMax) {  // past the fill call's limit: every struct a Req{} once, leaves per batch
-            std::vector<uint8_t> all(_max * sizeof(Req));
-            for (uint64_t i = 0; i < _max; ++i) std::memcpy(all.data() + i * sizeof(Req), &proto, sizeof(Req));
-            check(hipMemcpy(m->d_reqs, all.data(), all.size(), hipMemcpyHostToDevice));
-        }
-        _m.push_back(std::move(m));
-        release();
+        m.req_fill.assign(reinterpret_cast<const uint8_t*>(&proto), reinterpret_cast<const uint8_t*>(&proto) + sizeof(Req));
     }
 
     /// Serve `method` whose request and/or response has string fields: frames
@@ -362,42 +324,11 @@ public:
     /// the CPU.  Up to SRPC_FRAMES_MAX_STRINGS string fields in Req.
     template <SrpcMessage Req, SrpcMessage Resp>
     void register_var_method(std::string method, var_handler_t handler, var_limits lim = {}) {
-        if (_m.size() >= SRPC_FRAMES_MAX_PLANS) throw plan_error("batch_server::register_var_method", SRPC_E_UNSUPPORTED);
-        check(hipSetDevice(_dev));
-        auto m = std::make_unique<method_entry>();
-        m->var = true;
-        m->name = std::move(method);
-        m->vhandler = std::move(handler);
-        const std::vector<uint8_t> rq = request_prefix<Req>(m->name), rs = response_prefix<Resp>(RPC_SUCCESS);
-        m->in = std::make_unique<raw_plan>(flat_kinds<Req>(), rq, _dev);
-        m->out = std::make_unique<raw_plan>(flat_kinds<Resp>(), rs, _dev);
-        m->req_prefix = rq;
-        m->min_in = rq.size() + min_body_bytes<Req>();
-        m->min_out = rs.size() + min_body_bytes<Resp>();
-        m->fin = std::max<uint64_t>(lim.max_request_bytes, 4 + m->min_in);
-        m->fout = 0;  // response frames vary
-        m->lim = lim;
-        // the ordered route's plans (ensure): a side without strings is a fixed-size plan behind the framed prefix
-        m->in_kinds = flat_kinds<Req>();
-        m->out_kinds = flat_kinds<Resp>();
-        m->framed_in = be32(static_cast<uint32_t>(m->min_in));
-        m->framed_in.insert(m->framed_in.end(), rq.begin(), rq.end());
-        m->framed_out = be32(static_cast<uint32_t>(m->min_out));
-        m->framed_out.insert(m->framed_out.end(), rs.begin(), rs.end());
-        Req rq0{};
-        for_each_leaf<Req>(rq0, [&](const auto& v) {
-            using F = std::remove_cvref_t<decltype(v)>;
-            m->req_string.push_back(std::is_same_v<F, std::string>);
-            m->req_size.push_back(std::is_same_v<F, std::string> ? 0 : sizeof(F));
-        });
-        Resp rs0{};
-        for_each_leaf<Resp>(rs0, [&](const auto& v) {
-            using F = std::remove_cvref_t<decltype(v)>;
-            m->resp_string.push_back(std::is_same_v<F, std::string>);
-            m->resp_size.push_back(std::is_same_v<F, std::string> ? 0 : sizeof(F));
-        });
-        _m.push_back(std::move(m));
-        release();
+        method_entry& m = add_method<Req, Resp>("batch_server::register_var_method", std::move(method), true);
+        m.vhandler = std::move(handler);
+        m.fin = std::max<uint64_t>(lim.max_request_bytes, 4 + m.min_in);
+        m.fout = 0;  // response frames vary
+        m.lim = lim;
     }
 
     /// handler(batch, stream) over a whole batch of every method in arrival
@@ -493,20 +424,19 @@ public:
         ensure();
         batch_stats st;
         const uint64_t cap = _cap;
-        uint64_t have = 0;     // bytes in _h_in
-        uint64_t walked = 0;   // bytes of whole frames found so far (frames _h_offs[0..nf))
+        uint64_t have = 0;     // bytes in h_in
+        uint64_t walked = 0;   // bytes of whole frames found so far (frames h_offs[0..nf))
         uint64_t nf = 0;
         bool eof = false;
-        bool buffered = false;  // whole frames already wait in _h_in: walk them before blocking in recv
+        bool buffered = false;  // whole frames already wait in h_in: walk them before blocking in recv
         int cur = 0;            // the staging slot frames are received into
-        use_slot(cur);
+        uint8_t* h_in = _slots[cur].h_in;
+        uint32_t* h_offs = _slots[cur].h_offs;
         pending pend;
         auto finish = [&] {
             if (!pend.valid) return;
-            use_slot(pend.slot);
             process_end(fd, pend, st);
             pend.valid = false;
-            use_slot(cur);
         };
         while (true) {
             if (!eof && !buffered) {
@@ -515,7 +445,7 @@ public:
                 // cap - have > 0 here: a full buffer is always consumed below,
                 // so recv returning 0 is the peer's orderly shutdown
                 auto t0 = clock::now();
-                ssize_t k = recv(fd, _h_in + have, cap - have, 0);
+                ssize_t k = recv(fd, h_in + have, cap - have, 0);
                 if (k < 0 && errno == EINTR) continue;
                 st.recv_seconds += secs(t0);
                 if (k <= 0) eof = true;
@@ -526,10 +456,10 @@ public:
             uint64_t next_len = 0;
             bool next_hdr = false;
             while (nf < _max && have - walked >= 4) {
-                next_len = 4 + static_cast<uint64_t>(be32_at(_h_in + walked));
+                next_len = 4 + static_cast<uint64_t>(be32_at(h_in + walked));
                 next_hdr = true;
                 if (have - walked < next_len) break;
-                _h_offs[nf++] = static_cast<uint32_t>(walked);
+                h_offs[nf++] = static_cast<uint32_t>(walked);
                 walked += next_len;
                 next_hdr = false;
             }
@@ -546,37 +476,35 @@ public:
             if (!full && !eof && more_pending(fd)) continue;  // fill the batch while data streams in
             if (nf) {
                 if (_nslots == 2) {
-                    pending p = process_begin(nf, walked, st);
-                    p.slot = cur;
+                    pending p = process_begin(cur, nf, walked, st);
                     finish();  // the previous batch's answers: its work ran while this one arrived
                     pend = p;
                     // the rest of the buffer (a cut frame) continues in the other slot
-                    const int nxt = cur ^ 1;
-                    std::memcpy(_slots[nxt].h_in, _h_in + walked, have - walked);
-                    cur = nxt;
-                    use_slot(cur);
+                    cur ^= 1;
+                    std::memcpy(_slots[cur].h_in, h_in + walked, have - walked);
+                    h_in = _slots[cur].h_in;
+                    h_offs = _slots[cur].h_offs;
                 } else {
-                    pending p = process_begin(nf, walked, st);
-                    p.slot = cur;
+                    pending p = process_begin(cur, nf, walked, st);
                     process_end(fd, p, st);
-                    std::memmove(_h_in, _h_in + walked, have - walked);
+                    std::memmove(h_in, h_in + walked, have - walked);
                 }
             } else {
-                std::memmove(_h_in, _h_in + walked, have - walked);
+                std::memmove(h_in, h_in + walked, have - walked);
             }
             have -= walked;
             walked = 0;
             nf = 0;
             if (oversize) {
                 finish();
-                if (!serve_oversize(fd, have, st)) return st;
+                if (!serve_oversize(fd, h_in, have, st)) return st;
                 have = 0;
             }
             // A batch ends at max_batch frames, so the buffer can still hold
             // whole frames (frames shorter than the method's fin) while the
             // peer, having sent everything, waits for their answers: serve
             // them before the next recv, which would block.
-            buffered = have >= 4 && have - 4 >= be32_at(_h_in);
+            buffered = have >= 4 && have - 4 >= be32_at(h_in);
         }
         finish();
         return st;  // bytes of a cut final frame are dropped, as the reference's recv_data does
@@ -584,48 +512,101 @@ public:
 
 private:
     using clock = std::chrono::steady_clock;
+    /// A registered method: what add_method and its register_* built, then the
+    /// device buffers and the pointer tables over them (alloc_method; release).
     struct method_entry {
         std::string name;
+        bool var = false, rec = false;  // register_var_method, register_record_method
         handler_t handler;
+        var_handler_t vhandler;
+        record_handler_t rhandler;
+        // `in` / `out`: framed fixed-size plans, or (var) string plans behind the unframed prefix
         std::unique_ptr<raw_plan> in, out;
         uint64_t fin = 0, fout = 0;
-        std::vector<void*> req_cols, resp_cols;
-        std::vector<uint64_t> req_bytes, resp_bytes;
-        // string-bodied methods (register_var_method); their device buffers are
-        // sized with the batch buffer (ensure / release)
-        bool var = false;
-        var_handler_t vhandler;
-        var_limits lim;
-        std::vector<uint8_t> req_prefix;           // str(method) | str(Req::name)
-        uint64_t min_in = 0, min_out = 0;          // records with empty strings
-        std::vector<bool> req_string, resp_string;
-        std::vector<uint64_t> req_size, resp_size;  // fixed leaves' bytes
-        std::vector<uint64_t*> req_offs, resp_offs; // string leaves' n+1 offsets (nullptr: fixed)
-        uint8_t* resp_wire = nullptr;               // packed responses and their index
-        uint64_t resp_wire_cap = 0;
-        uint64_t* resp_rec = nullptr;
-        uint64_t* h_ends = nullptr;                 // pinned: per response field, offs[0] and offs[n]
-        // ordered mode with string methods (set_ordered_var): the plan kinds the *_mixed_var calls
-        // take, per side -- `in` / `out` where they already are of that kind, else a fixed-size plan
-        // behind the framed prefix -- and the per-leaf tables those calls and the handlers read
         std::vector<int32_t> in_kinds, out_kinds;
-        std::vector<uint8_t> framed_in, framed_out;
+        std::vector<bool> req_string, resp_string;   // per leaf
+        std::vector<uint64_t> req_size, resp_size;   // fixed leaves' bytes (0: a string)
+        uint64_t min_in = 0, min_out = 0;            // records with empty strings
+        std::vector<uint8_t> req_prefix;             // str(method) | str(Req::name)
+        std::vector<uint8_t> framed_in, framed_out;  // BE32(min) | prefix
+        var_limits lim;
+        // ordered mode with string methods: the plan kinds the *_mixed_var calls take, per side --
+        // `in` / `out` where they already are of that kind, else a fixed-size plan behind the framed prefix
         std::unique_ptr<raw_plan> ord_in, ord_out;
-        std::vector<const uint64_t*> c_req_offs, c_resp_offs;
-        std::vector<uint64_t> req_scap;             // bytes of every request column
-        // struct-array methods (register_record_method): no columns; one array per side
-        bool rec = false;
-        record_handler_t rhandler;
-        uint64_t req_stride = 0, resp_stride = 0;   // sizeof(Req), sizeof(Resp)
+        // struct-array methods: no columns; one array per side
+        uint64_t req_stride = 0, resp_stride = 0;    // sizeof(Req), sizeof(Resp)
         std::vector<uint32_t> req_loffs, resp_loffs; // leaf_offsets<Req>(), <Resp>()
-        std::vector<uint8_t> req_fill;              // a Req{}'s bytes
-        void* d_reqs = nullptr;
-        void* d_resps = nullptr;
+        std::vector<uint8_t> req_fill;               // a Req{}'s bytes
+        device_buffer<uint8_t> d_reqs, d_resps;
+        // the columns: per leaf its values or chars, and a string leaf's n+1 offsets
+        std::vector<device_buffer<uint8_t>> req_buf, resp_buf;
+        std::vector<device_buffer<uint64_t>> req_off_buf, resp_off_buf;
+        std::vector<uint64_t> req_bytes, resp_bytes;  // bytes of every column
+        std::vector<uint64_t> req_scap;               // of which a decode may fill
+        // the bucket route's string methods: packed responses and their index, the response offsets' ends
+        device_buffer<uint8_t> resp_wire;
+        uint64_t resp_wire_cap = 0;
+        device_buffer<uint64_t> resp_rec;
+        pinned_buffer<uint64_t> h_ends;               // per response field, offs[0] and offs[n]
+        // the tables the library calls and the handlers read (nullptr offsets: a fixed leaf)
+        std::vector<void*> req_cols, resp_cols;
+        std::vector<const void*> c_resp_cols;
+        std::vector<uint64_t*> req_offs, resp_offs;
+        std::vector<const uint64_t*> c_req_offs, c_resp_offs;
+
         bool in_str() const { return std::find(req_string.begin(), req_string.end(), true) != req_string.end(); }
         bool out_str() const { return std::find(resp_string.begin(), resp_string.end(), true) != resp_string.end(); }
+        void release() {
+            for (auto* v : {&req_buf, &resp_buf}) v->clear();
+            for (auto* v : {&req_off_buf, &resp_off_buf}) v->clear();
+            d_reqs.reset(), d_resps.reset(), resp_wire.reset(), resp_rec.reset(), h_ends.reset();
+            ord_in.reset(), ord_out.reset();
+        }
     };
-    void memset_cols(std::vector<void*> const& cols, std::vector<uint64_t> const& bytes) {
-        for (size_t f = 0; f < cols.size(); ++f) check(hipMemsetAsync(cols[f], 0, bytes[f], _s));
+
+    /// What every register_* shares: the limit, the plans, the per-leaf tables.
+    /// var: string plans behind the unframed prefix, else framed fixed-size ones.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    method_entry& add_method(const char* what, std::string name, bool var, bool fixed_only = false) {
+        if (_m.size() >= SRPC_FRAMES_MAX_PLANS) throw plan_error(what, SRPC_E_UNSUPPORTED);
+        auto m = std::make_unique<method_entry>();
+        m->in_kinds = flat_kinds<Req>();
+        m->out_kinds = flat_kinds<Resp>();
+        if (fixed_only)
+            for (const auto* kinds : {&m->in_kinds, &m->out_kinds})
+                for (int32_t k : *kinds)
+                    if (k == SRPC_KIND_STRING)
+                        throw plan_error((std::string(what) + " (string schema)").c_str(), SRPC_E_UNSUPPORTED);
+        check(hipSetDevice(_dev));
+        m->name = std::move(name);
+        m->var = var;
+        m->req_prefix = request_prefix<Req>(m->name);
+        const std::vector<uint8_t> rs = response_prefix<Resp>(RPC_SUCCESS);
+        m->min_in = m->req_prefix.size() + min_body_bytes<Req>();
+        m->min_out = rs.size() + min_body_bytes<Resp>();
+        m->framed_in = be32(static_cast<uint32_t>(m->min_in));
+        m->framed_in.insert(m->framed_in.end(), m->req_prefix.begin(), m->req_prefix.end());
+        m->framed_out = be32(static_cast<uint32_t>(m->min_out));
+        m->framed_out.insert(m->framed_out.end(), rs.begin(), rs.end());
+        m->in = std::make_unique<raw_plan>(m->in_kinds, var ? m->req_prefix : m->framed_in, _dev);
+        m->out = std::make_unique<raw_plan>(m->out_kinds, var ? rs : m->framed_out, _dev);
+        m->fin = m->in->record_bytes();
+        m->fout = m->out->record_bytes();
+        Req rq{};
+        for_each_leaf<Req>(rq, [&](const auto& v) {
+            using F = std::remove_cvref_t<decltype(v)>;
+            m->req_string.push_back(std::is_same_v<F, std::string>);
+            m->req_size.push_back(std::is_same_v<F, std::string> ? 0 : sizeof(F));
+        });
+        Resp rp{};
+        for_each_leaf<Resp>(rp, [&](const auto& v) {
+            using F = std::remove_cvref_t<decltype(v)>;
+            m->resp_string.push_back(std::is_same_v<F, std::string>);
+            m->resp_size.push_back(std::is_same_v<F, std::string> ? 0 : sizeof(F));
+        });
+        _m.push_back(std::move(m));
+        release();  // buffers are sized for the largest frames on the next serve
+        return *_m.back();
     }
 
     static double secs(clock::time_point t0) { return std::chrono::duration<double>(clock::now() - t0).count(); }
@@ -637,11 +618,6 @@ private:
     }
     static uint32_t be32_at(const uint8_t* b) {
         return (uint32_t(b[0]) << 24) | (uint32_t(b[1]) << 16) | (uint32_t(b[2]) << 8) | uint32_t(b[3]);
-    }
-    void* alloc(size_t b) {
-        void* p = nullptr;
-        check(hipMalloc(&p, b));
-        return p;
     }
     static bool more_pending(int fd) {
         int avail = 0;
@@ -677,401 +653,249 @@ private:
     }
     static constexpr uint64_t kRecordFillMax = 256;  // struct bytes srpc_gpu_unpack_aos_fill takes
 
-    /// A record method's three steps on n contiguous request frames at src:
-    /// decode into its Req array (status slot st), handler, framed responses from
-    /// its Resp array to dst.  Returns the decode's status (positive for the
-    /// warm-up's zero frame); the handler and the pack throw.
-    int run_record_method(method_entry& m, const uint8_t* src, uint64_t n, srpc_unpack_status* st, uint8_t* dst,
-                          const char* what) {
-        const int rc = m.req_stride <= kRecordFillMax
-                           ? srpc_gpu_unpack_aos_fill(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
-                                                      m.req_loffs.data(), m.req_fill.data(), st, _s)
-                           : srpc_gpu_unpack_aos(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
-                                                 m.req_loffs.data(), st, _s);
-        if (rc < 0) return rc;
-        check_srpc(m.rhandler(m.d_reqs, m.d_resps, n, _s), what);
-        check_srpc(srpc_gpu_pack_aos(m.out->get(), m.d_resps, m.resp_stride, m.resp_loffs.data(), n, dst, n * m.fout, _s),
-                   "srpc_gpu_pack_aos");
-        return rc;
-    }
+    // ---- the buffers: owned in groups, built by ensure(), dropped by release() ----
 
-    /// A string method's device buffers for batches of _max frames in _cap bytes.
-    void alloc_var(method_entry& m) {
-        m.req_cols.clear();
-        m.req_bytes.clear();
-        m.req_offs.clear();
-        for (size_t f = 0; f < m.req_string.size(); ++f) {
-            m.req_bytes.push_back(m.req_string[f] ? _cap + 16 : _max * m.req_size[f] + 16);
-            m.req_cols.push_back(alloc(m.req_bytes.back()));
-            m.req_offs.push_back(m.req_string[f] ? static_cast<uint64_t*>(alloc(8 * (_max + 1) + 16)) : nullptr);
+    /// A staging slot: the pinned halves of a batch in flight, and its last copy's event.
+    struct slot {
+        pinned_buffer<uint8_t> h_in, h_out, h_cls;
+        pinned_buffer<uint32_t> h_offs;
+        // per method: its unpack status [k], its pack status [K + k] (each
+        // call resets its own, so methods never clear each other's)
+        pinned_buffer<srpc_unpack_status> h_status;
+        hipEvent_t done = nullptr;  // the batch's last copy
+        slot() = default;
+        slot(slot const&) = delete;
+        slot& operator=(slot const&) = delete;
+        ~slot() { reset(); }
+        void reset() {
+            h_in.reset(), h_out.reset(), h_cls.reset(), h_offs.reset(), h_status.reset();
+            if (done) (void)hipEventDestroy(done);
+            done = nullptr;
         }
-        m.resp_cols.clear();
-        m.resp_bytes.clear();
-        m.resp_offs.clear();
+    };
+    struct batch_buffers {  // every route
+        device_buffer<uint8_t> d_in, d_cls, d_out;
+        device_buffer<uint32_t> d_offs;
+        device_buffer<uint64_t> d_counts;
+        device_buffer<srpc_unpack_status> d_status;
+        pinned_buffer<uint64_t> h_counts;
+    };
+    struct bucket_buffers {
+        device_buffer<uint32_t> d_index;
+        device_buffer<uint64_t> d_out_off;
+        device_buffer<uint8_t> d_gather, d_resp;
+        device_buffer<void> d_scratch;
+        // with a string method registered (either route that serves them)
+        device_buffer<uint64_t> d_var_rec;  // the request index of the bucket being served
+        device_buffer<void> d_var_scratch;
+        pinned_buffer<uint64_t> h_out_off;
+    };
+    struct ordered_buffers {  // the call index and the ranks stand in for the buckets
+        device_buffer<void> d_mix_index;
+        device_buffer<uint32_t> d_rank;
+    };
+    struct ordered_var_buffers {
+        device_buffer<void> d_scratch;
+        device_buffer<uint64_t> d_ends, d_total;
+        device_buffer<uint32_t> d_offs;
+        pinned_buffer<uint64_t> h_ends, h_total;
+        pinned_buffer<uint32_t> h_offs;
+    };
+
+    /// Method m's device buffers for batches of _max frames in _cap bytes, and
+    /// the pointer tables over them.
+    void alloc_method(method_entry& m) {
+        if (m.rec) {
+            m.d_reqs.alloc(_max * m.req_stride + 16);
+            m.d_resps.alloc(_max * m.resp_stride + 16);
+            check(hipMemset(m.d_resps, 0, _max * m.resp_stride + 16));
+            if (m.req_stride > kRecordFillMax) {  // past the fill call's limit: every struct a Req{} once, leaves per batch
+                std::vector<uint8_t> all(_max * m.req_stride);
+                for (uint64_t i = 0; i < _max; ++i) std::memcpy(all.data() + i * m.req_stride, m.req_fill.data(), m.req_stride);
+                check(hipMemcpy(m.d_reqs, all.data(), all.size(), hipMemcpyHostToDevice));
+            }
+            return;
+        }
+        auto side = [&](std::vector<bool> const& str, std::vector<uint64_t> const& size, uint64_t str_bytes,
+                        std::vector<device_buffer<uint8_t>>& buf, std::vector<device_buffer<uint64_t>>& off_buf,
+                        std::vector<uint64_t>& bytes, std::vector<void*>& cols, std::vector<uint64_t*>& offs) {
+            buf.clear(), off_buf.clear(), bytes.clear(), cols.clear(), offs.clear();
+            buf.resize(str.size()), off_buf.resize(str.size());
+            for (size_t f = 0; f < str.size(); ++f) {
+                bytes.push_back(str[f] ? str_bytes : _max * size[f] + 16);
+                buf[f].alloc(bytes[f]);
+                if (str[f]) off_buf[f].alloc(8 * (_max + 1) + 16);
+                cols.push_back(buf[f]);
+                offs.push_back(off_buf[f]);
+            }
+        };
+        side(m.req_string, m.req_size, _cap + 16, m.req_buf, m.req_off_buf, m.req_bytes, m.req_cols, m.req_offs);
+        side(m.resp_string, m.resp_size, _max * m.lim.max_response_chars + 16, m.resp_buf, m.resp_off_buf, m.resp_bytes,
+             m.resp_cols, m.resp_offs);
+        m.c_resp_cols.assign(m.resp_cols.begin(), m.resp_cols.end());
+        m.c_req_offs.assign(m.req_offs.begin(), m.req_offs.end());
+        m.c_resp_offs.assign(m.resp_offs.begin(), m.resp_offs.end());
+        m.req_scap.clear();
+        for (uint64_t b : m.req_bytes) m.req_scap.push_back(b - 16);  // a string column: the receive buffer's bytes
+        if (!m.var) return;
         m.resp_wire_cap = _max * m.min_out + 16;
-        for (size_t f = 0; f < m.resp_string.size(); ++f) {
-            const uint64_t b = m.resp_string[f] ? _max * m.lim.max_response_chars + 16 : _max * m.resp_size[f] + 16;
-            if (m.resp_string[f]) m.resp_wire_cap += b;
-            m.resp_bytes.push_back(b);
-            m.resp_cols.push_back(alloc(b));
-            m.resp_offs.push_back(m.resp_string[f] ? static_cast<uint64_t*>(alloc(8 * (_max + 1) + 16)) : nullptr);
-        }
-        check(hipHostMalloc(reinterpret_cast<void**>(&m.h_ends), 16 * m.resp_string.size() + 16, hipHostMallocDefault));
+        for (size_t f = 0; f < m.resp_string.size(); ++f)
+            if (m.resp_string[f]) m.resp_wire_cap += m.resp_bytes[f];
+        m.h_ends.alloc(16 * m.resp_string.size() + 16);
         if (_ordered_var) return;  // the replies are packed straight into the reply stream
-        m.resp_wire = static_cast<uint8_t*>(alloc(m.resp_wire_cap));
-        m.resp_rec = static_cast<uint64_t*>(alloc(8 * (_max + 1) + 16));
+        m.resp_wire.alloc(m.resp_wire_cap);
+        m.resp_rec.alloc(8 * (_max + 1) + 16);
         uint64_t a = 0, b = 0;
         check_srpc(srpc_plan_var_scratch_bytes(m.in->get(), _max, _cap, &a), "srpc_plan_var_scratch_bytes");
         check_srpc(srpc_plan_var_scratch_bytes(m.out->get(), _max, m.resp_wire_cap, &b), "srpc_plan_var_scratch_bytes");
         _var_scratch_bytes = std::max({_var_scratch_bytes, a, b});
     }
-    void free_var(method_entry& m) {
-        for (void* p : m.req_cols) (void)hipFree(p);
-        for (void* p : m.resp_cols) (void)hipFree(p);
-        for (uint64_t* p : m.req_offs)
-            if (p) (void)hipFree(p);
-        for (uint64_t* p : m.resp_offs)
-            if (p) (void)hipFree(p);
-        if (m.resp_wire) (void)hipFree(m.resp_wire);
-        if (m.resp_rec) (void)hipFree(m.resp_rec);
-        if (m.h_ends) (void)hipHostFree(m.h_ends);
-        m.h_ends = nullptr;
-        m.req_cols.clear();
-        m.resp_cols.clear();
-        m.req_offs.clear();
-        m.resp_offs.clear();
-        m.resp_wire = nullptr;
-        m.resp_rec = nullptr;
-    }
 
     void ensure() {
-        if (_h_in) return;
+        if (_slots[0].h_in) return;
         const uint64_t K = _m.size();
         _cap = _max * max_fin();
         if (_cap > 0xffffffffull) throw plan_error("batch_server: batch buffer over 4 GiB", SRPC_E_UNSUPPORTED);
+        _var_methods = any_var_method();
         _var_scratch_bytes = 0;
-        for (auto& m : _m)
-            if (m->var) alloc_var(*m);
-        if (_var_scratch_bytes) _d_var_scratch = alloc(_var_scratch_bytes);
-        if (any_var_method()) {
-            _d_var_rec = alloc(8 * (_max + 1) + 16);
-            check(hipHostMalloc(reinterpret_cast<void**>(&_h_out_off), 8 * (_max + 1) + 16, hipHostMallocDefault));
+        for (auto& m : _m) alloc_method(*m);
+        if (_var_scratch_bytes) _bk.d_var_scratch.alloc(_var_scratch_bytes);
+        if (_var_methods) {
+            _bk.d_var_rec.alloc(8 * (_max + 1) + 16);
+            _bk.h_out_off.alloc(8 * (_max + 1) + 16);
         }
         const uint64_t out_cap = this->out_cap();
         // two staging slots (two batches in flight) unless a string method's
         // batches need the host between their kernels (SRPC_SERVER_SLOTS=1:
         // one batch at a time, the A/B baseline)
         const char* slots_env = std::getenv("SRPC_SERVER_SLOTS");
-        _nslots = any_var_method() || _ordered_var || (slots_env && slots_env[0] == '1') ? 1 : 2;
+        _nslots = _var_methods || _ordered_var || (slots_env && slots_env[0] == '1') ? 1 : 2;
         for (int i = 0; i < _nslots; ++i) {
             slot& z = _slots[i];
-            check(hipHostMalloc(reinterpret_cast<void**>(&z.h_in), _cap + 16, hipHostMallocDefault));
-            check(hipHostMalloc(reinterpret_cast<void**>(&z.h_offs), 4 * _max + 16, hipHostMallocDefault));
-            check(hipHostMalloc(reinterpret_cast<void**>(&z.h_out), out_cap + 16, hipHostMallocDefault));
-            check(hipHostMalloc(reinterpret_cast<void**>(&z.h_cls), _max + 16, hipHostMallocDefault));
-            // per method: its unpack status [k], its pack status [K + k] (each
-            // call resets its own, so methods never clear each other's)
-            check(hipHostMalloc(reinterpret_cast<void**>(&z.h_status), 2 * K * sizeof(srpc_unpack_status),
-                                hipHostMallocDefault));
+            z.h_in.alloc(_cap + 16);
+            z.h_offs.alloc(4 * _max + 16);
+            z.h_out.alloc(out_cap + 16);
+            z.h_cls.alloc(_max + 16);
+            z.h_status.alloc(2 * K * sizeof(srpc_unpack_status));
             check(hipEventCreateWithFlags(&z.done, hipEventDisableTiming));
         }
-        use_slot(0);
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_counts), 8 * (K + 2) + 16, hipHostMallocDefault));
-        check(hipMalloc(&_d_in, _cap + 16));
-        check(hipMalloc(&_d_offs, 4 * _max + 16));
-        check(hipMalloc(&_d_cls, _max + 16));
-        check(hipMalloc(&_d_counts, 8 * (K + 2) + 16));
-        check(hipMalloc(&_d_out, out_cap + 16));
-        check(hipMalloc(&_d_status, 2 * K * sizeof(srpc_unpack_status)));
+        _b.h_counts.alloc(8 * (K + 2) + 16);
+        _b.d_in.alloc(_cap + 16);
+        _b.d_offs.alloc(4 * _max + 16);
+        _b.d_cls.alloc(_max + 16);
+        _b.d_counts.alloc(8 * (K + 2) + 16);
+        _b.d_out.alloc(out_cap + 16);
+        _b.d_status.alloc(2 * K * sizeof(srpc_unpack_status));
+        build_tables();
         if (_ordered) {
-            // the call index and the ranks stand in for the buckets: no bucket
-            // index, no gather buffer, no second response buffer
+            // no bucket index, no gather buffer, no second response buffer
             check_srpc(srpc_frames_mixed_index_bytes(_max, static_cast<int>(K), &_mix_index_bytes),
                        "srpc_frames_mixed_index_bytes");
-            check(hipMalloc(&_d_mix_index, _mix_index_bytes + 16));
-            check(hipMalloc(&_d_rank, 4 * _max + 16));
-            if (_ordered_var) ensure_ordered_var(out_cap);
+            _od.d_mix_index.alloc(_mix_index_bytes + 16);
+            _od.d_rank.alloc(4 * _max + 16);
+            if (_ordered_var) {
+                if (out_cap > 0xffffffffull) throw plan_error("batch_server: reply buffer over 4 GiB", SRPC_E_UNSUPPORTED);
+                uint64_t a = 0, b = 0;
+                check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_in_plans.data(), static_cast<int>(K), _max, &a),
+                           "srpc_frames_mixed_var_scratch_bytes");
+                check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_out_plans.data(), static_cast<int>(K), _max, &b),
+                           "srpc_frames_mixed_var_scratch_bytes");
+                _ov_scratch_bytes = std::max(a, b);
+                _ov.d_scratch.alloc(_ov_scratch_bytes + 16);
+                _ov.d_ends.alloc(8 * (_ov_slots + 1) + 16);
+                _ov.d_total.alloc(16);
+                _ov.d_offs.alloc(4 * (_max + 1) + 16);
+                _ov.h_ends.alloc(8 * (_ov_slots + 1) + 16);
+                _ov.h_total.alloc(16);
+                _ov.h_offs.alloc(4 * (_max + 1) + 16);
+            }
         } else {
-            check(hipMalloc(&_d_index, 4 * K * _max + 16));
-            check(hipMalloc(&_d_out_off, 8 * (_max + 1) + 16));
-            check(hipMalloc(&_d_gather, _cap + 16));
-            check(hipMalloc(&_d_resp, out_cap + 16));
+            _bk.d_index.alloc(4 * K * _max + 16);
+            _bk.d_out_off.alloc(8 * (_max + 1) + 16);
+            _bk.d_gather.alloc(_cap + 16);
+            _bk.d_resp.alloc(out_cap + 16);
             check_srpc(srpc_frames_scratch_bytes(_max, static_cast<int>(K), &_scratch_bytes),
                        "srpc_frames_scratch_bytes");
-            check(hipMalloc(&_d_scratch, _scratch_bytes));
-        }
-        _in_plans.clear();
-        _out_plans.clear();
-        _req_tbl.clear();
-        _resp_tbl.clear();
-        _const_resp.clear();
-        _caps.assign(K, _max);
-        for (auto const& m : _m) {
-            _out_plans.push_back(m->out->get());
-            _req_tbl.push_back(m->req_cols.data());
-            _const_resp.emplace_back(m->resp_cols.begin(), m->resp_cols.end());
-        }
-        for (auto const& c : _const_resp) _resp_tbl.push_back(c.data());
-        _resp_mut_tbl.clear();
-        for (auto const& m : _m) _resp_mut_tbl.push_back(m->resp_cols.data());
-        _resp_bytes.clear();
-        _var_rec.clear();
-        _var_idx.clear();
-        for (auto const& m : _m) {
-            if (m->var) _var_idx.push_back(_in_plans.size());
-            _in_plans.push_back(m->in->get());
-            _resp_bytes.push_back(static_cast<uint32_t>(m->fout));
-            _var_rec.push_back(m->var ? m->resp_rec : nullptr);
+            _bk.d_scratch.alloc(_scratch_bytes);
         }
         warm_up();
     }
 
-    /// One-frame run of every kernel the batches use (the library's and each
-    /// handler, on one all-zero record) and one copy through every staging
-    /// buffer, at serve start: first uses cost milliseconds that otherwise land
-    /// on the connection's first batch (profiles/r02_e2e_warmup.log).
-    void warm_up() {
-        if (_ordered_var) return warm_up_ordered_var();
-        if (_ordered) return warm_up_ordered();
-        const int K = static_cast<int>(_m.size());
-        const uint64_t out_cap = this->out_cap();
-        check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
-        check(hipMemsetAsync(_d_resp, 0, out_cap + 16, _s));
-        check(hipMemsetAsync(_d_gather, 0, _cap + 16, _s));
-        check(hipMemsetAsync(_d_index, 0, 4 * _m.size() * _max + 16, _s));
-        check(hipMemsetAsync(_d_out_off, 0, 8 * (_max + 1) + 16, _s));
-        check(hipMemsetAsync(_d_cls, 0, _max + 16, _s));
-        check(hipMemsetAsync(_d_scratch, 0, _scratch_bytes, _s));
-        for (auto const& m : _m) {
-            memset_cols(m->req_cols, m->req_bytes);
-            memset_cols(m->resp_cols, m->resp_bytes);
-            for (uint64_t* p : m->req_offs)
-                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
-            for (uint64_t* p : m->resp_offs)
-                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
-        }
-        if (_d_var_scratch) check(hipMemsetAsync(_d_var_scratch, 0, _var_scratch_bytes, _s));
-        std::memset(_h_in, 0, _cap);
-        std::memset(_h_offs, 0, 4 * _max);
-        // a batch's exact sequence of copies and launches on one all-zero frame,
-        // twice (the first pass pays the first uses; whole buffers move)
-        for (int pass = 0; pass < 2; ++pass) {
-            check(hipMemcpyAsync(_d_in, _h_in, _cap, hipMemcpyHostToDevice, _s));
-            check(hipMemcpyAsync(_d_offs, _h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
-            check_srpc(srpc_frames_classify(_in_plans.data(), _resp_bytes.data(), K, static_cast<const uint8_t*>(_d_in),
-                                            8, static_cast<const uint32_t*>(_d_offs), 1, static_cast<uint8_t*>(_d_cls),
-                                            static_cast<uint32_t*>(_d_index), static_cast<uint64_t*>(_d_counts),
-                                            static_cast<uint64_t*>(_d_out_off), _d_scratch, _scratch_bytes, _s),
-                       "srpc_frames_classify");
-            check(hipMemcpyAsync(_h_counts, _d_counts, 8 * (K + 2), hipMemcpyDeviceToHost, _s));
-            check(hipStreamSynchronize(_s));
-            check(hipMemsetAsync(_d_status, 0, 2 * _m.size() * sizeof(srpc_unpack_status), _s));
-            for (size_t k = 0; k < _m.size(); ++k) {
-                auto const& m = _m[k];
-                if (m->var) {
-                    warm_up_var(*m, k);
-                    continue;
-                }
-                check_srpc(srpc_frames_gather(static_cast<const uint8_t*>(_d_in), static_cast<const uint32_t*>(_d_offs),
-                                              static_cast<const uint32_t*>(_d_index), 1, static_cast<uint32_t>(m->fin),
-                                              static_cast<uint8_t*>(_d_gather), _s),
-                           "srpc_frames_gather");
-                if (m->rec) {  // the same on its struct arrays, both destinations
-                    for (void* dst : {_d_out, _d_resp})
-                        check_srpc(run_record_method(*m, static_cast<const uint8_t*>(_d_gather), 1, _d_status + k,
-                                                     static_cast<uint8_t*>(dst), "batch handler (warm-up)"),
-                                   "srpc_gpu_unpack_aos");
-                } else {
-                    (void)srpc_gpu_unpack(m->in->get(), static_cast<const uint8_t*>(_d_gather), m->fin, 1,
-                                          m->req_cols.data(), _d_status + k, _s);  // a prefix error on the zero frame: expected
-                    // the handler's own kernels load their code object on first use
-                    // too: it runs on the one zero record (its output is never sent)
-                    check_srpc(m->handler(m->req_cols.data(), m->resp_cols.data(), 1, _s), "batch handler (warm-up)");
-                    check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_out), m->fout,
-                                             _s),
-                               "srpc_gpu_pack");
-                    check_srpc(srpc_gpu_pack(m->out->get(), m->resp_cols.data(), 1, static_cast<uint8_t*>(_d_resp), m->fout,
-                                             _s),
-                               "srpc_gpu_pack");
-                }
-                check_srpc(srpc_frames_scatter(static_cast<const uint8_t*>(_d_resp),
-                                               static_cast<const uint32_t*>(_d_index), 1, static_cast<uint32_t>(m->fout),
-                                               static_cast<const uint64_t*>(_d_out_off), static_cast<uint8_t*>(_d_out),
-                                               _s),
-                           "srpc_frames_scatter");
-            }
-            check(hipMemcpyAsync(_h_out, _d_out, out_cap, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_cls, _d_cls, _max, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_status, _d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
-                                 _s));
-            check(hipStreamSynchronize(_s));
-        }
-    }
-    /// Ordered mode, the decode half of a batch: one
-    /// srpc_frames_unpack_requests_mixed over the nf frames in _d_in[0, used)
-    /// into the methods' request columns (and the ranks, when the ordered
-    /// handler is set), then the counts on the host after one sync.
-    void ordered_decode(uint64_t nf, uint64_t used) {
-        const int K = static_cast<int>(_m.size());
-        check(hipMemsetAsync(_d_status, 0, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status), _s));
-        check_srpc(srpc_frames_unpack_requests_mixed(_in_plans.data(), K, static_cast<const uint8_t*>(_d_in), used,
-                                                     static_cast<const uint32_t*>(_d_offs), nf, _req_tbl.data(),
-                                                     nullptr, _caps.data(), static_cast<uint8_t*>(_d_cls),
-                                                     _d_mix_index, _mix_index_bytes,
-                                                     static_cast<uint64_t*>(_d_counts), _d_status, _s),
-                   "srpc_frames_unpack_requests_mixed");
-        if (_ohandler)
-            check_srpc(srpc_frames_mixed_ranks(_d_mix_index, static_cast<const uint8_t*>(_d_cls), nf, K,
-                                               static_cast<uint32_t*>(_d_rank), _s),
-                       "srpc_frames_mixed_ranks");
-        check(hipMemcpyAsync(_h_counts, _d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
-        check(hipStreamSynchronize(_s));
-    }
-    int run_ordered_handler(uint64_t nf) {
-        ordered_batch b;
-        b.n = nf;
-        b.d_method = static_cast<const uint8_t*>(_d_cls);
-        b.d_rank = static_cast<const uint32_t*>(_d_rank);
-        b.counts = _h_counts;
-        b.methods = _m.size();
-        b.req_cols = _req_tbl.data();
-        b.resp_cols = _resp_mut_tbl.data();
-        return _ohandler(b, _s);
-    }
-    /// Ordered mode, the reply half: the response plans' frames in arrival
-    /// order straight into _d_out (an unknown frame gets no bytes: the pack's
-    /// "bad call", answered on the CPU in its place, so the flag it would
-    /// raise is not asked for).
-    void ordered_pack(uint64_t nf) {
-        check_srpc(srpc_frames_pack_requests_mixed(_out_plans.data(), static_cast<int>(_m.size()), _resp_tbl.data(),
-                                                   nullptr, _caps.data(), static_cast<const uint8_t*>(_d_cls),
-                                                   _d_mix_index, nf, static_cast<uint8_t*>(_d_out), out_cap(), nullptr,
-                                                   nullptr, _s),
-                   "srpc_frames_pack_requests_mixed (replies)");
-    }
-    /// warm_up for ordered mode: the batch's sequence on one all-zero frame
-    /// (nobody's), every per-method handler on one zero record -- or the
-    /// ordered handler on that batch of one unknown frame -- twice.
-    void warm_up_ordered() {
-        const uint64_t out_cap = this->out_cap();
-        check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
-        check(hipMemsetAsync(_d_cls, 0, _max + 16, _s));
-        check(hipMemsetAsync(_d_mix_index, 0, _mix_index_bytes + 16, _s));
-        check(hipMemsetAsync(_d_rank, 0, 4 * _max + 16, _s));
-        for (auto const& m : _m) {
-            memset_cols(m->req_cols, m->req_bytes);
-            memset_cols(m->resp_cols, m->resp_bytes);
-        }
-        std::memset(_h_in, 0, _cap);
-        std::memset(_h_offs, 0, 4 * _max);
-        for (int pass = 0; pass < 2; ++pass) {
-            check(hipMemcpyAsync(_d_in, _h_in, _cap, hipMemcpyHostToDevice, _s));
-            check(hipMemcpyAsync(_d_offs, _h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
-            ordered_decode(1, std::min<uint64_t>(8, _cap));
-            if (_ohandler) {
-                check_srpc(run_ordered_handler(1), "ordered batch handler (warm-up)");
-            } else {
-                for (auto const& m : _m)
-                    check_srpc(m->handler(m->req_cols.data(), m->resp_cols.data(), 1, _s), "batch handler (warm-up)");
-            }
-            ordered_pack(1);
-            check(hipMemcpyAsync(_h_out, _d_out, out_cap, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_cls, _d_cls, _max, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_status, _d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
-                                 _s));
-            check(hipStreamSynchronize(_s));
-        }
-    }
-
-    // ---- ordered mode with string-bodied methods (set_ordered_var) ----
-
-    /// The route's plans, tables and buffers (ensure; the methods' columns are
-    /// allocated).  Per method and per side: a side with strings keeps the
-    /// unframed-prefix string plan register_var_method built, a side without
+    /// The per-method tables every route's calls take, over the methods' own
+    /// (alloc_method).  The ordered routes' plans, per method and per side: a
+    /// side with strings keeps the unframed-prefix string plan, a side without
     /// gets a fixed-size plan behind the framed prefix (register_method's own,
     /// or one built here for a string method's fixed side).
-    void ensure_ordered_var(uint64_t out_cap) {
-        const int K = static_cast<int>(_m.size());
-        if (out_cap > 0xffffffffull) throw plan_error("batch_server: reply buffer over 4 GiB", SRPC_E_UNSUPPORTED);
-        _ov_in_plans.clear(), _ov_out_plans.clear();
+    void build_tables() {
+        _in_plans.clear(), _ord_in_plans.clear(), _ord_out_plans.clear(), _resp_bytes.clear(), _var_rec.clear();
+        _req_tbl.clear(), _resp_tbl.clear(), _resp_mut_tbl.clear();
         _ov_req_offs.clear(), _ov_c_req_offs.clear(), _ov_resp_offs.clear(), _ov_c_resp_offs.clear();
         _ov_req_scap.clear(), _ov_resp_cap.clear();
+        _caps.assign(_m.size(), _max);
         _ov_slots = 0;
         for (auto& m : _m) {
-            if (m->var && !m->in_str()) m->ord_in = std::make_unique<raw_plan>(m->in_kinds, m->framed_in, _dev);
-            if (m->var && !m->out_str()) m->ord_out = std::make_unique<raw_plan>(m->out_kinds, m->framed_out, _dev);
-            _ov_in_plans.push_back(m->ord_in ? m->ord_in->get() : m->in->get());
-            _ov_out_plans.push_back(m->ord_out ? m->ord_out->get() : m->out->get());
-            if (!m->var) {  // no offsets arrays: a nullptr per leaf
-                m->req_offs.assign(m->req_cols.size(), nullptr);
-                m->resp_offs.assign(m->resp_cols.size(), nullptr);
-            }
-            m->c_req_offs.assign(m->req_offs.begin(), m->req_offs.end());
-            m->c_resp_offs.assign(m->resp_offs.begin(), m->resp_offs.end());
-            m->req_scap.clear();
-            for (uint64_t b : m->req_bytes) m->req_scap.push_back(b - 16);  // a string column: the receive buffer's bytes
-            for (uint64_t* o : m->req_offs) _ov_slots += o ? 1 : 0;
-        }
-        for (auto const& m : _m) {
+            if (_ordered_var && m->var && !m->in_str()) m->ord_in = std::make_unique<raw_plan>(m->in_kinds, m->framed_in, _dev);
+            if (_ordered_var && m->var && !m->out_str())
+                m->ord_out = std::make_unique<raw_plan>(m->out_kinds, m->framed_out, _dev);
+            _in_plans.push_back(m->in->get());
+            _ord_in_plans.push_back(m->ord_in ? m->ord_in->get() : m->in->get());
+            _ord_out_plans.push_back(m->ord_out ? m->ord_out->get() : m->out->get());
+            _resp_bytes.push_back(static_cast<uint32_t>(m->fout));
+            _var_rec.push_back(m->resp_rec);
+            _req_tbl.push_back(m->req_cols.data());
+            _resp_mut_tbl.push_back(m->resp_cols.data());
+            _resp_tbl.push_back(m->c_resp_cols.data());
             _ov_req_offs.push_back(m->req_offs.data());
             _ov_c_req_offs.push_back(m->c_req_offs.data());
             _ov_resp_offs.push_back(m->resp_offs.data());
             _ov_c_resp_offs.push_back(m->c_resp_offs.data());
             _ov_req_scap.push_back(m->req_scap.data());
             _ov_resp_cap.push_back(m->resp_bytes.data());
+            for (uint64_t* o : m->req_offs) _ov_slots += o ? 1 : 0;
         }
-        uint64_t a = 0, b = 0;
-        check_srpc(srpc_frames_mixed_var_scratch_bytes(_ov_in_plans.data(), K, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
-        check_srpc(srpc_frames_mixed_var_scratch_bytes(_ov_out_plans.data(), K, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
-        _ov_scratch_bytes = std::max(a, b);
-        _d_ov_scratch = alloc(_ov_scratch_bytes + 16);
-        _d_ov_ends = alloc(8 * (_ov_slots + 1) + 16);
-        _d_ov_total = alloc(16);
-        _d_ov_offs = alloc(4 * (_max + 1) + 16);
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_ends), 8 * (_ov_slots + 1) + 16, hipHostMallocDefault));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_total), 16, hipHostMallocDefault));
-        check(hipHostMalloc(reinterpret_cast<void**>(&_h_ov_offs), 4 * (_max + 1) + 16, hipHostMallocDefault));
     }
 
-    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed_var over
-    /// the nf frames in _d_in[0, used) into the methods' request columns, chars
-    /// and offsets (and the ranks, when the ordered handler is set), then the
-    /// counts and the string slots' ends on the host after one sync.
-    void ordered_var_decode(uint64_t nf, uint64_t used) {
-        const int K = static_cast<int>(_m.size());
-        check(hipMemsetAsync(_d_status, 0, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status), _s));
-        check_srpc(srpc_frames_unpack_requests_mixed_var(
-                       _ov_in_plans.data(), K, static_cast<const uint8_t*>(_d_in), used,
-                       static_cast<const uint32_t*>(_d_offs), nf, _req_tbl.data(), _ov_req_offs.data(), _ov_req_scap.data(),
-                       nullptr, _caps.data(), static_cast<uint8_t*>(_d_cls), _d_mix_index, _mix_index_bytes,
-                       static_cast<uint64_t*>(_d_counts), static_cast<uint64_t*>(_d_ov_ends), _d_status, _d_ov_scratch,
-                       _ov_scratch_bytes, _s),
-                   "srpc_frames_unpack_requests_mixed_var");
-        if (_ovhandler)
-            check_srpc(srpc_frames_mixed_ranks(_d_mix_index, static_cast<const uint8_t*>(_d_cls), nf, K,
-                                               static_cast<uint32_t*>(_d_rank), _s),
-                       "srpc_frames_mixed_ranks");
-        check(hipMemcpyAsync(_h_counts, _d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
-        if (_ov_slots) check(hipMemcpyAsync(_h_ov_ends, _d_ov_ends, 8 * _ov_slots, hipMemcpyDeviceToHost, _s));
-        check(hipStreamSynchronize(_s));
+    void release() {
+        for (auto& m : _m) m->release();
+        for (slot& z : _slots) z.reset();
+        _nslots = 0;
+        _b = {}, _bk = {}, _od = {}, _ov = {};
     }
-    int run_ordered_var_handler(uint64_t nf) {
-        ordered_var_batch b;
-        b.n = nf;
-        b.d_method = static_cast<const uint8_t*>(_d_cls);
-        b.d_rank = static_cast<const uint32_t*>(_d_rank);
-        b.counts = _h_counts;
-        b.methods = _m.size();
-        b.req_cols = _req_tbl.data();
-        b.resp_cols = _resp_mut_tbl.data();
-        b.req_str_offs = _ov_c_req_offs.data();
-        b.resp_str_offs = _ov_resp_offs.data();
-        b.resp_cap = _ov_resp_cap.data();
-        return _ovhandler(b, _s);
+
+    // ---- the steps of a batch, shared by the batches and the warm-up ----
+
+    /// A batch between process_begin and process_end: the skeleton fills the
+    /// first line, the route's steps the rest.
+    struct pending {
+        bool valid = false;
+        int slot = 0;
+        uint64_t nf = 0, used = 0;
+        double gpu_s = 0;  // host time spent on the batch's GPU work (enqueue, syncs, the final wait)
+        uint64_t unknown = 0, total = 0;  // frames for the CPU; bytes of the GPU's replies
+        bool mixed = false;
+        bool cls_on_host = false;  // the route already fetched the class bytes
+        // where frame i's answer ends: [i + 1] of the route's offsets, or (neither) after its fixed frame
+        const uint64_t* ends64 = nullptr;
+        const uint32_t* ends32 = nullptr;
+        uint64_t d2h_extra = 0;  // d2h_bytes beyond the replies: the class bytes and offsets the route fetched
+    };
+    /// The batch being enqueued, for the trace (SRPC_SERVER_TRACE) and its timers.
+    struct trace_point {
+        bool on = false;
+        uint64_t batch = 0, nf = 0;
+        clock::time_point t0;
+    };
+    void mark(const char* what) const {
+        if (_tp.on)
+            std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)_tp.batch,
+                         (unsigned long long)_tp.nf, what, 1e3 * secs(_tp.t0));
     }
-    /// Method k's handler over its n requests in arrival order.
-    int run_ordered_var_method(method_entry& m, uint64_t n) {
-        if (!m.var) return m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s);
+    void clear_status() {
+        check(hipMemsetAsync(_b.d_status, 0, 2 * _m.size() * sizeof(srpc_unpack_status), _s));
+    }
+
+    /// A string method's handler over n requests in its columns.
+    int run_var_handler(method_entry& m, uint64_t n) {
         var_batch b;
         b.n = n;
         b.req_cols = m.req_cols.data();
@@ -1081,98 +905,10 @@ private:
         b.resp_cap = m.resp_bytes.data();
         return m.vhandler(b, _s);
     }
-    /// The reply half: the response plans' frames in arrival order straight
-    /// into _d_out, nothing for an unknown frame; the stream's size, and with
-    /// unknown frames every answer's offset, to the host.  No sync here.
-    void ordered_var_pack(uint64_t nf, bool unknown) {
-        const int K = static_cast<int>(_m.size());
-        // an unknown frame is the pack's "bad call" and would raise its flag: asked for only without one
-        check_srpc(srpc_frames_pack_requests_mixed_var(
-                       _ov_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(), nullptr, _caps.data(),
-                       static_cast<const uint8_t*>(_d_cls), _d_mix_index, nf, static_cast<uint8_t*>(_d_out), out_cap(),
-                       static_cast<uint32_t*>(_d_ov_offs), static_cast<uint64_t*>(_d_ov_total),
-                       unknown ? nullptr : _d_status + K, _d_ov_scratch, _ov_scratch_bytes, _s),
-                   "srpc_frames_pack_requests_mixed_var (replies)");
-        check(hipMemcpyAsync(_h_ov_total, _d_ov_total, 8, hipMemcpyDeviceToHost, _s));
-        if (unknown) check(hipMemcpyAsync(_h_ov_offs, _d_ov_offs, 4 * (nf + 1), hipMemcpyDeviceToHost, _s));
-    }
-    /// warm_up for this route: the batch's sequence on one all-zero frame
-    /// (nobody's), every per-method handler on one zero record (empty strings)
-    /// -- or the ordered handler on that batch of one unknown frame -- twice.
-    void warm_up_ordered_var() {
-        const uint64_t out_cap = this->out_cap();
-        check(hipMemsetAsync(_d_out, 0, out_cap + 16, _s));
-        check(hipMemsetAsync(_d_cls, 0, _max + 16, _s));
-        check(hipMemsetAsync(_d_mix_index, 0, _mix_index_bytes + 16, _s));
-        check(hipMemsetAsync(_d_rank, 0, 4 * _max + 16, _s));
-        check(hipMemsetAsync(_d_ov_scratch, 0, _ov_scratch_bytes, _s));
-        check(hipMemsetAsync(_d_ov_offs, 0, 4 * (_max + 1) + 16, _s));
-        for (auto const& m : _m) {
-            memset_cols(m->req_cols, m->req_bytes);
-            memset_cols(m->resp_cols, m->resp_bytes);
-            for (uint64_t* p : m->req_offs)
-                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
-            for (uint64_t* p : m->resp_offs)
-                if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
-        }
-        std::memset(_h_in, 0, _cap);
-        std::memset(_h_offs, 0, 4 * _max);
-        for (int pass = 0; pass < 2; ++pass) {
-            check(hipMemcpyAsync(_d_in, _h_in, _cap, hipMemcpyHostToDevice, _s));
-            check(hipMemcpyAsync(_d_offs, _h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
-            ordered_var_decode(1, std::min<uint64_t>(8, _cap));
-            if (_ovhandler) {
-                check_srpc(run_ordered_var_handler(1), "ordered batch handler (warm-up)");
-            } else {
-                for (auto const& m : _m) check_srpc(run_ordered_var_method(*m, 1), "batch handler (warm-up)");
-            }
-            ordered_var_pack(1, true);
-            check(hipMemcpyAsync(_h_out, _d_out, out_cap, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_cls, _d_cls, _max, hipMemcpyDeviceToHost, _s));
-            check(hipMemcpyAsync(_h_status, _d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
-                                 _s));
-            check(hipStreamSynchronize(_s));
-        }
-    }
-
-    /// One string-method batch on one well-formed request with empty strings
-    /// (its prefix, zeros): every kernel of the var path and the handler load
-    /// their code objects here, not on the first batch.
-    void warm_up_var(method_entry& m, size_t k) {
-        std::vector<uint8_t> f = be32(static_cast<uint32_t>(m.min_in));
-        f.insert(f.end(), m.req_prefix.begin(), m.req_prefix.end());
-        f.resize(4 + m.min_in, 0);
-        check(hipMemcpyAsync(_d_in, f.data(), f.size(), hipMemcpyHostToDevice, _s));
-        check(hipMemsetAsync(_d_index, 0, 4, _s));
-        check(hipMemsetAsync(_d_offs, 0, 4, _s));
-        check_srpc(srpc_frames_gather_var(static_cast<const uint8_t*>(_d_in), static_cast<const uint32_t*>(_d_offs),
-                                          static_cast<const uint32_t*>(_d_index), 1, static_cast<uint8_t*>(_d_gather),
-                                          static_cast<uint64_t*>(_d_var_rec), _d_scratch, _scratch_bytes, _s),
-                   "srpc_frames_gather_var");
-        run_var_unpack(m, k, 1, m.min_in);
-        run_var_pack(m, k, 1);
-        check_srpc(srpc_frames_scatter_var(m.resp_wire, m.resp_rec, static_cast<const uint32_t*>(_d_index), 1,
-                                           static_cast<const uint64_t*>(_d_out_off), static_cast<uint8_t*>(_d_out), _s),
-                   "srpc_frames_scatter_var");
-    }
-    /// unpack_var -> handler over n gathered requests (_d_gather, index
-    /// _d_var_rec, at most wire_len bytes) of method k, then the first and last
-    /// offsets of every response string field to m.h_ends (checked against the
-    /// columns' sizes before anything reads the chars: run_var_pack).
-    void run_var_unpack(method_entry& m, size_t k, uint64_t n, uint64_t wire_len) {
-        check_srpc(srpc_gpu_unpack_var(m.in->get(), static_cast<const uint8_t*>(_d_gather), wire_len, n,
-                                       static_cast<const uint64_t*>(_d_var_rec), m.req_cols.data(), m.req_offs.data(),
-                                       _d_status + k, _d_var_scratch, _var_scratch_bytes, _s),
-                   "srpc_gpu_unpack_var");
-        std::vector<const uint64_t*> req_offs(m.req_offs.begin(), m.req_offs.end());
-        var_batch b;
-        b.n = n;
-        b.req_cols = m.req_cols.data();
-        b.req_str_offs = req_offs.data();
-        b.resp_cols = m.resp_cols.data();
-        b.resp_str_offs = m.resp_offs.data();
-        b.resp_cap = m.resp_bytes.data();
-        check_srpc(m.vhandler(b, _s), "batch handler");
+    /// The first and last offsets of every response string field of m's n
+    /// responses to m.h_ends (checked against the columns' sizes before
+    /// anything reads the chars: demote_overflowing).
+    void copy_response_ends(method_entry& m, uint64_t n) {
         for (size_t f = 0; f < m.resp_offs.size(); ++f) {
             if (!m.resp_offs[f]) continue;
             check(hipMemcpyAsync(m.h_ends + 2 * f, m.resp_offs[f], 8, hipMemcpyDeviceToHost, _s));
@@ -1190,386 +926,451 @@ private:
         }
         return true;
     }
+    /// Overflow demotion, after the string methods' handlers and
+    /// copy_response_ends: the sync the ends need; every string method whose
+    /// responses do not fit their columns (max_response_chars) is answered on the
+    /// CPU server for this batch, in place -- its frames become unknown in
+    /// z.h_cls (fetched first unless cls_on_host) and d_cls, its count moves to
+    /// `unknown`.  True when a method was demoted: the caller then brings what
+    /// else its route keeps on the device in line with the new classes.
+    bool demote_overflowing(slot& z, uint64_t nf, bool cls_on_host, uint64_t& unknown, batch_stats& st) {
+        const size_t K = _m.size();
+        check(hipStreamSynchronize(_s));  // the responses' sizes
+        bool demoted[SRPC_FRAMES_MAX_PLANS] = {};
+        bool any = false;
+        for (size_t k = 0; k < K; ++k) {
+            if (!_m[k]->var || !_b.h_counts[k] || var_responses_fit(*_m[k])) continue;
+            demoted[k] = any = true;
+            st.overflow_batches += 1;
+        }
+        if (!any) return false;
+        if (!cls_on_host) {
+            check(hipMemcpyAsync(z.h_cls, _b.d_cls, nf, hipMemcpyDeviceToHost, _s));
+            check(hipStreamSynchronize(_s));
+        }
+        for (uint64_t i = 0; i < nf; ++i)
+            if (z.h_cls[i] != SRPC_FRAME_UNKNOWN && demoted[z.h_cls[i]]) z.h_cls[i] = SRPC_FRAME_UNKNOWN;
+        for (size_t k = 0; k < K; ++k)
+            if (demoted[k]) {
+                unknown += _b.h_counts[k];
+                _b.h_counts[k] = 0;
+            }
+        check(hipMemcpyAsync(_b.d_cls, z.h_cls, nf, hipMemcpyHostToDevice, _s));
+        return true;
+    }
+
+    // -- the bucket route --
+
+    void classify(uint64_t nf, uint64_t used) {
+        const int K = static_cast<int>(_m.size());
+        check_srpc(srpc_frames_classify(_in_plans.data(), _resp_bytes.data(), K, _b.d_in, used, _b.d_offs, nf, _b.d_cls,
+                                        _bk.d_index, _b.d_counts, _bk.d_out_off, _bk.d_scratch, _scratch_bytes, _s),
+                   "srpc_frames_classify");
+        check(hipMemcpyAsync(_b.h_counts, _b.d_counts, 8 * (K + 2), hipMemcpyDeviceToHost, _s));
+    }
+    /// A record method's three steps on n contiguous request frames at src:
+    /// decode into its Req array (status slot st), handler, framed responses from
+    /// its Resp array to dst.  Returns the decode's status (positive for the
+    /// warm-up's zero frame); the handler and the pack throw.
+    int run_record_method(method_entry& m, const uint8_t* src, uint64_t n, srpc_unpack_status* st, uint8_t* dst,
+                          const char* what) {
+        const int rc = m.req_stride <= kRecordFillMax
+                           ? srpc_gpu_unpack_aos_fill(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
+                                                      m.req_loffs.data(), m.req_fill.data(), st, _s)
+                           : srpc_gpu_unpack_aos(m.in->get(), src, n * m.fin, n, m.d_reqs, m.req_stride,
+                                                 m.req_loffs.data(), st, _s);
+        if (rc < 0) return rc;
+        check_srpc(m.rhandler(m.d_reqs, m.d_resps, n, _s), what);
+        check_srpc(srpc_gpu_pack_aos(m.out->get(), m.d_resps, m.resp_stride, m.resp_loffs.data(), n, dst, n * m.fout, _s),
+                   "srpc_gpu_pack_aos");
+        return rc;
+    }
+    /// Fixed-size method k on n contiguous request frames at src: decode,
+    /// handler, framed responses to dst.  (A decode status is positive on the
+    /// warm-up's zero frame: expected, and never sent.)
+    void run_fixed_method(method_entry& m, size_t k, const uint8_t* src, uint64_t n, uint8_t* dst, const char* what) {
+        if (m.rec) {
+            check_srpc(run_record_method(m, src, n, _b.d_status + k, dst, what), "srpc_gpu_unpack_aos");
+            mark("record method");
+            return;
+        }
+        check_srpc(srpc_gpu_unpack(m.in->get(), src, n * m.fin, n, m.req_cols.data(), _b.d_status + k, _s),
+                   "srpc_gpu_unpack");
+        mark("unpack");
+        check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s), what);
+        mark("handler");
+        check_srpc(srpc_gpu_pack(m.out->get(), m.resp_cols.data(), n, dst, n * m.fout, _s), "srpc_gpu_pack");
+        mark("pack");
+    }
+    /// unpack_var -> handler over n gathered requests (d_gather, index
+    /// d_var_rec, at most wire_len bytes) of string method k, then its
+    /// responses' ends to the host.
+    void run_var_unpack(method_entry& m, size_t k, uint64_t n, uint64_t wire_len) {
+        check_srpc(srpc_gpu_unpack_var(m.in->get(), _bk.d_gather, wire_len, n, _bk.d_var_rec, m.req_cols.data(),
+                                       m.req_offs.data(), _b.d_status + k, _bk.d_var_scratch, _var_scratch_bytes, _s),
+                   "srpc_gpu_unpack_var");
+        check_srpc(run_var_handler(m, n), "batch handler");
+        copy_response_ends(m, n);
+    }
     void run_var_pack(method_entry& m, size_t k, uint64_t n) {
-        std::vector<const uint64_t*> resp_offs(m.resp_offs.begin(), m.resp_offs.end());
-        std::vector<const void*> resp_cols(m.resp_cols.begin(), m.resp_cols.end());
-        check_srpc(srpc_gpu_pack_var(m.out->get(), resp_cols.data(), resp_offs.data(), n, m.resp_wire, m.resp_wire_cap,
-                                     m.resp_rec, _d_status + _m.size() + k, _d_var_scratch, _var_scratch_bytes, _s),
+        check_srpc(srpc_gpu_pack_var(m.out->get(), m.c_resp_cols.data(), m.c_resp_offs.data(), n, m.resp_wire,
+                                     m.resp_wire_cap, m.resp_rec, _b.d_status + _m.size() + k, _bk.d_var_scratch,
+                                     _var_scratch_bytes, _s),
                    "srpc_gpu_pack_var");
     }
 
-    void release() {
-        for (auto& m : _m)
-            if (m->var) free_var(*m);
-        for (void* p : {_d_var_rec, _d_var_scratch})
-            if (p) (void)hipFree(p);
-        if (_h_out_off) (void)hipHostFree(_h_out_off);
-        _d_var_rec = _d_var_scratch = nullptr;
-        _h_out_off = nullptr;
-        for (void* p : {_d_in, _d_offs, _d_cls, _d_index, _d_counts, _d_out_off, _d_gather, _d_resp, _d_out,
-                        static_cast<void*>(_d_status), _d_scratch, _d_mix_index, _d_rank})
-            if (p) (void)hipFree(p);
-        _d_mix_index = _d_rank = nullptr;
-        for (void* p : {_d_ov_ends, _d_ov_total, _d_ov_offs, _d_ov_scratch})
-            if (p) (void)hipFree(p);
-        for (void* p : {static_cast<void*>(_h_ov_ends), static_cast<void*>(_h_ov_total), static_cast<void*>(_h_ov_offs)})
-            if (p) (void)hipHostFree(p);
-        _d_ov_ends = _d_ov_total = _d_ov_offs = _d_ov_scratch = nullptr;
-        _h_ov_ends = _h_ov_total = nullptr;
-        _h_ov_offs = nullptr;
-        for (auto& m : _m) m->ord_in.reset(), m->ord_out.reset();
-        for (slot& z : _slots) {
-            for (void* p : {static_cast<void*>(z.h_in), static_cast<void*>(z.h_offs), static_cast<void*>(z.h_out),
-                            static_cast<void*>(z.h_cls), static_cast<void*>(z.h_status)})
-                if (p) (void)hipHostFree(p);
-            if (z.done) (void)hipEventDestroy(z.done);
-            z = slot{};
-        }
-        _nslots = 0;
-        if (_h_counts) (void)hipHostFree(_h_counts);
-        _d_in = _d_offs = _d_cls = _d_index = _d_counts = _d_out_off = _d_gather = _d_resp = _d_out = _d_scratch =
-            nullptr;
-        _d_status = nullptr;
-        _h_in = _h_out = _h_cls = nullptr;
-        _h_offs = nullptr;
-        _h_counts = nullptr;
-        _h_status = nullptr;
-    }
-
-    /// A batch between process_begin and process_end.
-    struct pending {
-        bool valid = false;
-        int slot = 0;
-        uint64_t nf = 0, used = 0, unknown = 0, total = 0;
-        bool any_var = false, mixed = false;
-        bool ov = false;   // the ordered route over string methods: the answers' offsets are _h_ov_offs
-        double gpu_s = 0;  // host time spent on the batch's GPU work (enqueue, syncs, the final wait)
-    };
-    void use_slot(int i) {
-        slot& z = _slots[i];
-        _h_in = z.h_in;
-        _h_offs = z.h_offs;
-        _h_out = z.h_out;
-        _h_cls = z.h_cls;
-        _h_status = z.h_status;
-    }
-
-    /// The GPU path for the nf whole frames in _h_in[0, used): every copy and
-    /// kernel enqueued (with the host syncs the batch's own decisions need:
-    /// its bucket counts, a string method's response sizes), the last copy
-    /// marked by the slot's event.  process_end answers it.
-    pending process_begin(uint64_t nf, uint64_t used, batch_stats& st) {
-        if (_ordered_var) return process_begin_ordered_var(nf, used, st);
-        if (_ordered) return process_begin_ordered(nf, used, st);
-        auto t0 = clock::now();
-        auto mark = [&](const char* what) {
-            if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
-                                    (unsigned long long)nf, what, 1e3 * secs(t0));
-        };
-        const int K = static_cast<int>(_m.size());
-        auto* d_in = static_cast<uint8_t*>(_d_in);
-        auto* d_offs = static_cast<uint32_t*>(_d_offs);
-        auto* d_idx = static_cast<uint32_t*>(_d_index);
-        auto* d_counts = static_cast<uint64_t*>(_d_counts);
-        auto* d_out_off = static_cast<uint64_t*>(_d_out_off);
-        check(hipMemcpyAsync(d_in, _h_in, used, hipMemcpyHostToDevice, _s));
-        check(hipMemcpyAsync(d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
-        mark("h2d");
-        check_srpc(srpc_frames_classify(_in_plans.data(), _resp_bytes.data(), K, d_in, used, d_offs, nf,
-                                        static_cast<uint8_t*>(_d_cls), d_idx, d_counts, d_out_off, _d_scratch,
-                                        _scratch_bytes, _s),
-                   "srpc_frames_classify");
-        check(hipMemcpyAsync(_h_counts, d_counts, 8 * (K + 2), hipMemcpyDeviceToHost, _s));
-        const bool var_methods = !_var_idx.empty();
-        if (var_methods) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
+    /// The bucket route's steps between the H2D and the D2H: classify and the
+    /// first sync, the string methods (their responses' sizes place every
+    /// answer: a second sync, the demotion, the offsets, a third for the reply
+    /// stream's size), then every fixed-size method's bucket.
+    void bucket_steps(slot& z, uint64_t nf, uint64_t used, batch_stats& st, pending& pd) {
+        const size_t K = _m.size();
+        classify(nf, used);
+        if (_var_methods) check(hipMemcpyAsync(z.h_cls, _b.d_cls, nf, hipMemcpyDeviceToHost, _s));
         mark("classify");
         check(hipStreamSynchronize(_s));
         mark("sync1");
-        st.classify_seconds += secs(t0);
-        uint64_t unknown = _h_counts[K + 1];
+        st.classify_seconds += secs(_tp.t0);
+        uint64_t* counts = _b.h_counts;
+        uint64_t unknown = counts[K + 1];
         bool mixed = false, any_var = false;
-        for (int k = 0; k < K; ++k) any_var |= _m[static_cast<size_t>(k)]->var && _h_counts[k] > 0;
+        for (size_t k = 0; k < K; ++k) any_var |= _m[k]->var && counts[k] > 0;
         uint64_t var_bytes[SRPC_FRAMES_MAX_PLANS] = {};  // payload bytes of each string method's frames
         if (any_var)
             for (uint64_t i = 0; i < nf; ++i) {
-                const uint8_t c = _h_cls[i];
-                if (c != SRPC_FRAME_UNKNOWN && _m[c]->var) var_bytes[c] += (i + 1 < nf ? _h_offs[i + 1] : used) - _h_offs[i] - 4;
+                const uint8_t c = z.h_cls[i];
+                if (c != SRPC_FRAME_UNKNOWN && _m[c]->var)
+                    var_bytes[c] += (i + 1 < nf ? z.h_offs[i + 1] : used) - z.h_offs[i] - 4;
             }
-        check(hipMemsetAsync(_d_status, 0, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status), _s));
-        bool demoted[SRPC_FRAMES_MAX_PLANS] = {};  // string methods whose answers go to the CPU this batch
+        clear_status();
         if (any_var) {
-            // string methods first: their responses' sizes place every answer.
-            // unpack + handler, then the responses' sizes are checked on the
-            // host BEFORE anything reads the response chars: a batch whose
-            // answers do not fit the columns (max_response_chars) is answered
-            // on the CPU server instead, in place (its frames become unknown)
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                const uint64_t n = _h_counts[k];
+            for (size_t k = 0; k < K; ++k) {
+                method_entry& m = *_m[k];
+                const uint64_t n = counts[k];
                 if (!m.var || !n) continue;
                 mixed |= n != nf;
-                check_srpc(srpc_frames_gather_var(d_in, d_offs, d_idx + static_cast<uint64_t>(k) * nf, n,
-                                                  static_cast<uint8_t*>(_d_gather), static_cast<uint64_t*>(_d_var_rec),
-                                                  _d_scratch, _scratch_bytes, _s),
+                check_srpc(srpc_frames_gather_var(_b.d_in, _b.d_offs, _bk.d_index + k * nf, n, _bk.d_gather, _bk.d_var_rec,
+                                                  _bk.d_scratch, _scratch_bytes, _s),
                            "srpc_frames_gather_var");
-                run_var_unpack(m, static_cast<size_t>(k), n, var_bytes[k]);
+                run_var_unpack(m, k, n, var_bytes[k]);
                 mark("var unpack");
             }
-            check(hipStreamSynchronize(_s));  // the responses' sizes
-            bool any_demoted = false;
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                if (!m.var || !_h_counts[k] || var_responses_fit(m)) continue;
-                demoted[k] = any_demoted = true;
-                st.overflow_batches += 1;
-            }
-            if (any_demoted) {
-                for (uint64_t i = 0; i < nf; ++i)
-                    if (_h_cls[i] != SRPC_FRAME_UNKNOWN && demoted[_h_cls[i]]) _h_cls[i] = SRPC_FRAME_UNKNOWN;
-                for (int k = 0; k < K; ++k)
-                    if (demoted[k]) {
-                        unknown += _h_counts[k];
-                        _h_counts[k] = 0;
-                    }
-                check(hipMemcpyAsync(_d_cls, _h_cls, nf, hipMemcpyHostToDevice, _s));
-                check(hipMemcpyAsync(d_counts, _h_counts, 8 * static_cast<uint64_t>(K), hipMemcpyHostToDevice, _s));
+            if (demote_overflowing(z, nf, true, unknown, st)) {
+                check(hipMemcpyAsync(_b.d_counts, counts, 8 * K, hipMemcpyHostToDevice, _s));
                 // the copies read pinned memory the next batch rewrites
                 check(hipStreamSynchronize(_s));
             }
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                if (m.var && _h_counts[k]) run_var_pack(m, static_cast<size_t>(k), _h_counts[k]);
-            }
+            for (size_t k = 0; k < K; ++k)
+                if (_m[k]->var && counts[k]) run_var_pack(*_m[k], k, counts[k]);
             mark("var pack");
-            check_srpc(srpc_frames_offsets(_in_plans.data(), _resp_bytes.data(), K, static_cast<const uint8_t*>(_d_cls),
-                                           nf, d_idx, d_counts, _var_rec.data(), d_out_off, d_counts + K, _d_scratch,
-                                           _scratch_bytes, _s),
+            check_srpc(srpc_frames_offsets(_in_plans.data(), _resp_bytes.data(), static_cast<int>(K), _b.d_cls, nf,
+                                           _bk.d_index, _b.d_counts, _var_rec.data(), _bk.d_out_off, _b.d_counts + K,
+                                           _bk.d_scratch, _scratch_bytes, _s),
                        "srpc_frames_offsets");
-            check(hipMemcpyAsync(_h_counts + K, d_counts + K, 8, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(counts + K, _b.d_counts + K, 8, hipMemcpyDeviceToHost, _s));
         }
-        for (int k = 0; k < K; ++k) {
-            const uint64_t n = _h_counts[k];
-            method_entry& m = *_m[static_cast<size_t>(k)];
+        for (size_t k = 0; k < K; ++k) {
+            const uint64_t n = counts[k];
+            method_entry& m = *_m[k];
             if (!n || m.var) continue;
             const bool whole = n == nf;  // every frame is method k: they already are its contiguous records
             mixed |= !whole;
-            const uint8_t* src = d_in;
+            const uint8_t* src = _b.d_in;
             if (!whole) {
-                check_srpc(srpc_frames_gather(d_in, d_offs, d_idx + static_cast<uint64_t>(k) * nf, n,
-                                              static_cast<uint32_t>(m.fin), static_cast<uint8_t*>(_d_gather), _s),
+                check_srpc(srpc_frames_gather(_b.d_in, _b.d_offs, _bk.d_index + k * nf, n, static_cast<uint32_t>(m.fin),
+                                              _bk.d_gather, _s),
                            "srpc_frames_gather");
-                src = static_cast<const uint8_t*>(_d_gather);
+                src = _bk.d_gather;
             }
-            auto* dst = static_cast<uint8_t*>(whole ? _d_out : _d_resp);
-            if (m.rec) {
-                check_srpc(run_record_method(m, src, n, _d_status + k, dst, "batch handler"), "srpc_gpu_unpack_aos");
-                mark("record method");
-            } else {
-                check_srpc(srpc_gpu_unpack(m.in->get(), src, n * m.fin, n, m.req_cols.data(), _d_status + k, _s),
-                           "srpc_gpu_unpack");
-                mark("unpack");
-                check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s), "batch handler");
-                mark("handler");
-                check_srpc(srpc_gpu_pack(m.out->get(), m.resp_cols.data(), n, dst, n * m.fout, _s), "srpc_gpu_pack");
-                mark("pack");
-            }
+            uint8_t* dst = whole ? _b.d_out : _bk.d_resp;
+            run_fixed_method(m, k, src, n, dst, "batch handler");
             if (!whole)
-                check_srpc(srpc_frames_scatter(dst, d_idx + static_cast<uint64_t>(k) * nf, n,
-                                               static_cast<uint32_t>(m.fout), d_out_off, static_cast<uint8_t*>(_d_out),
-                                               _s),
+                check_srpc(srpc_frames_scatter(dst, _bk.d_index + k * nf, n, static_cast<uint32_t>(m.fout), _bk.d_out_off,
+                                               _b.d_out, _s),
                            "srpc_frames_scatter");
         }
         if (any_var) {
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                const uint64_t n = _h_counts[k];
-                if (m.var && n)
-                    check_srpc(srpc_frames_scatter_var(m.resp_wire, m.resp_rec, d_idx + static_cast<uint64_t>(k) * nf,
-                                                       n, d_out_off, static_cast<uint8_t*>(_d_out), _s),
+            for (size_t k = 0; k < K; ++k)
+                if (_m[k]->var && counts[k])
+                    check_srpc(srpc_frames_scatter_var(_m[k]->resp_wire, _m[k]->resp_rec, _bk.d_index + k * nf, counts[k],
+                                                       _bk.d_out_off, _b.d_out, _s),
                                "srpc_frames_scatter_var");
-            }
-            if (unknown) check(hipMemcpyAsync(_h_out_off, d_out_off, 8 * (nf + 1), hipMemcpyDeviceToHost, _s));
+            if (unknown) check(hipMemcpyAsync(_bk.h_out_off, _bk.d_out_off, 8 * (nf + 1), hipMemcpyDeviceToHost, _s));
             check(hipStreamSynchronize(_s));  // the reply stream's size
             mark("sync_var");
+            pd.ends64 = _bk.h_out_off;
         }
-        const uint64_t total = _h_counts[K];
-        if (total) check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, _s));
-        mark("d2h_out");
-        if (unknown && !var_methods) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
-        check(hipMemcpyAsync(_h_status, _d_status, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status),
-                             hipMemcpyDeviceToHost, _s));
-        mark("d2h");
-        pending pd;
-        for (int i = 0; i < _nslots; ++i)
-            if (_slots[i].h_in == _h_in) pd.slot = i;
-        check(hipEventRecord(_slots[pd.slot].done, _s));
-        pd.valid = true;
-        pd.nf = nf;
-        pd.used = used;
         pd.unknown = unknown;
-        pd.total = total;
-        pd.any_var = any_var;
+        pd.total = counts[K];
         pd.mixed = mixed;
-        pd.gpu_s = secs(t0);
-        return pd;
+        pd.cls_on_host = _var_methods;
+        pd.d2h_extra = (unknown || _var_methods ? nf : 0) + (unknown && any_var ? 8 * (nf + 1) : 0);
+    }
+    /// One string-method batch on one well-formed request with empty strings
+    /// (its prefix, zeros): every kernel of the var path and the handler load
+    /// their code objects here, not on the first batch.
+    void warm_up_var(method_entry& m, size_t k) {
+        std::vector<uint8_t> f = m.framed_in;
+        f.resize(4 + m.min_in, 0);
+        check(hipMemcpyAsync(_b.d_in, f.data(), f.size(), hipMemcpyHostToDevice, _s));
+        check(hipMemsetAsync(_bk.d_index, 0, 4, _s));
+        check(hipMemsetAsync(_b.d_offs, 0, 4, _s));
+        check_srpc(srpc_frames_gather_var(_b.d_in, _b.d_offs, _bk.d_index, 1, _bk.d_gather, _bk.d_var_rec, _bk.d_scratch,
+                                          _scratch_bytes, _s),
+                   "srpc_frames_gather_var");
+        run_var_unpack(m, k, 1, m.min_in);
+        run_var_pack(m, k, 1);
+        check_srpc(srpc_frames_scatter_var(m.resp_wire, m.resp_rec, _bk.d_index, 1, _bk.d_out_off, _b.d_out, _s),
+                   "srpc_frames_scatter_var");
+    }
+    /// The bucket route's steps on the warm-up's one all-zero frame: every
+    /// method's bucket as if the frame were its own, through both destinations.
+    void bucket_warm_up_steps() {
+        classify(1, 8);
+        check(hipStreamSynchronize(_s));
+        clear_status();
+        for (size_t k = 0; k < _m.size(); ++k) {
+            method_entry& m = *_m[k];
+            if (m.var) {
+                warm_up_var(m, k);
+                continue;
+            }
+            check_srpc(srpc_frames_gather(_b.d_in, _b.d_offs, _bk.d_index, 1, static_cast<uint32_t>(m.fin), _bk.d_gather, _s),
+                       "srpc_frames_gather");
+            // the handler's own kernels load their code object on first use
+            // too: it runs on the one zero record (its output is never sent)
+            run_fixed_method(m, k, _bk.d_gather, 1, _b.d_out, "batch handler (warm-up)");
+            if (m.rec)  // the same on its struct arrays, into the other destination
+                run_fixed_method(m, k, _bk.d_gather, 1, _bk.d_resp, "batch handler (warm-up)");
+            else
+                check_srpc(srpc_gpu_pack(m.out->get(), m.resp_cols.data(), 1, _bk.d_resp, m.fout, _s), "srpc_gpu_pack");
+            check_srpc(srpc_frames_scatter(_bk.d_resp, _bk.d_index, 1, static_cast<uint32_t>(m.fout), _bk.d_out_off,
+                                           _b.d_out, _s),
+                       "srpc_frames_scatter");
+        }
     }
 
-    /// process_begin in ordered mode: H2D, one decode of every method's frames
-    /// into its request columns at their arrival ranks, the counts and one
-    /// sync, the handlers, one reply pack in arrival order into _d_out, D2H.
-    /// The methods' columns and _d_cls are shared by the two staging slots:
-    /// everything that touches them is in stream order.
-    pending process_begin_ordered(uint64_t nf, uint64_t used, batch_stats& st) {
-        auto t0 = clock::now();
-        auto mark = [&](const char* what) {
-            if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
-                                    (unsigned long long)nf, what, 1e3 * secs(t0));
-        };
+    // -- the ordered routes (set_ordered, set_ordered_var): one decode, the handlers, one pack --
+
+    bool whole_batch_handler() const { return _ordered_var ? bool(_ovhandler) : bool(_ohandler); }
+
+    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed[_var]
+    /// over the nf frames in d_in[0, used) into the methods' request columns
+    /// (chars and offsets too), the ranks when the ordered handler is set, then
+    /// the counts (and the string slots' ends) on the host after one sync.
+    void ordered_decode(uint64_t nf, uint64_t used) {
         const int K = static_cast<int>(_m.size());
-        check(hipMemcpyAsync(_d_in, _h_in, used, hipMemcpyHostToDevice, _s));
-        check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
-        mark("h2d");
+        clear_status();
+        if (_ordered_var)
+            check_srpc(srpc_frames_unpack_requests_mixed_var(
+                           _ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf, _req_tbl.data(), _ov_req_offs.data(),
+                           _ov_req_scap.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, _mix_index_bytes,
+                           _b.d_counts, _ov.d_ends, _b.d_status, _ov.d_scratch, _ov_scratch_bytes, _s),
+                       "srpc_frames_unpack_requests_mixed_var");
+        else
+            check_srpc(srpc_frames_unpack_requests_mixed(_ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf,
+                                                         _req_tbl.data(), nullptr, _caps.data(), _b.d_cls,
+                                                         _od.d_mix_index, _mix_index_bytes, _b.d_counts, _b.d_status, _s),
+                       "srpc_frames_unpack_requests_mixed");
+        if (whole_batch_handler())
+            check_srpc(srpc_frames_mixed_ranks(_od.d_mix_index, _b.d_cls, nf, K, _od.d_rank, _s), "srpc_frames_mixed_ranks");
+        check(hipMemcpyAsync(_b.h_counts, _b.d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
+        if (_ordered_var && _ov_slots)
+            check(hipMemcpyAsync(_ov.h_ends, _ov.d_ends, 8 * _ov_slots, hipMemcpyDeviceToHost, _s));
+        check(hipStreamSynchronize(_s));
+    }
+    /// The ordered handler over the batch of nf frames, or every method's
+    /// handler over its requests in arrival order (warm: over one zero record).
+    void ordered_handlers(uint64_t nf, bool warm) {
+        if (whole_batch_handler()) {
+            const char* what = warm ? "ordered batch handler (warm-up)" : "ordered batch handler";
+            auto fill = [&](auto& b) {
+                b.n = nf;
+                b.d_method = _b.d_cls;
+                b.d_rank = _od.d_rank;
+                b.counts = _b.h_counts;
+                b.methods = _m.size();
+                b.req_cols = _req_tbl.data();
+                b.resp_cols = _resp_mut_tbl.data();
+            };
+            if (_ordered_var) {
+                ordered_var_batch b;
+                fill(b);
+                b.req_str_offs = _ov_c_req_offs.data();
+                b.resp_str_offs = _ov_resp_offs.data();
+                b.resp_cap = _ov_resp_cap.data();
+                check_srpc(_ovhandler(b, _s), what);
+            } else {
+                ordered_batch b;
+                fill(b);
+                check_srpc(_ohandler(b, _s), what);
+            }
+            return;
+        }
+        for (size_t k = 0; k < _m.size(); ++k) {
+            method_entry& m = *_m[k];
+            const uint64_t n = warm ? 1 : _b.h_counts[k];
+            if (!n) continue;
+            check_srpc(m.var ? run_var_handler(m, n) : m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s),
+                       warm ? "batch handler (warm-up)" : "batch handler");
+        }
+    }
+    /// The reply half: the response plans' frames in arrival order straight
+    /// into d_out (an unknown frame gets no bytes: the pack's "bad call",
+    /// answered on the CPU in its place).  With string methods, the stream's
+    /// size and, with unknown frames, every answer's offset go to the host.  No
+    /// sync here.
+    void ordered_pack(uint64_t nf, bool unknown) {
+        const int K = static_cast<int>(_m.size());
+        if (!_ordered_var) {  // (the flag a bad call would raise is not asked for)
+            check_srpc(srpc_frames_pack_requests_mixed(_ord_out_plans.data(), K, _resp_tbl.data(), nullptr, _caps.data(),
+                                                       _b.d_cls, _od.d_mix_index, nf, _b.d_out, out_cap(), nullptr, nullptr,
+                                                       _s),
+                       "srpc_frames_pack_requests_mixed (replies)");
+            return;
+        }
+        // an unknown frame is the pack's "bad call" and would raise its flag: asked for only without one
+        check_srpc(srpc_frames_pack_requests_mixed_var(_ord_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(),
+                                                       nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, nf, _b.d_out,
+                                                       out_cap(), _ov.d_offs, _ov.d_total,
+                                                       unknown ? nullptr : _b.d_status + K, _ov.d_scratch,
+                                                       _ov_scratch_bytes, _s),
+                   "srpc_frames_pack_requests_mixed_var (replies)");
+        check(hipMemcpyAsync(_ov.h_total, _ov.d_total, 8, hipMemcpyDeviceToHost, _s));
+        if (unknown) check(hipMemcpyAsync(_ov.h_offs, _ov.d_offs, 4 * (nf + 1), hipMemcpyDeviceToHost, _s));
+    }
+    /// The ordered routes' steps between the H2D and the D2H.  The methods'
+    /// columns and d_cls are shared by the two staging slots: everything that
+    /// touches them is in stream order.  With string methods: the string
+    /// responses' sizes checked against their columns (a second sync, only when
+    /// a string response exists) before the pack, the total and a sync after.
+    void ordered_steps(slot& z, uint64_t nf, uint64_t used, batch_stats& st, pending& pd) {
+        const size_t K = _m.size();
         ordered_decode(nf, used);
         mark("decode");
-        st.classify_seconds += secs(t0);
-        const uint64_t unknown = _h_counts[K];
-        uint64_t total = 0;
-        bool mixed = false;
-        for (int k = 0; k < K; ++k) {
-            const uint64_t n = _h_counts[k];
-            total += n * _m[static_cast<size_t>(k)]->fout;
+        st.classify_seconds += secs(_tp.t0);
+        uint64_t unknown = _b.h_counts[K], total = 0;
+        bool mixed = false, sized = false;
+        for (size_t k = 0; k < K; ++k) {
+            const uint64_t n = _b.h_counts[k];
+            total += n * _m[k]->fout;  // (the whole of it without string methods)
             mixed |= n && n != nf;
+            sized |= n && _m[k]->var && _m[k]->out_str();
         }
-        if (_ohandler) {
-            check_srpc(run_ordered_handler(nf), "ordered batch handler");
-        } else {
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                if (_h_counts[k])
-                    check_srpc(m.handler(m.req_cols.data(), m.resp_cols.data(), _h_counts[k], _s), "batch handler");
-            }
-        }
+        ordered_handlers(nf, false);
         mark("handler");
-        if (total) {
-            ordered_pack(nf);
-            check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, _s));
+        if (!_ordered_var) {
+            if (total) ordered_pack(nf, false);
+            mark("pack");
+            pd.d2h_extra = unknown ? nf : 0;
+        } else {
+            if (sized) {
+                for (size_t k = 0; k < K; ++k)
+                    if (_m[k]->var && _b.h_counts[k]) copy_response_ends(*_m[k], _b.h_counts[k]);
+                // its frames become unknown; the ranks are per method, so the other methods' elements stay
+                pd.cls_on_host = demote_overflowing(z, nf, false, unknown, st);
+                if (pd.cls_on_host)
+                    check_srpc(srpc_frames_mixed_index(_b.d_cls, nf, static_cast<int>(K), _od.d_mix_index, _mix_index_bytes,
+                                                       _b.d_counts, nullptr, _s),
+                               "srpc_frames_mixed_index");
+                mark("sizes");
+            }
+            ordered_pack(nf, unknown != 0);
+            check(hipStreamSynchronize(_s));  // the reply stream's size
+            total = _ov.h_total[0];
+            if (total > out_cap()) throw plan_error("batch_server: the replies overran the reply buffer", SRPC_E_INVALID);
+            mark("pack");
+            pd.ends32 = _ov.h_offs;
+            pd.d2h_extra = unknown ? nf + 4 * (nf + 1) : 0;
         }
-        mark("pack");
-        if (unknown) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
-        check(hipMemcpyAsync(_h_status, _d_status, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status),
-                             hipMemcpyDeviceToHost, _s));
-        mark("d2h");
-        pending pd;
-        for (int i = 0; i < _nslots; ++i)
-            if (_slots[i].h_in == _h_in) pd.slot = i;
-        check(hipEventRecord(_slots[pd.slot].done, _s));
-        pd.valid = true;
-        pd.nf = nf;
-        pd.used = used;
         pd.unknown = unknown;
         pd.total = total;
         pd.mixed = mixed;
-        pd.gpu_s = secs(t0);
-        return pd;
     }
 
-    /// process_begin on this route: H2D, one decode, the counts and one sync,
-    /// the handlers, the string responses' sizes checked against their columns
-    /// (a second sync, only when a string response exists), one reply pack in
-    /// arrival order, the total and a sync, D2H.
-    pending process_begin_ordered_var(uint64_t nf, uint64_t used, batch_stats& st) {
-        auto t0 = clock::now();
-        auto mark = [&](const char* what) {
-            if (_trace) std::fprintf(stderr, "batch %llu nf %llu %-10s %.3f ms\n", (unsigned long long)st.gpu_batches,
-                                    (unsigned long long)nf, what, 1e3 * secs(t0));
-        };
-        const int K = static_cast<int>(_m.size());
-        check(hipMemcpyAsync(_d_in, _h_in, used, hipMemcpyHostToDevice, _s));
-        check(hipMemcpyAsync(_d_offs, _h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
-        mark("h2d");
-        ordered_var_decode(nf, used);
-        mark("decode");
-        st.classify_seconds += secs(t0);
-        uint64_t unknown = _h_counts[K];
-        bool mixed = false, any_var = false, sized = false;
-        for (int k = 0; k < K; ++k) {
-            const uint64_t n = _h_counts[k];
-            mixed |= n && n != nf;
-            any_var |= n && _m[static_cast<size_t>(k)]->var;
-            sized |= n && _m[static_cast<size_t>(k)]->var && _m[static_cast<size_t>(k)]->out_str();
-        }
-        if (_ovhandler) {
-            check_srpc(run_ordered_var_handler(nf), "ordered batch handler");
+    /// One-frame run of every kernel the batches use (the library's and each
+    /// handler, on one all-zero record -- or the ordered handler on that batch
+    /// of one unknown frame) and one copy through every staging buffer, at
+    /// serve start: first uses cost milliseconds that otherwise land on the
+    /// connection's first batch (profiles/r02_e2e_warmup.log).
+    void warm_up() {
+        slot& z = _slots[0];
+        const uint64_t out_cap = this->out_cap();
+        _tp.on = false;
+        check(hipMemsetAsync(_b.d_out, 0, out_cap + 16, _s));
+        check(hipMemsetAsync(_b.d_cls, 0, _max + 16, _s));
+        if (_ordered) {
+            check(hipMemsetAsync(_od.d_mix_index, 0, _mix_index_bytes + 16, _s));
+            check(hipMemsetAsync(_od.d_rank, 0, 4 * _max + 16, _s));
+            if (_ordered_var) {
+                check(hipMemsetAsync(_ov.d_scratch, 0, _ov_scratch_bytes, _s));
+                check(hipMemsetAsync(_ov.d_offs, 0, 4 * (_max + 1) + 16, _s));
+            }
         } else {
-            for (int k = 0; k < K; ++k)
-                if (_h_counts[k]) check_srpc(run_ordered_var_method(*_m[static_cast<size_t>(k)], _h_counts[k]), "batch handler");
+            check(hipMemsetAsync(_bk.d_resp, 0, out_cap + 16, _s));
+            check(hipMemsetAsync(_bk.d_gather, 0, _cap + 16, _s));
+            check(hipMemsetAsync(_bk.d_index, 0, 4 * _m.size() * _max + 16, _s));
+            check(hipMemsetAsync(_bk.d_out_off, 0, 8 * (_max + 1) + 16, _s));
+            check(hipMemsetAsync(_bk.d_scratch, 0, _scratch_bytes, _s));
+            if (_bk.d_var_scratch) check(hipMemsetAsync(_bk.d_var_scratch, 0, _var_scratch_bytes, _s));
         }
-        mark("handler");
-        bool h_cls_valid = false;
-        if (sized) {
-            // the responses' sizes are checked on the host BEFORE anything reads the response chars: a
-            // method whose answers do not fit its columns is answered on the CPU server instead, in place
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                const uint64_t n = _h_counts[k];
-                if (!m.var || !n) continue;
-                for (size_t f = 0; f < m.resp_offs.size(); ++f) {
-                    if (!m.resp_offs[f]) continue;
-                    check(hipMemcpyAsync(m.h_ends + 2 * f, m.resp_offs[f], 8, hipMemcpyDeviceToHost, _s));
-                    check(hipMemcpyAsync(m.h_ends + 2 * f + 1, m.resp_offs[f] + n, 8, hipMemcpyDeviceToHost, _s));
-                }
+        for (auto const& m : _m) {
+            for (size_t f = 0; f < m->req_cols.size(); ++f) check(hipMemsetAsync(m->req_cols[f], 0, m->req_bytes[f], _s));
+            for (size_t f = 0; f < m->resp_cols.size(); ++f) check(hipMemsetAsync(m->resp_cols[f], 0, m->resp_bytes[f], _s));
+            for (auto const* offs : {&m->req_offs, &m->resp_offs})
+                for (uint64_t* p : *offs)
+                    if (p) check(hipMemsetAsync(p, 0, 8 * (_max + 1), _s));
+        }
+        std::memset(z.h_in, 0, _cap);
+        std::memset(z.h_offs, 0, 4 * _max);
+        // a batch's exact sequence of copies and launches on one all-zero frame
+        // (nobody's), twice (the first pass pays the first uses; whole buffers move)
+        for (int pass = 0; pass < 2; ++pass) {
+            check(hipMemcpyAsync(_b.d_in, z.h_in, _cap, hipMemcpyHostToDevice, _s));
+            check(hipMemcpyAsync(_b.d_offs, z.h_offs, 4 * _max, hipMemcpyHostToDevice, _s));
+            if (_ordered) {
+                ordered_decode(1, std::min<uint64_t>(8, _cap));
+                ordered_handlers(1, true);
+                ordered_pack(1, true);
+            } else {
+                bucket_warm_up_steps();
             }
+            check(hipMemcpyAsync(z.h_out, _b.d_out, out_cap, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(z.h_cls, _b.d_cls, _max, hipMemcpyDeviceToHost, _s));
+            check(hipMemcpyAsync(z.h_status, _b.d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
+                                 _s));
             check(hipStreamSynchronize(_s));
-            bool demoted[SRPC_FRAMES_MAX_PLANS] = {};
-            bool any_demoted = false;
-            for (int k = 0; k < K; ++k) {
-                method_entry& m = *_m[static_cast<size_t>(k)];
-                if (!m.var || !_h_counts[k] || var_responses_fit(m)) continue;
-                demoted[k] = any_demoted = true;
-                st.overflow_batches += 1;
-            }
-            if (any_demoted) {
-                // its frames become unknown; the ranks are per method, so the other methods' elements stay
-                check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
-                check(hipStreamSynchronize(_s));
-                for (uint64_t i = 0; i < nf; ++i)
-                    if (_h_cls[i] != SRPC_FRAME_UNKNOWN && demoted[_h_cls[i]]) _h_cls[i] = SRPC_FRAME_UNKNOWN;
-                for (int k = 0; k < K; ++k)
-                    if (demoted[k]) {
-                        unknown += _h_counts[k];
-                        _h_counts[k] = 0;
-                    }
-                check(hipMemcpyAsync(_d_cls, _h_cls, nf, hipMemcpyHostToDevice, _s));
-                check_srpc(srpc_frames_mixed_index(static_cast<const uint8_t*>(_d_cls), nf, K, _d_mix_index,
-                                                   _mix_index_bytes, static_cast<uint64_t*>(_d_counts), nullptr, _s),
-                           "srpc_frames_mixed_index");
-                h_cls_valid = true;
-            }
-            mark("sizes");
         }
-        ordered_var_pack(nf, unknown != 0);
-        check(hipStreamSynchronize(_s));  // the reply stream's size
-        const uint64_t total = _h_ov_total[0];
-        if (total > out_cap()) throw plan_error("batch_server: the replies overran the reply buffer", SRPC_E_INVALID);
-        mark("pack");
-        if (total) check(hipMemcpyAsync(_h_out, _d_out, total, hipMemcpyDeviceToHost, _s));
-        if (unknown && !h_cls_valid) check(hipMemcpyAsync(_h_cls, _d_cls, nf, hipMemcpyDeviceToHost, _s));
-        check(hipMemcpyAsync(_h_status, _d_status, 2 * static_cast<uint64_t>(K) * sizeof(srpc_unpack_status),
-                             hipMemcpyDeviceToHost, _s));
-        mark("d2h");
+    }
+
+    // ---- the batch skeleton ----
+
+    /// The GPU path for the nf whole frames in slot si's h_in[0, used): every
+    /// copy and kernel enqueued (with the host syncs the batch's own decisions
+    /// need: its counts, a string method's response sizes), the last copy
+    /// marked by the slot's event.  process_end answers it.
+    pending process_begin(int si, uint64_t nf, uint64_t used, batch_stats& st) {
+        slot& z = _slots[si];
+        _tp = {_trace, st.gpu_batches, nf, clock::now()};
+        check(hipMemcpyAsync(_b.d_in, z.h_in, used, hipMemcpyHostToDevice, _s));
+        check(hipMemcpyAsync(_b.d_offs, z.h_offs, 4 * nf, hipMemcpyHostToDevice, _s));
+        mark("h2d");
         pending pd;
-        for (int i = 0; i < _nslots; ++i)
-            if (_slots[i].h_in == _h_in) pd.slot = i;
-        check(hipEventRecord(_slots[pd.slot].done, _s));
+        if (_ordered) ordered_steps(z, nf, used, st, pd);
+        else bucket_steps(z, nf, used, st, pd);
+        if (pd.total) check(hipMemcpyAsync(z.h_out, _b.d_out, pd.total, hipMemcpyDeviceToHost, _s));
+        if (!_ordered) mark("d2h_out");
+        if (pd.unknown && !pd.cls_on_host) check(hipMemcpyAsync(z.h_cls, _b.d_cls, nf, hipMemcpyDeviceToHost, _s));
+        check(hipMemcpyAsync(z.h_status, _b.d_status, 2 * _m.size() * sizeof(srpc_unpack_status), hipMemcpyDeviceToHost,
+                             _s));
+        mark("d2h");
+        check(hipEventRecord(z.done, _s));
         pd.valid = true;
+        pd.slot = si;
         pd.nf = nf;
         pd.used = used;
-        pd.unknown = unknown;
-        pd.total = total;
-        pd.any_var = any_var;
-        pd.mixed = mixed;
-        pd.ov = true;
-        pd.gpu_s = secs(t0);
+        pd.gpu_s = secs(_tp.t0);
+        _tp.on = false;
         return pd;
     }
 
@@ -1577,11 +1378,11 @@ private:
     /// statuses and send its answers: the GPU's in runs, the CPU's in their
     /// places.
     void process_end(int fd, pending const& pd, batch_stats& st) {
-        const int K = static_cast<int>(_m.size());
-        const uint64_t nf = pd.nf, used = pd.used, unknown = pd.unknown, total = pd.total;
-        const bool any_var = pd.any_var, mixed = pd.mixed, var_methods = !_var_idx.empty();
+        slot& z = _slots[pd.slot];
+        const size_t K = _m.size();
+        const uint64_t nf = pd.nf, unknown = pd.unknown, total = pd.total;
         auto t0 = clock::now();
-        check(hipEventSynchronize(_slots[pd.slot].done));
+        check(hipEventSynchronize(z.done));
         if (_trace)
             std::fprintf(stderr, "batch %llu nf %llu wait       %.3f ms\n", (unsigned long long)st.gpu_batches,
                          (unsigned long long)nf, 1e3 * secs(t0));
@@ -1589,26 +1390,25 @@ private:
         // string records to their frame's end), and string responses were
         // checked against their columns before packing: a status here means
         // the buckets and the plans disagree (an internal invariant)
-        for (int k = 0; k < 2 * K; ++k)
-            if (_h_status[k].flags)
+        for (size_t k = 0; k < 2 * K; ++k)
+            if (z.h_status[k].flags)
                 throw plan_error(k < K ? "batch_server: classified frame failed to unpack"
                                        : "batch_server: string responses overran a sized wire",
                                  SRPC_E_INVALID);
         const double dt = pd.gpu_s + secs(t0);
         if (st.gpu_batches == 0 && st.fallback_requests == 0) st.first_batch_seconds = dt;
         st.gpu_seconds += dt;
-        st.h2d_bytes += used + 4 * nf;
-        st.d2h_bytes += pd.ov ? total + (unknown ? nf + 4 * (nf + 1) : 0)
-                              : total + (unknown || var_methods ? nf : 0) + (unknown && any_var ? 8 * (nf + 1) : 0);
+        st.h2d_bytes += pd.used + 4 * nf;
+        st.d2h_bytes += total + pd.d2h_extra;
         if (total) {
             st.gpu_batches += 1;
-            st.mixed_batches += mixed ? 1 : 0;
+            st.mixed_batches += pd.mixed ? 1 : 0;
         }
         st.gpu_requests += nf - unknown;
         st.requests += nf - unknown;
         auto t1 = clock::now();
         if (!unknown) {
-            transport::send_all(fd, _h_out, total);
+            transport::send_all(fd, z.h_out, total);
             st.send_seconds += secs(t1);
             return;
         }
@@ -1618,37 +1418,37 @@ private:
         _pieces.clear();
         uint64_t run = 0, pos = 0;
         for (uint64_t i = 0; i < nf; ++i) {
-            const uint8_t c = _h_cls[i];
+            const uint8_t c = z.h_cls[i];
             if (c != SRPC_FRAME_UNKNOWN) {
                 // the end of frame i's answer
-                run = pd.ov ? _h_ov_offs[i + 1] : any_var ? _h_out_off[i + 1] : run + _m[c]->fout;
-                if (pd.ov && _h_ov_offs[i + 1] == _h_ov_offs[i])
+                run = pd.ends32 ? pd.ends32[i + 1] : pd.ends64 ? pd.ends64[i + 1] : run + _m[c]->fout;
+                if (pd.ends32 && pd.ends32[i + 1] == pd.ends32[i])
                     throw plan_error("batch_server: a handler's response offsets decrease", SRPC_E_INVALID);
                 continue;
             }
             if (run > pos) _pieces.push_back({true, pos, run - pos});
             pos = run;
-            const uint64_t o = _h_offs[i];
+            const uint64_t o = z.h_offs[i];
             const uint64_t a0 = _arena.size();
-            answer_cpu(_h_in + o + 4, be32_at(_h_in + o), st);
+            answer_cpu(z.h_in + o + 4, be32_at(z.h_in + o), st);
             _pieces.push_back({false, a0, _arena.size() - a0});
         }
         if (run > pos) _pieces.push_back({true, pos, run - pos});
-        send_pieces(fd);
+        send_pieces(fd, z.h_out);
         st.send_seconds += secs(t1);
     }
 
     struct piece {
-        bool gpu;  // _h_out or _arena
+        bool gpu;  // h_out or _arena
         uint64_t off, len;
     };
 
     /// sendmsg over the pieces, IOV_MAX at a time, resuming partial sends.
-    void send_pieces(int fd) {
+    void send_pieces(int fd, uint8_t* h_out) {
         if (_pieces.size() > 4096) {  // many short runs: one copy beats ~170 ns per iovec in the kernel
             _flat.resize(0);
             for (piece const& p : _pieces) {
-                const uint8_t* b = (p.gpu ? _h_out : _arena.data()) + p.off;
+                const uint8_t* b = (p.gpu ? h_out : _arena.data()) + p.off;
                 _flat.insert(_flat.end(), b, b + p.len);
             }
             transport::send_all(fd, _flat.data(), _flat.size());
@@ -1657,7 +1457,7 @@ private:
         std::vector<iovec> iov;
         iov.reserve(_pieces.size());
         for (piece const& p : _pieces)
-            iov.push_back({(p.gpu ? _h_out : _arena.data()) + p.off, static_cast<size_t>(p.len)});
+            iov.push_back({(p.gpu ? h_out : _arena.data()) + p.off, static_cast<size_t>(p.len)});
         size_t at = 0;
         while (at < iov.size()) {
             msghdr mh{};
@@ -1676,11 +1476,11 @@ private:
     }
 
     /// A frame longer than the batch buffer: `have` bytes of it are at the
-    /// start of _h_in; read the rest and answer it on the CPU.  False at EOF.
-    bool serve_oversize(int fd, uint64_t have, batch_stats& st) {
-        const uint64_t len = be32_at(_h_in);
+    /// start of h_in; read the rest and answer it on the CPU.  False at EOF.
+    bool serve_oversize(int fd, const uint8_t* h_in, uint64_t have, batch_stats& st) {
+        const uint64_t len = be32_at(h_in);
         std::vector<uint8_t> payload(len);
-        std::memcpy(payload.data(), _h_in + 4, have - 4);
+        std::memcpy(payload.data(), h_in + 4, have - 4);
         auto t0 = clock::now();
         const bool ok = transport::recv_all(fd, payload.data() + (have - 4), len - (have - 4));
         st.recv_seconds += secs(t0);
@@ -1719,63 +1519,35 @@ private:
     int _dev;
     hipStream_t _s = nullptr;
     std::vector<std::unique_ptr<method_entry>> _m;
-    std::vector<const srpc_plan*> _in_plans;
-    std::vector<uint32_t> _resp_bytes;
     std::vector<uint8_t> _arena;  // CPU answers of the batch being sent
     std::vector<piece> _pieces;
     std::vector<uint8_t> _flat;
-    uint64_t _cap = 0, _scratch_bytes = 0;
     bool _trace = std::getenv("SRPC_SERVER_TRACE") != nullptr;  // per-recv / per-batch timeline on stderr
-    // the staging slot in use (the pinned buffers of _slots[i], use_slot)
-    uint8_t* _h_in = nullptr;
-    uint32_t* _h_offs = nullptr;
-    uint8_t* _h_out = nullptr;
-    uint8_t* _h_cls = nullptr;
-    uint64_t* _h_counts = nullptr;
-    srpc_unpack_status* _h_status = nullptr;
-    struct slot {
-        uint8_t* h_in = nullptr;
-        uint32_t* h_offs = nullptr;
-        uint8_t* h_out = nullptr;
-        uint8_t* h_cls = nullptr;
-        srpc_unpack_status* h_status = nullptr;
-        hipEvent_t done = nullptr;  // the batch's last copy
-    };
+    trace_point _tp;
+    bool _ordered = false, _ordered_var = false;
+    ordered_handler_t _ohandler;
+    ordered_var_handler_t _ovhandler;
+    // the buffers (ensure / release)
     slot _slots[2];
     int _nslots = 0;
-    void *_d_in = nullptr, *_d_offs = nullptr, *_d_cls = nullptr, *_d_index = nullptr, *_d_counts = nullptr,
-         *_d_out_off = nullptr, *_d_gather = nullptr, *_d_resp = nullptr, *_d_out = nullptr, *_d_scratch = nullptr;
-    srpc_unpack_status* _d_status = nullptr;
-    // ordered mode
-    bool _ordered = false;
-    ordered_handler_t _ohandler;
-    void *_d_mix_index = nullptr, *_d_rank = nullptr;
-    uint64_t _mix_index_bytes = 0;
-    std::vector<const srpc_plan*> _out_plans;             // the framed response plans
-    std::vector<uint64_t> _caps;                          // elements of every method's columns (_max)
-    std::vector<void* const*> _req_tbl, _resp_mut_tbl;    // per method: its request / response columns
-    std::vector<std::vector<const void*>> _const_resp;
+    batch_buffers _b;
+    bucket_buffers _bk;
+    ordered_buffers _od;
+    ordered_var_buffers _ov;
+    uint64_t _cap = 0, _scratch_bytes = 0, _var_scratch_bytes = 0, _mix_index_bytes = 0, _ov_scratch_bytes = 0;
+    bool _var_methods = false;  // a string method is registered
+    uint32_t _ov_slots = 0;     // string leaves of all requests
+    // per method, in registration order (build_tables)
+    std::vector<const srpc_plan*> _in_plans;                  // classify's: `in`
+    std::vector<const srpc_plan*> _ord_in_plans, _ord_out_plans;  // the ordered routes' decode and pack
+    std::vector<uint32_t> _resp_bytes;                        // fout
+    std::vector<const uint64_t*> _var_rec;                    // its response index (nullptr: fixed)
+    std::vector<uint64_t> _caps;                              // elements of its columns (_max)
+    std::vector<void* const*> _req_tbl, _resp_mut_tbl;        // its request / response columns
     std::vector<const void* const*> _resp_tbl;
-    // ordered mode with string methods
-    bool _ordered_var = false;
-    ordered_var_handler_t _ovhandler;
-    std::vector<const srpc_plan*> _ov_in_plans, _ov_out_plans;
-    std::vector<uint64_t* const*> _ov_req_offs;            // per method: its request leaves' offsets arrays
+    std::vector<uint64_t* const*> _ov_req_offs, _ov_resp_offs;  // its leaves' offsets arrays
     std::vector<const uint64_t* const*> _ov_c_req_offs, _ov_c_resp_offs;
-    std::vector<uint64_t* const*> _ov_resp_offs;
-    std::vector<const uint64_t*> _ov_req_scap, _ov_resp_cap;
-    uint32_t _ov_slots = 0;                                 // string leaves of all requests
-    void *_d_ov_ends = nullptr, *_d_ov_total = nullptr, *_d_ov_offs = nullptr, *_d_ov_scratch = nullptr;
-    uint64_t *_h_ov_ends = nullptr, *_h_ov_total = nullptr;
-    uint32_t* _h_ov_offs = nullptr;
-    uint64_t _ov_scratch_bytes = 0;
-    // string methods
-    std::vector<const uint64_t*> _var_rec;  // per method: its response index (nullptr: fixed)
-    std::vector<size_t> _var_idx;           // the string methods' slots
-    void* _d_var_rec = nullptr;             // the request index of the bucket being served
-    void* _d_var_scratch = nullptr;
-    uint64_t _var_scratch_bytes = 0;
-    uint64_t* _h_out_off = nullptr;
+    std::vector<const uint64_t*> _ov_req_scap, _ov_resp_cap;  // bytes a decode may fill / of its response columns
 };
 
 }  // namespace srpc::gpu

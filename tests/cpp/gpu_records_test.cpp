@@ -24,6 +24,8 @@
 #include <thread>
 #include <vector>
 
+#include "served_socketpair.hpp"
+
 static int g_fail = 0, g_pass = 0;
 #define CHECK(c)                                                                    \
     do {                                                                            \
@@ -208,27 +210,8 @@ static void register_all(srpc::gpu::batch_server& srv) {
 
 // A batch_server (two record methods, one column method, no fallback) on one
 // end of a socketpair, on a thread.
-struct served_pair {
-    int fd = -1, sfd = -1;
-    std::thread t;
-    srpc::gpu::batch_stats stats;
-    explicit served_pair(uint64_t batch = kBatch) {
-        int sv[2];
-        if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
-        fd = sv[0];
-        sfd = sv[1];
-        t = std::thread([this, batch] {
-            srpc::gpu::batch_server srv(batch);
-            register_all(srv);
-            stats = srv.serve_connection(sfd);
-            close(sfd);
-        });
-    }
-    void finish() {
-        shutdown(fd, SHUT_WR);
-        t.join();
-        close(fd);
-    }
+struct served_pair : served_socketpair {
+    explicit served_pair(uint64_t batch = kBatch) : served_socketpair(batch, register_all) {}
 };
 
 static uint64_t mix(uint64_t i) {

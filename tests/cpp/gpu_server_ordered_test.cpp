@@ -29,6 +29,8 @@
 #include <thread>
 #include <vector>
 
+#include "served_socketpair.hpp"
+
 static int g_fail = 0, g_pass = 0;
 #define CHECK(c)                                                                    \
     do {                                                                            \
@@ -94,32 +96,9 @@ struct Divider_servicer : srpc::servicer_base {
 };
 
 // A batch_server on one end of a socketpair, on a thread.
-struct served_pair {
-    int fd = -1, sfd = -1;
-    std::thread t;
-    srpc::gpu::batch_stats stats;
-    int thrown = 0;
-    explicit served_pair(std::function<void(srpc::gpu::batch_server&)> setup, srpc::server* fallback = nullptr) {
-        int sv[2];
-        if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
-        fd = sv[0];
-        sfd = sv[1];
-        t = std::thread([this, setup, fallback] {
-            srpc::gpu::batch_server srv(kBatch, 0, fallback);
-            setup(srv);
-            try {
-                stats = srv.serve_connection(sfd);
-            } catch (srpc::gpu::plan_error const& e) {
-                thrown = e.code;
-            }
-            close(sfd);
-        });
-    }
-    void finish() {
-        shutdown(fd, SHUT_WR);
-        t.join();
-        close(fd);
-    }
+struct served_pair : served_socketpair {
+    explicit served_pair(std::function<void(srpc::gpu::batch_server&)> setup, srpc::server* fallback = nullptr)
+        : served_socketpair(kBatch, std::move(setup), fallback) {}
 };
 
 static uint64_t mix64(uint64_t x) {

@@ -22,39 +22,16 @@
 // the server's stream, copy the batch's columns out, compute, and copy back.
 // The messages, columns and reply checks are mixed_var_fixture.hpp's.
 #include "mixed_var_fixture.hpp"
+#include "served_socketpair.hpp"
 
 #include <srpc/server.hpp>
 
 constexpr uint64_t kSrvBatch = 1024;  // both sides: several batches per call
 
 // A batch_server on one end of a socketpair, on a thread.
-struct ordered_pair {
-    int fd = -1, sfd = -1;
-    std::thread t;
-    srpc::gpu::batch_stats stats;
-    int thrown = 0;
-    explicit ordered_pair(std::function<void(srpc::gpu::batch_server&)> setup, srpc::server* fallback = nullptr) {
-        int sv[2];
-        if (socketpair(AF_UNIX, SOCK_STREAM, 0, sv) != 0) std::exit(2);
-        fd = sv[0];
-        sfd = sv[1];
-        t = std::thread([this, setup, fallback] {
-            srpc::gpu::batch_server srv(kSrvBatch, 0, fallback);
-            setup(srv);
-            try {
-                stats = srv.serve_connection(sfd);
-            } catch (srpc::gpu::plan_error const& e) {
-                thrown = e.code;
-                std::fprintf(stderr, "server: %s\n", e.what());
-            }
-            close(sfd);
-        });
-    }
-    void finish() {
-        shutdown(fd, SHUT_WR);
-        t.join();
-        close(fd);
-    }
+struct ordered_pair : served_socketpair {
+    explicit ordered_pair(std::function<void(srpc::gpu::batch_server&)> setup, srpc::server* fallback = nullptr)
+        : served_socketpair(kSrvBatch, std::move(setup), fallback) {}
 };
 
 // ---- (a), (c): per-method handlers that keep what they saw ------------------------------------
