@@ -54,7 +54,14 @@
 // column's capacity is never passed, and an overflow throws SRPC_E_CAPACITY
 // once the chunk is accounted for.  Both overloads are one chunk loop too: the
 // pack call (and where the chunk's request bytes are read), the decode call and
-// the string capacities are its only branches on `any_var`.
+// the string capacities are its only branches on `any_var`.  With struct-array
+// legs (`leg_records`, call_records' form: every leg of the call, fixed-size Req
+// and Resp) the same loop makes srpc_frames_pack_requests_mixed_aos and
+// srpc_frames_unpack_replies_mixed_aos its pack and decode calls: call i's
+// request is the next struct of its leg's request array and its reply is
+// written whole into the next struct of its reply array, so a trace over
+// objects keeps its call order and its one exchange per chunk without a column
+// copy of any message.
 //
 // Every loop counts a chunk's replies by one rule (tally_replies,
 // reply_walk.hpp): from the codes when the decode flagged nothing, otherwise
@@ -125,6 +132,13 @@ struct mixed_leg {
     uint64_t* const* d_resp_str_offs = nullptr;        // per reply leaf, calls + 1 entries each
     const uint64_t* resp_cap = nullptr;                // per reply leaf: the bytes a string column has
     const std::vector<uint8_t>* resp_leaf = nullptr;   // reply leaf bytes, 0: a string
+    // struct-array legs (batch_client::leg_records); the column pointers above stay null
+    bool records = false;
+    const void* d_req_recs = nullptr;
+    void* d_resp_recs = nullptr;
+    uint64_t req_stride = 0, resp_stride = 0;          // sizeof(Req), sizeof(Resp)
+    std::vector<uint32_t> req_offs, resp_offs;         // leaf_offsets<Req>(), leaf_offsets<Resp>()
+    std::vector<uint8_t> proto;                        // resp_stride bytes: every reply byte no leaf covers
 };
 
 class batch_client {
@@ -264,6 +278,39 @@ public:
                         calls);
     }
 
+    /// A leg from and into device arrays of the caller's own structs (fixed-size
+    /// Req and Resp; a string schema or sizeof(Resp) > 256 throws plan_error
+    /// SRPC_E_UNSUPPORTED before anything is allocated): call r of the leg (in
+    /// batch order) takes its request from d_reqs[r] (leaf_offsets<Req>()) and
+    /// leaves its reply in d_resps[r], written whole by
+    /// srpc_frames_unpack_replies_mixed_aos -- the reply's leaves (zero unless
+    /// the reply is a full frame, as a column leg gets zero fields; unanswered
+    /// calls likewise, with RPC_ERR_RECV_TIMEOUT), every other byte from `proto`,
+    /// whose bytes the leg keeps.  Both arrays are 16-byte aligned and hold
+    /// `calls` structs.  The plans are call()'s, cached by this client.  Every
+    /// leg of a call_mixed must then be a record leg: beside a column leg or a
+    /// leg_var leg the call throws plan_error(SRPC_E_UNSUPPORTED) before anything
+    /// is sent.  No transpose, on the host or on the device.  Device code must
+    /// not call a virtual function on a d_resps[r]: its vtable slot holds proto's
+    /// host pointer.
+    template <SrpcMessage Req, SrpcMessage Resp>
+    mixed_leg leg_records(std::string const& method, const Req* d_reqs, Resp* d_resps, uint64_t calls,
+                          const Resp& proto = Resp{}) {
+        check(hipSetDevice(_dev));
+        if (sizeof(Resp) > 256) throw plan_error("batch_client::leg_records (sizeof(Resp) > 256)", SRPC_E_UNSUPPORTED);
+        entry& e = plans<Req, Resp>(method);  // string schemas are refused here, before a plan is built
+        mixed_leg l = make_leg(e, nullptr, nullptr, nullptr, nullptr, nullptr, calls);
+        l.records = true;
+        l.d_req_recs = d_reqs;
+        l.d_resp_recs = d_resps;
+        l.req_stride = sizeof(Req);
+        l.resp_stride = sizeof(Resp);
+        l.req_offs = leaf_offsets<Req>();
+        l.resp_offs = leaf_offsets<Resp>();
+        l.proto.assign(reinterpret_cast<const uint8_t*>(&proto), reinterpret_cast<const uint8_t*>(&proto) + sizeof(Resp));
+        return l;
+    }
+
     /// n calls in the caller's order over at most SRPC_FRAMES_MAX_PLANS legs:
     /// call i is the next call of legs[d_method[i]] (d_method: n device bytes);
     /// d_codes[i] receives its status code.  The frames leave in call order,
@@ -296,7 +343,14 @@ public:
         if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
             throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
         bool any_var = false;
-        for (mixed_leg const& l : legs) any_var = any_var || l.req_var || l.resp_var;
+        size_t nrec = 0;
+        for (mixed_leg const& l : legs) {
+            any_var = any_var || l.req_var || l.resp_var;
+            nrec += l.records;
+        }
+        const bool recs = nrec != 0;  // struct-array legs: all of them, or none
+        if (recs && (nrec != K || any_var))
+            throw plan_error("batch_client::call_mixed (record legs beside column legs)", SRPC_E_UNSUPPORTED);
         uint64_t fin = any_var ? lim.max_request_bytes : 0, fout = any_var ? lim.max_reply_bytes : 0;
         std::vector<const srpc_plan*> rq(K), rs(K);
         std::vector<const void* const*> rqc(K);
@@ -307,11 +361,24 @@ public:
         std::vector<const uint64_t*> scapp(K, nullptr);
         std::vector<uint64_t> first(K, 0), cap(K), slot_cap;
         std::vector<mixed_reply_plan> judge(K);
+        std::vector<const void*> qrec(K), fill(K);
+        std::vector<void*> srec(K);
+        std::vector<uint64_t> qstride(K), sstride(K);
+        std::vector<const uint32_t*> qoff(K), soff(K);
         for (size_t k = 0; k < K; ++k) {
             mixed_leg const& l = legs[k];
-            if (!l.req || !l.resp || !l.resp_prefix || !l.d_req_cols || !l.d_resp_cols ||
+            if (!l.req || !l.resp || !l.resp_prefix ||
+                (recs ? (l.calls && (!l.d_req_recs || !l.d_resp_recs)) || l.proto.size() != l.resp_stride
+                      : !l.d_req_cols || !l.d_resp_cols) ||
                 (l.req_var && !l.d_req_str_offs) || (l.resp_var && (!l.d_resp_str_offs || !l.resp_cap || !l.resp_leaf)))
                 throw plan_error("batch_client::call_mixed (leg)", SRPC_E_INVALID);
+            qrec[k] = l.d_req_recs;
+            srec[k] = l.d_resp_recs;
+            qstride[k] = l.req_stride;
+            sstride[k] = l.resp_stride;
+            qoff[k] = l.req_offs.data();
+            soff[k] = l.resp_offs.data();
+            fill[k] = l.proto.data();
             fin = std::max(fin, l.fin);
             fout = std::max(fout, l.fout);
             rq[k] = l.req;
@@ -344,6 +411,12 @@ public:
         else ensure(fin, fout);
         ensure_mixed();
         if (any_var) ensure_mixed_var(rq.data(), rs.data(), nk);
+        if (recs) {  // the decode's tables and fills
+            uint64_t b = 0;
+            check_srpc(srpc_frames_mixed_aos_scratch_bytes(rs.data(), nk, sstride.data(), &b),
+                       "srpc_frames_mixed_aos_scratch_bytes");
+            ensure_vscratch(b);
+        }
         const uint64_t out_cap = std::min<uint64_t>(_out_cap, (1ull << 32) - 1);
         const size_t nslots = slot_cap.size();
         uint64_t* const h_counts = _s.h_mcounts;
@@ -362,6 +435,11 @@ public:
                                                                d_method + lo, _s.d_mindex, m, _s.d_out, out_cap, _s.d_moffs,
                                                                _s.d_mv, _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
                            "srpc_frames_pack_requests_mixed_var");
+            else if (recs)
+                check_srpc(srpc_frames_pack_requests_mixed_aos(rq.data(), nk, qrec.data(), qstride.data(), qoff.data(),
+                                                               first.data(), cap.data(), d_method + lo, _s.d_mindex, m,
+                                                               _s.d_out, _out_cap, _s.d_moffs, _s.d_status, stream),
+                           "srpc_frames_pack_requests_mixed_aos");
             else
                 check_srpc(srpc_frames_pack_requests_mixed(rq.data(), nk, rqc.data(), first.data(), cap.data(), d_method + lo,
                                                            _s.d_mindex, m, _s.d_out, _out_cap, _s.d_moffs, _s.d_status, stream),
@@ -412,6 +490,13 @@ public:
                                                                 d_codes + lo, _s.d_mv + 1, _s.d_status, _s.d_vscratch,
                                                                 _s.vscratch_cap, stream),
                            "srpc_frames_unpack_replies_mixed_var");
+            else if (recs)
+                check_srpc(srpc_frames_unpack_replies_mixed_aos(rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo,
+                                                                _s.d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
+                                                                srec.data(), sstride.data(), soff.data(), fill.data(),
+                                                                first.data(), cap.data(), d_codes + lo, _s.d_status,
+                                                                _s.d_vscratch, _s.vscratch_cap, stream),
+                           "srpc_frames_unpack_replies_mixed_aos");
             else
                 check_srpc(srpc_frames_unpack_replies_mixed(rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo,
                                                             _s.d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),

@@ -754,6 +754,88 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
                                      const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
                                      srpc_unpack_status* d_status, void* stream);
 
+/* ---- batches of calls of several methods from struct arrays, in call order
+ * (client side; added within ABI 8) ---------------------------------------------
+ * srpc_frames_pack_requests_mixed and srpc_frames_unpack_replies_mixed with
+ * one device array of the caller's own structs per plan in place of its
+ * columns.  Everything that is not about where a call's fields live is the
+ * section above, unchanged: K, the fixed-size plans with framed prefixes,
+ * d_method, rank(i), h_first, h_cap, BAD calls, the call index of
+ * srpc_frames_mixed_index (used as it is), the reply table of
+ * srpc_frames_unpack_replies per call's own plan, SRPC_REPLY_NO_CODE and the
+ * status rules.
+ *
+ * Structs: plan k's calls live in d_recs[k] (host array of K device pointers,
+ * 16-byte aligned), h_stride[k] bytes each, leaf f of the plan's field order at
+ * byte h_leaf_offs[k][f] (u32); the conventions of srpc_gpu_pack_aos /
+ * srpc_gpu_unpack_aos_fill: natural alignment, no two leaves sharing a byte, no
+ * leaf past the stride.  Call i's struct is element h_first[k] + rank(i);
+ * h_cap[k] is the elements the array has.
+ *
+ * srpc_frames_pack_requests_mixed_aos: the output bytes, d_offs, the status,
+ * the handling of BAD calls and of out_cap are the column call's on the same
+ * values.  Only leaf bytes of the chunk's own structs are read; h_stride[k] is
+ * any value below 2^32.  One launch; no scratch.
+ *
+ * srpc_frames_unpack_replies_mixed_aos: d_codes, the flags and
+ * first_bad_record are the column call's on the same input.  h_fill[k] is
+ * h_stride[k] <= 256 host bytes (e.g. the image of a Resp{}), copied during the
+ * call.  Every struct of the chunk's ncalls calls that is not BAD is written
+ * whole, exactly once, and never read: leaf bytes get the frame's values for a
+ * full frame, zero for any other frame and for calls nframes <= i < ncalls
+ * (which also get unanswered_code); every other byte comes from plan k's fill.
+ * No byte outside elements [h_first[k], h_first[k] + calls of k in the chunk)
+ * of any array is written, and nothing is written for a BAD call.
+ * d_scratch (16-byte aligned, srpc_frames_mixed_aos_scratch_bytes: the plans'
+ * per-struct-byte source tables and fills, 3 S16 + 16 bytes per plan, S16 =
+ * h_stride[k] rounded up to 16) receives them by by-value launches: no host
+ * copy outlives the call.
+ *
+ * Both calls are stream-ordered, allocate nothing, wait on nothing on the host
+ * or the device and can be captured; their launches (pack: one; decode: status
+ * reset, one per 2 KiB of scratch, one decode) do not depend on the data; work
+ * is bounded as the column calls state.
+ *
+ * The decode's workgroup takes srpc_frames_mixed_aos_tile calls: the rule of
+ * srpc_frames_mixed_tile with the scratch bytes taken out of the 32 KiB image.
+ * It stages and judges as the column kernel; then, the good calls of one plan
+ * being consecutive elements of its array, it assembles every 16-byte piece of
+ * those K slices from the image, zero or the fill through the plan's table and
+ * stores it whole; a slice's first and last bytes that share a piece with a
+ * neighbouring tile's slice are stored bytewise.
+ *
+ * Refused with nothing launched, in this order:
+ *   1. SRPC_E_INVALID (before any plan is read): the column calls' NULL and
+ *      range checks with d_recs, h_stride, h_leaf_offs, h_leaf_offs[k], h_fill,
+ *      h_fill[k], d_scratch and d_recs[k] (where h_cap[k] leaves an element)
+ *      among the pointers; h_stride[k] == 0 or >= 2^32;
+ *   2. SRPC_E_UNSUPPORTED: a string plan, a short prefix, more than
+ *      SRPC_FRAMES_MIXED_MAX_FIELDS leaves, a decode stride above 256;
+ *   3. SRPC_E_INVALID: overlapping leaves, or a leaf past the stride;
+ *   4. SRPC_E_ALIGN: d_buf, d_out, an array, d_scratch (16), the index (8),
+ *      d_offs (4), or an offset or stride against its leaf's size;
+ *   5. SRPC_E_CAPACITY: scratch_bytes or out_cap. */
+int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+                                        uint64_t* out);
+/* Testing hook: calls per workgroup tile of the decode (the pack's is srpc_frames_mixed_tile). */
+int srpc_frames_mixed_aos_tile(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+                               uint32_t* calls_per_tile);
+int srpc_frames_pack_requests_mixed_aos(const srpc_plan* const* req_plans, int nplans,
+                                        const void* const* d_recs, const uint64_t* h_stride,
+                                        const uint32_t* const* h_leaf_offs, const uint64_t* h_first,
+                                        const uint64_t* h_cap, const uint8_t* d_method, const void* d_index,
+                                        uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                        uint32_t* d_offs /* ncalls + 1, may be NULL */,
+                                        srpc_unpack_status* d_status, void* stream);
+int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                         uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                         const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                         uint8_t unanswered_code, void* const* d_recs, const uint64_t* h_stride,
+                                         const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+                                         const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                         srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                         void* stream);
+
 /* ---- batches of request frames of several methods, in arrival order (server
  * side; added within ABI 8) ------------------------------------------------------
  * The server's counterpart of the section above: where srpc_frames_classify

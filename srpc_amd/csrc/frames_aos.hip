@@ -36,6 +36,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "aos_pieces.h"
 #include "plan.h"
 #include "srpc_gpu.h"
 
@@ -43,13 +44,7 @@ namespace srpc_impl {
 namespace {
 
 constexpr uint32_t kReplyTileBytes = 16384;   // LDS budget of image + table + fill, as the column kernel's image
-constexpr uint32_t kPosZero = 0xffffffffu;    // pos[j]: the frame's leaves are zero
-constexpr uint32_t kPosGlobal = 0xfffffffeu;  // pos[j]: a full frame outside the image
 constexpr int kReplyLoads = 4;                // 16-byte loads in flight per lane
-constexpr uint32_t kAosMaxStride = 256;
-constexpr uint32_t kSrcFill = 0xfff;          // table entry: the byte comes from the fill record
-
-typedef uint32_t ra_u32x4 __attribute__((ext_vector_type(4)));
 
 struct ReplyAosArgs {
     const uint8_t* prefix;  // the plan's device prefix (zero-padded 16 bytes past its end)
@@ -60,8 +55,6 @@ struct ReplyAosArgs {
     uint16_t tab[kAosMaxStride];      // struct byte k: (run bytes from k on, 1..8) << 12 | wire offset or kSrcFill
     uint32_t fillw[kAosMaxStride / 4];  // the fill record (stride bytes, zero padded)
 };
-
-inline uint32_t s16_of(uint32_t stride) { return (stride + 15) & ~15u; }
 
 // Frames per tile: the column kernel's rule with the table's and the fill's
 // bytes (2 S16 + S16, and their padding: under S16) taken out of the image's
@@ -78,17 +71,6 @@ inline size_t reply_aos_lds_bytes(uint32_t F, uint32_t prefix_len, uint32_t R, u
 __device__ __forceinline__ uint32_t be32_at(const uint8_t* b) {
     return (static_cast<uint32_t>(b[0]) << 24) | (static_cast<uint32_t>(b[1]) << 16) |
            (static_cast<uint32_t>(b[2]) << 8) | static_cast<uint32_t>(b[3]);
-}
-
-// The k <= 8 low bytes of v into bytes [b, b + k) of the 16-byte piece lo | hi.
-__device__ __forceinline__ void piece_put(uint64_t& lo, uint64_t& hi, uint32_t b, uint64_t v, uint32_t k) {
-    if (k < 8) v &= (1ull << (8 * k)) - 1;
-    if (b < 8) {
-        lo |= v << (8 * b);
-        if (b && b + k > 8) hi |= v >> (64 - 8 * b);
-    } else {
-        hi |= v << (8 * (b - 8));
-    }
 }
 
 template <bool INDEXED>
@@ -242,9 +224,9 @@ __global__ __launch_bounds__(kBlock) void k_unpack_replies_aos(ReplyAosArgs a, c
             }
         }
         if (cnt == 16) {
-            __builtin_nontemporal_store(ra_u32x4{static_cast<uint32_t>(vlo), static_cast<uint32_t>(vlo >> 32),
+            __builtin_nontemporal_store(aos_u32x4{static_cast<uint32_t>(vlo), static_cast<uint32_t>(vlo >> 32),
                                                  static_cast<uint32_t>(vhi), static_cast<uint32_t>(vhi >> 32)},
-                                        reinterpret_cast<ra_u32x4*>(dst + x0));
+                                        reinterpret_cast<aos_u32x4*>(dst + x0));
         } else {  // the array's last, partial piece: its own bytes only
             for (uint32_t y = 0; y < cnt; ++y)
                 dst[x0 + y] = static_cast<uint8_t>(y < 8 ? vlo >> (8 * y) : vhi >> (8 * (y - 8)));
@@ -295,17 +277,9 @@ int srpc_frames_unpack_replies_aos(const srpc_plan* reply_plan, const uint8_t* d
     const uint32_t stride = static_cast<uint32_t>(record_stride);
     // the struct's bytes: -1 fill, else the wire offset of the leaf byte there
     int32_t from[kAosMaxStride];
-    std::fill(from, from + stride, -1);
-    for (uint32_t f = 0; f < p->nfields; ++f) {
-        if (field_offsets[f] + static_cast<uint64_t>(p->size[f]) > stride) return SRPC_E_INVALID;
-        for (uint32_t b = 0; b < p->size[f]; ++b) {
-            if (from[field_offsets[f] + b] >= 0) return SRPC_E_INVALID;  // two leaves share a byte
-            from[field_offsets[f] + b] = static_cast<int32_t>(p->off[f] + b);
-        }
-    }
+    if (int rc = aos_sources(p, field_offsets, stride, from)) return rc;
     if (!aligned(d_buf, 16) || !aligned(d_records, 16)) return SRPC_E_ALIGN;
-    for (uint32_t f = 0; f < p->nfields; ++f)
-        if (field_offsets[f] % p->size[f] || stride % p->size[f]) return SRPC_E_ALIGN;  // as in C++ structs
+    if (!aos_layout_aligned(p, field_offsets, stride)) return SRPC_E_ALIGN;  // as in C++ structs
     auto s = static_cast<hipStream_t>(stream);
     if (d_status) {
         hipLaunchKernelGGL(k_reset_status_aos, dim3(1), dim3(64), 0, s, d_status);
@@ -319,12 +293,7 @@ int srpc_frames_unpack_replies_aos(const srpc_plan* reply_plan, const uint8_t* d
     a.stride = stride;
     a.R = reply_aos_tile_frames(a.F, stride);
     std::memcpy(a.fillw, h_fill, stride);
-    for (uint32_t k = stride; k-- > 0;) {  // run lengths, from the struct's end
-        uint32_t run = 1;
-        if (k + 1 < stride && (from[k] < 0 ? from[k + 1] < 0 : from[k + 1] == from[k] + 1))
-            run = std::min<uint32_t>(8, 1 + (a.tab[k + 1] >> 12));
-        a.tab[k] = static_cast<uint16_t>((run << 12) | (from[k] < 0 ? kSrcFill : static_cast<uint32_t>(from[k])));
-    }
+    aos_run_table(from, stride, a.tab);
     const uint32_t grid = static_cast<uint32_t>((nframes + a.R - 1) / a.R);
     const size_t lds = reply_aos_lds_bytes(a.F, a.prefix_len, a.R, stride, d_offs != nullptr);
     auto* recs = static_cast<uint8_t*>(d_records);

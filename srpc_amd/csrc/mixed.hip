@@ -14,6 +14,8 @@
 //       prefixes (segments of rows per thread, the segment sums scanned in LDS)
 //       and writes the chunk's counts.  The index IS that table: 4 (K + 1)
 //       (1 + 1/16) bytes per 256 calls, no rank per call.
+//   (k_mixed_pack's tile and the decode's judgement of a frame are
+//   mix_pack_tile and mix_judge of mixed_common.h, shared with mixed_aos.hip.)
 //   mix_ranks      (mixed_common.h; every consumer) the granule's 256 method bytes again: the
 //       rank of a call is its plan's two table entries (granule + super-row)
 //       plus the ballot counts of the lanes before it.
@@ -115,101 +117,13 @@ __global__ __launch_bounds__(kBlock) void k_mixed_ranks(const uint32_t* __restri
     if (i < ncalls) rank[i] = r.cls < K ? r.rank : kNoRank;
 }
 
-// LDS of k_mixed_pack: image[a.img] | templates[tmpl_bytes] | 16 pad, then
-// static wcnt, wsum and the tile's byte range.
+// The request pack over columns: mix_pack_tile (mixed_common.h) with a leaf of
+// element e at col[f] + e * size[f].
 __global__ __launch_bounds__(kBlock) void k_mixed_pack(MixArgs a, const uint8_t* __restrict__ method,
                                                        const uint32_t* __restrict__ table, uint64_t rows,
                                                        uint64_t ncalls, uint8_t* __restrict__ out,
                                                        uint32_t* __restrict__ offs, srpc_unpack_status* st) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
-    __shared__ uint32_t wcnt[kMixLds];
-    __shared__ uint32_t wsum[kMixWaves];
-    __shared__ uint32_t range[2];
-    __shared__ MixLds d;
-    if (ncalls == 0) {
-        if (offs && threadIdx.x == 0) offs[0] = 0;
-        return;
-    }
-    const uint32_t K = a.nplans;
-    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
-    const uint64_t g = c0 / kMixGranule;
-    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);  // the tile's first lane
-    const uint64_t i = g * kMixGranule + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint32_t* base = wcnt + kMixWaves * kMixRow;  // after mix_ranks: the calls of each plan before the granule
-
-    mix_lds_fill(d, a);
-    mix_templates(lds + a.img, a);  // the K prefixes as LDS templates
-
-    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
-    const bool present = r.cls <= K;
-    const bool good = r.cls < K && r.rank < d.room[r.cls];
-    const uint32_t F = good ? d.F[r.cls] : 0;
-
-    // bytes of the frames before this granule, and an exclusive scan inside it
-    uint64_t gbase = 0;
-    for (uint32_t k = 0; k < K; ++k) gbase += static_cast<uint64_t>(min(base[k], a.room[k])) * a.F[k];
-    uint32_t inc = F;
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    uint32_t at = inc - F;
-    for (uint32_t q = 0; q < w; ++q) at += wsum[q];
-
-    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T;
-    if (threadIdx.x == j0) range[0] = at;
-    if (threadIdx.x == j0 + a.T - 1) range[1] = at + F;
-    __syncthreads();
-    const uint64_t lo = gbase + range[0], hi = gbase + range[1];  // the tile's bytes of the stream
-    const uint64_t A = lo & ~15ull;                                // the image's first byte
-
-    if (mine && present) {
-        const uint64_t o = gbase + at;
-        if (offs) {
-            offs[i] = static_cast<uint32_t>(o);
-            if (i + 1 == ncalls) offs[ncalls] = static_cast<uint32_t>(o + F);
-        }
-        if (!good) {
-            if (st) report_bad(st, SRPC_STATUS_BOUNDS, i);
-        } else {
-            const uint32_t k = r.cls;
-            const uint32_t p = static_cast<uint32_t>(o - A);  // < T * F_max + 16 <= a.img
-            const uint64_t e = d.first[k] + r.rank;
-            const uint32_t f0 = d.field0[k], f1 = d.field0[k + 1];
-            // the first fields' loads are issued together, before the prefix is copied
-            constexpr uint32_t kAhead = 2;
-            uint64_t v[kAhead];
-#pragma unroll
-            for (uint32_t u = 0; u < kAhead; ++u) {
-                const uint32_t f = min(f0 + u, f1 - 1);
-                v[u] = load_elem(d.col[f] + e * d.size[f], d.size[f]);
-            }
-            lds_copy_run(lds, p, a.img + d.tmpl[k], d.prefix_len[k]);
-#pragma unroll
-            for (uint32_t u = 0; u < kAhead; ++u)
-                if (f0 + u < f1) lds_put_small(lds, p + d.off[f0 + u], v[u], d.size[f0 + u]);
-            for (uint32_t f = f0 + kAhead; f < f1; ++f) {
-                const uint32_t s = d.size[f];
-                lds_put_small(lds, p + d.off[f], load_elem(d.col[f] + e * s, s), s);
-            }
-        }
-    }
-    __syncthreads();
-
-    // image -> stream: whole 16-byte chunks inside [lo, hi) as one store, the rest bytewise
-    const uint32_t nch = static_cast<uint32_t>((hi - A + 15) >> 4);
-    for (uint32_t c = threadIdx.x; c < nch; c += kBlock) {
-        const uint64_t b0 = A + 16ull * c;
-        if (b0 >= lo && b0 + 16 <= hi) {
-            *reinterpret_cast<uint4*>(out + b0) = *reinterpret_cast<const uint4*>(lds + 16 * c);
-        } else {
-            for (uint32_t b = 0; b < 16; ++b)
-                if (b0 + b >= lo && b0 + b < hi) out[b0 + b] = lds[16 * c + b];
-        }
-    }
+    mix_pack_tile<false>(a, nullptr, method, table, rows, ncalls, out, offs, st);
 }
 
 // LDS of k_mixed_unpack: image[a.img + 32] | lo[T + 1] (8-byte padded) | the K
@@ -226,109 +140,41 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack(MixArgs a, const uint8_
     __shared__ MixLds d;
     uint8_t* img = lds;
     uint32_t* lo = reinterpret_cast<uint32_t*>(lds + a.img + 32);
-    const uint8_t* tmpl = lds + a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
+    uint8_t* tmpl = lds + a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
     const uint32_t K = a.nplans;
     mix_lds_fill(d, a);
-    mix_templates(lds + a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u), a);
+    mix_templates(tmpl, a);
     const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
     const uint64_t g = c0 / kMixGranule;
     const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
     const uint64_t i = g * kMixGranule + threadIdx.x;
     // frames of this tile
     const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(a.T, nframes - c0)) : 0;
-    for (uint32_t j = threadIdx.x; j <= a.T; j += kBlock) lo[j] = c0 + j < nframes ? offs[c0 + j] : static_cast<uint32_t>(buf_len);
+    req_offsets(lo, a.T, offs, nframes, c0, buf_len);
 
     const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);  // barrier: lo[] is complete
     const bool good = r.cls < K && r.rank < d.room[r.cls];
 
     // 1. the span of the tile's frames -> image, from a 16-byte boundary
-    const uint32_t cap = a.img;
-    uint64_t s0 = 0;
-    uint32_t staged = 0;
-    if (nr) {
-        const uint64_t o0 = lo[0], oe = lo[nr];
-        s0 = o0 & ~15ull;
-        if (o0 <= buf_len) {
-            const uint64_t end = oe >= o0 && oe <= buf_len ? oe : buf_len;
-            staged = static_cast<uint32_t>(min<uint64_t>(end - s0, cap));
-        }
-    }
-    const uint8_t* src = buf + s0;
-    const uint32_t full = staged >> 4;
-    constexpr int kLoads = 4;  // 16-byte loads in flight per lane
-    for (uint32_t cb = threadIdx.x; cb < full; cb += kBlock * kLoads) {
-        uint4 vv[kLoads];
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u) vv[u] = *reinterpret_cast<const uint4*>(src + 16 * min(cb + u * kBlock, full - 1));
-#pragma unroll
-        for (int u = 0; u < kLoads; ++u)
-            if (cb + u * kBlock < full) *reinterpret_cast<uint4*>(img + 16 * (cb + u * kBlock)) = vv[u];
-    }
-    for (uint32_t b = full * 16 + threadIdx.x; b < staged; b += kBlock) img[b] = src[b];
-    __syncthreads();
+    const ReqSpan sp = req_stage(img, lo, nr, a.img, buf, buf_len);
 
     // 2. a lane per call: judge its frame, store its code and fields
     const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T && i < ncalls;
     if (!mine) return;
-    const uint32_t j = threadIdx.x - j0;
-    uint32_t code = SRPC_REPLY_NO_CODE, flag = 0, q = 0;
-    bool decoded = false, in_img = false;
-    uint64_t o = 0;
-    if (j >= nr) {
-        code = unanswered;  // no frame: no flag
-    } else if (!good) {
-        flag = SRPC_STATUS_BOUNDS;  // no plan, or no element to decode into
-    } else {
-        const uint32_t k = r.cls;
-        const uint64_t e = lo[j + 1];
-        o = lo[j];
-        if (!(o <= e && e <= buf_len) || e - o < 5) {
-            flag = SRPC_STATUS_BOUNDS;
-        } else {
-            const uint64_t len = e - o;
-            const uint64_t need = len == d.F[k] ? len : 5;
-            in_img = o >= s0 && o - s0 + need <= staged;
-            q = static_cast<uint32_t>(o - s0);
-            const uint8_t* h = in_img ? img + q : buf + o;
-            const uint32_t be = mix_be32(h), cb = h[4];
-            if (be != len - 4) {
-                flag = SRPC_STATUS_BOUNDS;
-            } else {
-                code = cb;
-                if (len == d.F[k]) {
-                    const uint32_t pl = d.prefix_len[k];
-                    const uint8_t* pre = tmpl + d.tmpl[k];
-                    bool eq = true;
-                    if (in_img) {
-                        for (uint32_t b = 0; b < pl; b += 8) {
-                            uint64_t m = pl - b >= 8 ? ~0ull : (1ull << (8 * (pl - b))) - 1;
-                            if (b == 0) m &= ~(0xffull << 32);  // the code byte
-                            eq &= ((lds_u64(img, q + b) ^ *reinterpret_cast<const uint64_t*>(pre + b)) & m) == 0;
-                        }
-                    } else {
-                        for (uint32_t b = 0; b < pl; ++b) eq &= b == 4 || buf[o + b] == pre[b];
-                    }
-                    if (eq) decoded = true;
-                    else flag = SRPC_STATUS_PREFIX;
-                } else if (!(len == 5 && cb != 0)) {
-                    flag = SRPC_STATUS_PREFIX;
-                }
-            }
-        }
-    }
-    codes[i] = static_cast<uint8_t>(code);
-    if (flag && st) report_bad(st, flag, i);
+    const MixReply y = mix_judge(d, r, good, threadIdx.x - j0, nr, lo, img, tmpl, sp, buf, buf_len, unanswered);
+    codes[i] = static_cast<uint8_t>(y.code);
+    if (y.flag && st) report_bad(st, y.flag, i);
     if (!good) return;  // no column element is touched for a bad call
     const uint32_t k = r.cls;
     const uint64_t e = d.first[k] + r.rank;
     for (uint32_t f = d.field0[k]; f < d.field0[k + 1]; ++f) {
         const uint32_t s = d.size[f];
         uint64_t v = 0;
-        if (decoded) {
-            if (in_img) {
-                v = s == 1 ? img[q + d.off[f]] : lds_u64(img, q + d.off[f]);
+        if (y.decoded) {
+            if (y.in_img) {
+                v = s == 1 ? img[y.q + d.off[f]] : lds_u64(img, y.q + d.off[f]);
             } else {
-                const uint8_t* gp = buf + o + d.off[f];
+                const uint8_t* gp = buf + y.o + d.off[f];
                 for (uint32_t b = 0; b < s; ++b) v |= static_cast<uint64_t>(gp[b]) << (8 * b);
             }
         }

@@ -1,0 +1,415 @@
+// mixed_aos.hip -- batches of calls of several methods in caller-given order,
+// each plan's calls held as one device array of the caller's own structs
+// (srpc_frames_pack_requests_mixed_aos, srpc_frames_unpack_replies_mixed_aos of
+// include/srpc_gpu.h): the struct-array form of mixed.hip's two calls.
+//
+// The index, mix_ranks, the tile, the granule's byte offset, the LDS lookups by
+// a lane's own plan, the prefix templates and the image are mixed.hip's
+// (mixed_common.h); only the field step differs.
+//
+//   k_mixed_pack_aos    mix_pack_tile<true>: a lane's leaves come from
+//       recs[k] + e * stride[k] + loff[f]; lanes of one plan hold consecutive
+//       ranks, so their structs are adjacent in memory.
+//   k_mixed_unpack_aos  stage, rank and judge as k_mixed_unpack (req_stage,
+//       mix_judge); each lane leaves pos[j] -- its frame's image position,
+//       "outside the image" or "leaves are zero".  Within a tile the good calls
+//       of plan k are consecutive ranks, so they are one contiguous slice of plan
+//       k's array: per-wave ballots leave its first element and count, and every
+//       lane its slot (slice position -> lane).  The workgroup then takes
+//       (plan, 16-byte piece) pairs over the K slices: a piece is assembled run
+//       by run through plan k's per-struct-byte table, as k_unpack_replies_aos
+//       does (aos_pieces.h), from the image at the frame's position, zero, or plan
+//       k's fill, and stored whole.  A slice starts and ends at any byte: its
+//       first and last piece, where they are shared with a neighbouring tile's
+//       slice (or lie at the array's edge), are stored bytewise, own bytes only.
+//       Every struct byte of a good call is written exactly once, none is read.
+//
+// The K tables and fills (up to 12.5 KiB) do not fit kernel arguments: they go
+// to the head of caller scratch by mix_upload's by-value chunk launches and
+// every workgroup copies them to LDS with 16-byte loads.
+// LDS of the decode: image[a.img + 32] | lo[T + 1] (8-byte padded) | the K
+//   prefixes | pos[T] | slot[T] (u16) | 16-byte aligned: tab_k[S16_k] (u16) ... |
+//   fill_k[S16_k + 16] ..., then static wcnt, the lookups and the slices.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+
+#include "aos_pieces.h"
+#include "mixed_common.h"
+#include "mixed_var_common.h"
+#include "plan.h"
+#include "srpc_gpu.h"
+
+namespace srpc_impl {
+namespace {
+
+struct MixAosStride {
+    uint32_t stride[kMixPlans];
+};
+
+struct MixAos {
+    uint8_t* recs[kMixPlans];     // plan k's struct array
+    uint32_t stride[kMixPlans];   // struct bytes
+    uint16_t tab[kMixPlans];      // byte offset of plan k's table inside the description
+    uint16_t fill[kMixPlans];     // ... of its fill record
+    uint32_t desc_bytes;          // tables and fills (a multiple of 16)
+};
+
+// Table and fill bytes of the plans' strides: 2 S16 + S16 + 16 each.
+inline uint32_t aos_desc_bytes(const uint64_t* h_stride, int nplans) {
+    uint32_t b = 0;
+    for (int k = 0; k < nplans; ++k) b += 3 * s16_of(static_cast<uint32_t>(h_stride[k])) + 16;
+    return b;
+}
+
+// Calls per tile of the decode: mix_tile with the tables and fills taken out of
+// the image's budget, so image + tables + fills stay within the column kernel's
+// image (at the floor of 16 calls: 16 * 1280 + 12.5 KiB, still under 33 KiB).
+inline uint32_t mix_aos_tile(uint32_t fmax, uint32_t desc_bytes) { return mix_tile(fmax, kMixImage - desc_bytes); }
+
+inline size_t mix_aos_lds(const MixArgs& a, uint32_t tb, uint32_t desc_bytes) {
+    const size_t head = a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u) + tb + 4 * a.T + 2 * a.T;
+    return ((head + 15) & ~size_t{15}) + desc_bytes;
+}
+
+__global__ __launch_bounds__(kBlock) void k_mixed_pack_aos(MixArgs a, MixAosStride x, const uint8_t* __restrict__ method,
+                                                           const uint32_t* __restrict__ table, uint64_t rows,
+                                                           uint64_t ncalls, uint8_t* __restrict__ out,
+                                                           uint32_t* __restrict__ offs, srpc_unpack_status* st) {
+    mix_pack_tile<true>(a, x.stride, method, table, rows, ncalls, out, offs, st);
+}
+
+__global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x, const uint4* __restrict__ desc,
+                                                             const uint8_t* __restrict__ method,
+                                                             const uint32_t* __restrict__ table, uint64_t rows,
+                                                             uint64_t ncalls, const uint8_t* __restrict__ buf,
+                                                             uint64_t buf_len, const uint32_t* __restrict__ offs,
+                                                             uint64_t nframes, uint32_t unanswered,
+                                                             uint8_t* __restrict__ codes, srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ MixLds d;
+    // the tile's slice of plan k's array, and plan k's struct
+    __shared__ uint64_t sbyte0[kMixPlans];     // the slice's first byte inside the array
+    __shared__ uint8_t* srecs[kMixPlans];
+    __shared__ uint32_t sfirst[kMixPlans];     // rank of the slice's first call
+    __shared__ uint32_t scount[kMixPlans];     // its calls
+    __shared__ uint32_t sbase[kMixPlans];      // its first entry of slot[]
+    __shared__ uint32_t pbase[kMixPlans + 1];  // its first (plan, piece) pair
+    __shared__ uint32_t sstride[kMixPlans];
+    __shared__ uint16_t stab[kMixPlans], sfill[kMixPlans];
+    const uint32_t K = a.nplans;
+    const uint32_t lo_bytes = (4 * (a.T + 1) + 7) & ~7u;
+    const uint32_t tb = a.tmpl[K - 1] + ((a.prefix_len[K - 1] + 7) & ~7u);
+    uint8_t* img = lds;
+    uint32_t* lo = reinterpret_cast<uint32_t*>(lds + a.img + 32);
+    uint8_t* tmpl = lds + a.img + 32 + lo_bytes;
+    uint32_t* pos = reinterpret_cast<uint32_t*>(tmpl + tb);
+    uint16_t* slot = reinterpret_cast<uint16_t*>(pos + a.T);
+    uint8_t* dsc = lds + ((a.img + 32 + lo_bytes + tb + 6 * a.T + 15) & ~15u);
+
+    mix_lds_fill(d, a);
+    mix_templates(tmpl, a);
+    if (threadIdx.x < K) {
+        const uint32_t k = threadIdx.x;
+        srecs[k] = x.recs[k];
+        sstride[k] = x.stride[k];
+        stab[k] = x.tab[k];
+        sfill[k] = x.fill[k];
+        sfirst[k] = 0xffffffffu;
+        scount[k] = 0;
+    }
+    for (uint32_t c = threadIdx.x; c < x.desc_bytes / 16; c += kBlock) reinterpret_cast<uint4*>(dsc)[c] = desc[c];
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(a.T, nframes - c0)) : 0;
+    req_offsets(lo, a.T, offs, nframes, c0, buf_len);
+
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);  // barrier: lo[] and the slices' init are complete
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T && i < ncalls;
+    const bool good = mine && r.cls < K && r.rank < d.room[r.cls];
+    const uint32_t j = threadIdx.x - j0;
+
+    // the tile's slices: good calls of one plan are consecutive ranks, ascending with the lane
+    for (uint32_t k = 0; k < K; ++k) {
+        const uint64_t b = __ballot(good && r.cls == k);
+        if (b) {
+            const uint32_t rk = __shfl(r.rank, __ffsll(static_cast<long long>(b)) - 1, 64);
+            if (lane == 0) {
+                atomicMin(&sfirst[k], rk);
+                atomicAdd(&scount[k], static_cast<uint32_t>(__popcll(b)));
+            }
+        }
+    }
+
+    // 1. the span of the tile's frames -> image, from a 16-byte boundary (ends with a barrier)
+    const ReqSpan sp = req_stage(img, lo, nr, a.img, buf, buf_len);
+
+    // 2. a lane per call: judge its frame, store its code, leave where its leaves are
+    if (mine) {
+        const MixReply y = mix_judge(d, r, good, j, nr, lo, img, tmpl, sp, buf, buf_len, unanswered);
+        codes[i] = static_cast<uint8_t>(y.code);
+        if (y.flag && st) report_bad(st, y.flag, i);
+        pos[j] = !y.decoded ? kPosZero : y.in_img ? y.q : kPosGlobal;
+    }
+    if (threadIdx.x <= K) {
+        uint32_t sb = 0, pb = 0;
+        for (uint32_t q = 0; q < threadIdx.x; ++q) {
+            const uint32_t n = scount[q];
+            const uint64_t b0 = (d.first[q] + sfirst[q]) * sstride[q];
+            sb += n;
+            pb += n ? static_cast<uint32_t>(((b0 & 15) + static_cast<uint64_t>(n) * sstride[q] + 15) >> 4) : 0;
+        }
+        pbase[threadIdx.x] = pb;
+        if (threadIdx.x < K) {
+            sbase[threadIdx.x] = sb;
+            sbyte0[threadIdx.x] = scount[threadIdx.x] ? (d.first[threadIdx.x] + sfirst[threadIdx.x]) * sstride[threadIdx.x] : 0;
+        }
+    }
+    __syncthreads();
+    if (good) slot[sbase[r.cls] + (r.rank - sfirst[r.cls])] = static_cast<uint16_t>(j);
+    __syncthreads();
+
+    // 3. image, zero and fill -> the slices, one lane per (plan, 16-byte piece)
+    const uint32_t total = pbase[K];
+    for (uint32_t xx = threadIdx.x; xx < total; xx += kBlock) {
+        uint32_t k = 0;
+        for (uint32_t q = 1; q < K; ++q) k = pbase[q] <= xx ? q : k;
+        const uint32_t stride = sstride[k];
+        const uint64_t B0 = sbyte0[k];
+        const uint32_t a0 = static_cast<uint32_t>(B0 & 15);
+        const uint32_t nbytes = scount[k] * stride;     // <= 256 * 256
+        const uint32_t p0 = 16 * (xx - pbase[k]);       // the piece, from the slice's first piece on
+        const uint32_t x0 = p0 > a0 ? p0 - a0 : 0;      // its first byte of the slice
+        const uint32_t x1 = min(p0 + 16 - a0, nbytes);  // ... and past its last
+        const uint32_t b0 = x0 + a0 - p0, b1 = x1 + a0 - p0;  // the same, inside the piece
+        const uint16_t* tab = reinterpret_cast<const uint16_t*>(dsc + stab[k]);
+        const uint8_t* fill = dsc + sfill[k];
+        const uint16_t* sl = slot + sbase[k];
+        uint32_t e = x0 / stride;
+        uint32_t kk = x0 - e * stride;
+        uint32_t jj = sl[e];
+        uint32_t p = pos[jj];
+        uint64_t vlo = 0, vhi = 0;
+        uint32_t b = b0;
+        while (b < b1) {
+            const uint32_t t = tab[kk];
+            const uint32_t m = min(t >> 12, b1 - b), w = t & 0xfff;
+            uint64_t v = 0;
+            if (w == kSrcFill) {
+                v = lds_u64(fill, kk);
+            } else if (p < kPosGlobal) {
+                v = lds_u64(img, p + w);
+            } else if (p == kPosGlobal) {
+                const uint8_t* gp = buf + lo[jj] + w;  // inside the frame: w + m <= F
+                for (uint32_t y = 0; y < m; ++y) v |= static_cast<uint64_t>(gp[y]) << (8 * y);
+            }
+            piece_put(vlo, vhi, b, v, m);
+            b += m;
+            kk += m;
+            if (kk == stride) {  // runs end with their struct
+                kk = 0;
+                ++e;
+                if (b < b1) {  // b < b1 keeps e inside the slice
+                    jj = sl[e];
+                    p = pos[jj];
+                }
+            }
+        }
+        uint8_t* dst = srecs[k] + (B0 - a0) + p0;
+        if (b1 - b0 == 16) {
+            __builtin_nontemporal_store(aos_u32x4{static_cast<uint32_t>(vlo), static_cast<uint32_t>(vlo >> 32),
+                                                  static_cast<uint32_t>(vhi), static_cast<uint32_t>(vhi >> 32)},
+                                        reinterpret_cast<aos_u32x4*>(dst));
+        } else {  // a slice's first or last piece: its own bytes only
+            for (uint32_t y = b0; y < b1; ++y)
+                dst[y] = static_cast<uint8_t>(y < 8 ? vlo >> (8 * y) : vhi >> (8 * (y - 8)));
+        }
+    }
+}
+
+// The arguments both calls share, checked before any plan is read.
+bool aos_args_invalid(const void* const* d_recs, const uint64_t* h_stride, const uint32_t* const* h_leaf_offs,
+                      const uint64_t* h_first, const uint64_t* h_cap, int nplans) {
+    for (int k = 0; k < nplans; ++k) {
+        if (h_stride[k] == 0 || h_stride[k] >= (1ull << 32) || !h_leaf_offs[k]) return true;
+        const uint64_t first = h_first ? h_first[k] : 0;
+        if (h_cap[k] > first && !d_recs[k]) return true;
+    }
+    return false;
+}
+
+// Every leaf inside the stride and no two sharing a byte (any stride below 2^32).
+int aos_leaves_ok(const srpc_plan* p, const uint32_t* offs, uint64_t stride) {
+    for (uint32_t f = 0; f < p->nfields; ++f) {
+        if (offs[f] + static_cast<uint64_t>(p->size[f]) > stride) return SRPC_E_INVALID;
+        for (uint32_t g = 0; g < f; ++g)
+            if (offs[f] < offs[g] + static_cast<uint64_t>(p->size[g]) && offs[g] < offs[f] + static_cast<uint64_t>(p->size[f]))
+                return SRPC_E_INVALID;
+    }
+    return SRPC_OK;
+}
+
+// Each leaf's address inside element 0 of its plan's array, as mix_args's columns.
+struct AosCols {
+    const void* leaf[kMixFields];
+    const void* const* plan[kMixPlans];
+};
+
+void aos_cols(const srpc_plan* const* plans, int nplans, const void* const* d_recs,
+              const uint32_t* const* h_leaf_offs, AosCols* c) {
+    uint32_t nf = 0;
+    for (int k = 0; k < nplans; ++k) {
+        c->plan[k] = c->leaf + nf;
+        for (uint32_t f = 0; f < plans[k]->nfields; ++f)
+            c->leaf[nf++] = static_cast<const uint8_t*>(d_recs[k]) + h_leaf_offs[k][f];
+    }
+}
+
+__global__ void k_mixed_aos_reset_status(srpc_unpack_status* st) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        st->flags = 0;
+        st->reserved = 0;
+        st->first_bad_record = ~0ull;
+    }
+}
+
+}  // namespace
+}  // namespace srpc_impl
+
+using namespace srpc_impl;
+
+extern "C" {
+
+int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+                                        uint64_t* out) {
+    if (!reply_plans || !h_stride || !out || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] == 0) return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
+    *out = aos_desc_bytes(h_stride, nplans);
+    return SRPC_OK;
+}
+
+int srpc_frames_mixed_aos_tile(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+                               uint32_t* calls_per_tile) {
+    if (!reply_plans || !h_stride || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] == 0) return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
+    *calls_per_tile = mix_aos_tile(fmax, aos_desc_bytes(h_stride, nplans));
+    return SRPC_OK;
+}
+
+int srpc_frames_pack_requests_mixed_aos(const srpc_plan* const* req_plans, int nplans, const void* const* d_recs,
+                                        const uint64_t* h_stride, const uint32_t* const* h_leaf_offs,
+                                        const uint64_t* h_first, const uint64_t* h_cap, const uint8_t* d_method,
+                                        const void* d_index, uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                        uint32_t* d_offs, srpc_unpack_status* d_status, void* stream) {
+    const TimedCall timed;
+    // the arguments themselves are checked before any plan is read
+    if (!req_plans || !d_recs || !h_stride || !h_leaf_offs || !h_cap || !d_index || nplans <= 0 || nplans > kMixPlans ||
+        ncalls >= (1ull << 32) || (ncalls && (!d_method || !d_out)))
+        return SRPC_E_INVALID;
+    if (aos_args_invalid(d_recs, h_stride, h_leaf_offs, h_first, h_cap, nplans)) return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(req_plans, nplans, 4, &fmax)) return rc;
+    for (int k = 0; k < nplans; ++k)
+        if (int rc = aos_leaves_ok(req_plans[k], h_leaf_offs[k], h_stride[k])) return rc;
+    if (!aligned(d_out, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4)) return SRPC_E_ALIGN;
+    for (int k = 0; k < nplans; ++k)
+        if (!aligned(d_recs[k], 16) || !aos_layout_aligned(req_plans[k], h_leaf_offs[k], h_stride[k])) return SRPC_E_ALIGN;
+    AosCols cols;
+    aos_cols(req_plans, nplans, d_recs, h_leaf_offs, &cols);
+    MixArgs a{};
+    MixAosStride x{};
+    uint32_t tb = 0;
+    if (int rc = mix_args(req_plans, nplans, cols.plan, h_first, h_cap, fmax, &a, &tb, 1)) return rc;
+    for (int k = 0; k < nplans; ++k) x.stride[k] = static_cast<uint32_t>(h_stride[k]);
+    if (out_cap < ncalls * fmax) return SRPC_E_CAPACITY;
+    if (d_offs && ncalls * fmax >= (1ull << 32)) return SRPC_E_INVALID;  // u32 offsets
+    const uint32_t grid = static_cast<uint32_t>(std::max<uint64_t>(1, (ncalls + a.T - 1) / a.T));
+    launch(k_mixed_pack_aos, dim3(grid), dim3(kBlock), a.img + tb + 16, static_cast<hipStream_t>(stream), a, x, d_method,
+           static_cast<const uint32_t*>(d_index), mix_rows(ncalls), ncalls, d_out, d_offs, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                         uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                         const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                         uint8_t unanswered_code, void* const* d_recs, const uint64_t* h_stride,
+                                         const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+                                         const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                         srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                         void* stream) {
+    const TimedCall timed;
+    if (!reply_plans || !d_recs || !h_stride || !h_leaf_offs || !h_fill || !h_cap || !d_index || !d_codes || !d_scratch ||
+        nplans <= 0 || nplans > kMixPlans || nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) ||
+        (ncalls && !d_method) || (nframes && (!d_buf || !d_offs)))
+        return SRPC_E_INVALID;
+    if (aos_args_invalid(d_recs, h_stride, h_leaf_offs, h_first, h_cap, nplans)) return SRPC_E_INVALID;
+    for (int k = 0; k < nplans; ++k)
+        if (!h_fill[k]) return SRPC_E_INVALID;
+    uint32_t fmax = 0;
+    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
+    // the tables and the fills, as they will lie in scratch and in LDS
+    alignas(16) uint8_t desc[kMixPlans * (3 * kAosMaxStride + 16)] = {};
+    MixAos x{};
+    x.desc_bytes = aos_desc_bytes(h_stride, nplans);
+    uint32_t at = 0;
+    for (int k = 0; k < nplans; ++k) {
+        const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
+        int32_t from[kAosMaxStride];
+        if (int rc = aos_sources(reply_plans[k], h_leaf_offs[k], stride, from)) return rc;
+        aos_run_table(from, stride, reinterpret_cast<uint16_t*>(desc + at));
+        x.tab[k] = static_cast<uint16_t>(at);
+        at += 2 * s16_of(stride);
+    }
+    for (int k = 0; k < nplans; ++k) {
+        const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
+        std::memcpy(desc + at, h_fill[k], stride);
+        x.fill[k] = static_cast<uint16_t>(at);
+        x.recs[k] = static_cast<uint8_t*>(d_recs[k]);
+        x.stride[k] = stride;
+        at += s16_of(stride) + 16;
+    }
+    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4) || !aligned(d_scratch, 16)) return SRPC_E_ALIGN;
+    for (int k = 0; k < nplans; ++k)
+        if (!aligned(d_recs[k], 16) || !aos_layout_aligned(reply_plans[k], h_leaf_offs[k], h_stride[k]))
+            return SRPC_E_ALIGN;
+    if (scratch_bytes < x.desc_bytes) return SRPC_E_CAPACITY;
+    AosCols cols;
+    aos_cols(reply_plans, nplans, d_recs, h_leaf_offs, &cols);
+    MixArgs a{};
+    uint32_t tb = 0;
+    if (int rc = mix_args(reply_plans, nplans, cols.plan, h_first, h_cap, fmax, &a, &tb, 1)) return rc;
+    a.T = mix_aos_tile(fmax, x.desc_bytes);
+    a.img = (a.T * fmax + 16 + 15) & ~15u;
+    auto s = static_cast<hipStream_t>(stream);
+    if (d_status) {
+        hipLaunchKernelGGL(k_mixed_aos_reset_status, dim3(1), dim3(64), 0, s, d_status);
+        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
+    }
+    if (!ncalls) return SRPC_OK;
+    if (int rc = mix_upload(desc, x.desc_bytes, d_scratch, s)) return rc;
+    const uint32_t grid = static_cast<uint32_t>((ncalls + a.T - 1) / a.T);
+    launch(k_mixed_unpack_aos, dim3(grid), dim3(kBlock), static_cast<uint32_t>(mix_aos_lds(a, tb, x.desc_bytes)), s, a, x,
+           static_cast<const uint4*>(d_scratch), d_method, static_cast<const uint32_t*>(d_index), mix_rows(ncalls), ncalls,
+           d_buf, buf_len, d_offs, nframes, static_cast<uint32_t>(unanswered_code), d_codes, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
+}  // extern "C"

@@ -4,7 +4,9 @@
 // share: the call index's geometry and mix_ranks, the rank of every call of a
 // granule from that index; for the two server-side files a tile's offsets and
 // staging; for the two fixed-size files also the kernels' arguments, their LDS
-// lookups and prefix templates.
+// lookups and prefix templates; for mixed.hip and mixed_aos.hip (the client
+// side over columns and over struct arrays) the request pack of a tile
+// (mix_pack_tile) and the reply decode's judgement of a frame (mix_judge).
 #pragma once
 
 #include <algorithm>
@@ -209,9 +211,9 @@ __device__ __forceinline__ void mix_templates(uint8_t* dst, const MixArgs& a) {
     }
 }
 
-inline uint32_t mix_tile(uint32_t fmax) {
+inline uint32_t mix_tile(uint32_t fmax, uint32_t image = kMixImage) {
     uint32_t t = kMixGranule;
-    while (t > 16 && t * fmax > kMixImage) t >>= 1;
+    while (t > 16 && t * fmax > image) t >>= 1;
     return t;
 }
 
@@ -230,9 +232,12 @@ inline int mix_plans_ok(const srpc_plan* const* plans, int nplans, uint32_t min_
     return SRPC_OK;
 }
 
-// Columns, rooms and layouts into the kernel's arguments.
+// Columns, rooms and layouts into the kernel's arguments.  col_align: what a
+// column pointer must keep (mixed_aos.hip passes each leaf's address inside
+// element 0 of its plan's struct array as the "column", checked there).
 inline int mix_args(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
-                    const uint64_t* h_first, const uint64_t* h_cap, uint32_t fmax, MixArgs* a, uint32_t* tmpl_bytes) {
+                    const uint64_t* h_first, const uint64_t* h_cap, uint32_t fmax, MixArgs* a, uint32_t* tmpl_bytes,
+                    uintptr_t col_align = 16) {
     uint32_t nf = 0, tb = 0;
     for (int k = 0; k < nplans; ++k) {
         const srpc_plan* p = plans[k];
@@ -243,7 +248,7 @@ inline int mix_args(const srpc_plan* const* plans, int nplans, const void* const
         for (uint32_t f = 0; f < p->nfields; ++f, ++nf) {
             const void* c = d_cols[k][f];
             if (room && !c) return SRPC_E_INVALID;
-            if (!aligned(c, 16)) return SRPC_E_ALIGN;
+            if (!aligned(c, col_align)) return SRPC_E_ALIGN;
             a->col[nf] = static_cast<uint8_t*>(const_cast<void*>(c));
             a->off[nf] = static_cast<uint16_t>(p->off[f]);
             a->size[nf] = static_cast<uint8_t>(p->size[f]);
@@ -262,6 +267,180 @@ inline int mix_args(const srpc_plan* const* plans, int nplans, const void* const
     a->img = (a->T * fmax + 16 + 15) & ~15u;
     *tmpl_bytes = tb;
     return SRPC_OK;
+}
+
+// ---- the client-side kernels of mixed.hip (columns) and mixed_aos.hip (struct
+// arrays): everything but where a call's fields live ----
+
+// The request pack of one tile.  AOS = false: leaf f of element e is at
+// col[f] + e * size[f] (a column).  AOS = true: at col[f] + e * stride[k],
+// col[f] being the leaf's address inside element 0 of plan k's struct array
+// and `stride` (kernel argument, K entries) the plans' struct bytes; lanes of
+// one plan hold consecutive ranks, so their structs are adjacent in memory.
+// Dynamic LDS: image[a.img] | templates[tmpl_bytes] | 16 pad.
+template <bool AOS>
+__device__ __forceinline__ void mix_pack_tile(const MixArgs& a, const uint32_t* stride,
+                                              const uint8_t* __restrict__ method,
+                                              const uint32_t* __restrict__ table, uint64_t rows, uint64_t ncalls,
+                                              uint8_t* __restrict__ out, uint32_t* __restrict__ offs,
+                                              srpc_unpack_status* st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    __shared__ uint32_t wcnt[kMixLds];
+    __shared__ uint32_t wsum[kMixWaves];
+    __shared__ uint32_t range[2];
+    __shared__ uint32_t step[AOS ? kMixPlans : 1];
+    __shared__ MixLds d;
+    if (ncalls == 0) {
+        if (offs && threadIdx.x == 0) offs[0] = 0;
+        return;
+    }
+    const uint32_t K = a.nplans;
+    const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
+    const uint64_t g = c0 / kMixGranule;
+    const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);  // the tile's first lane
+    const uint64_t i = g * kMixGranule + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t* base = wcnt + kMixWaves * kMixRow;  // after mix_ranks: the calls of each plan before the granule
+
+    mix_lds_fill(d, a);
+    if constexpr (AOS)
+        if (threadIdx.x < K) step[threadIdx.x] = stride[threadIdx.x];
+    mix_templates(lds + a.img, a);  // the K prefixes as LDS templates
+
+    const MixLane r = mix_ranks(method, ncalls, K, table, rows, g, wcnt);
+    const bool present = r.cls <= K;
+    const bool good = r.cls < K && r.rank < d.room[r.cls];
+    const uint32_t F = good ? d.F[r.cls] : 0;
+
+    // bytes of the frames before this granule, and an exclusive scan inside it
+    uint64_t gbase = 0;
+    for (uint32_t k = 0; k < K; ++k) gbase += static_cast<uint64_t>(min(base[k], a.room[k])) * a.F[k];
+    uint32_t inc = F;
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    uint32_t at = inc - F;
+    for (uint32_t q = 0; q < w; ++q) at += wsum[q];
+
+    const bool mine = threadIdx.x >= j0 && threadIdx.x < j0 + a.T;
+    if (threadIdx.x == j0) range[0] = at;
+    if (threadIdx.x == j0 + a.T - 1) range[1] = at + F;
+    __syncthreads();
+    const uint64_t lo = gbase + range[0], hi = gbase + range[1];  // the tile's bytes of the stream
+    const uint64_t A = lo & ~15ull;                                // the image's first byte
+
+    if (mine && present) {
+        const uint64_t o = gbase + at;
+        if (offs) {
+            offs[i] = static_cast<uint32_t>(o);
+            if (i + 1 == ncalls) offs[ncalls] = static_cast<uint32_t>(o + F);
+        }
+        if (!good) {
+            if (st) report_bad(st, SRPC_STATUS_BOUNDS, i);
+        } else {
+            const uint32_t k = r.cls;
+            const uint32_t p = static_cast<uint32_t>(o - A);  // < T * F_max + 16 <= a.img
+            const uint64_t e = d.first[k] + r.rank;
+            const uint32_t f0 = d.field0[k], f1 = d.field0[k + 1];
+            const uint64_t es = AOS ? e * step[k] : 0;  // the struct's byte offset
+            // the first fields' loads are issued together, before the prefix is copied
+            constexpr uint32_t kAhead = 2;
+            uint64_t v[kAhead];
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u) {
+                const uint32_t f = min(f0 + u, f1 - 1);
+                v[u] = load_elem(d.col[f] + (AOS ? es : e * d.size[f]), d.size[f]);
+            }
+            lds_copy_run(lds, p, a.img + d.tmpl[k], d.prefix_len[k]);
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u)
+                if (f0 + u < f1) lds_put_small(lds, p + d.off[f0 + u], v[u], d.size[f0 + u]);
+            for (uint32_t f = f0 + kAhead; f < f1; ++f) {
+                const uint32_t s = d.size[f];
+                lds_put_small(lds, p + d.off[f], load_elem(d.col[f] + (AOS ? es : e * s), s), s);
+            }
+        }
+    }
+    __syncthreads();
+
+    // image -> stream: whole 16-byte chunks inside [lo, hi) as one store, the rest bytewise
+    const uint32_t nch = static_cast<uint32_t>((hi - A + 15) >> 4);
+    for (uint32_t c = threadIdx.x; c < nch; c += kBlock) {
+        const uint64_t b0 = A + 16ull * c;
+        if (b0 >= lo && b0 + 16 <= hi) {
+            *reinterpret_cast<uint4*>(out + b0) = *reinterpret_cast<const uint4*>(lds + 16 * c);
+        } else {
+            for (uint32_t b = 0; b < 16; ++b)
+                if (b0 + b >= lo && b0 + b < hi) out[b0 + b] = lds[16 * c + b];
+        }
+    }
+}
+
+// What the reply decode finds for one call of its tile.
+struct MixReply {
+    uint64_t o;     // the frame's stream offset
+    uint32_t code;  // d_codes[i]
+    uint32_t flag;  // status flag, 0 for none
+    uint32_t q;     // the frame's image position (in_img)
+    bool decoded;   // a full frame of the call's own plan: its fields are the frame's
+    bool in_img;    // ... and it lies inside the staged span; else it is read from buf + o
+};
+
+// Call j of a tile with nr frames, judged by the table of
+// srpc_frames_unpack_replies against its own plan's prefix.  good: the call has
+// a plan and an element.  lo[]: the tile's offsets (req_offsets), sp: its
+// staged span (req_stage), tmpl: the K prefixes (mix_templates).
+__device__ __forceinline__ MixReply mix_judge(const MixLds& d, const MixLane& r, bool good, uint32_t j, uint32_t nr,
+                                              const uint32_t* lo, const uint8_t* img, const uint8_t* tmpl,
+                                              const ReqSpan& sp, const uint8_t* __restrict__ buf, uint64_t buf_len,
+                                              uint32_t unanswered) {
+    MixReply y{0, SRPC_REPLY_NO_CODE, 0, 0, false, false};
+    if (j >= nr) {
+        y.code = unanswered;  // no frame: no flag
+    } else if (!good) {
+        y.flag = SRPC_STATUS_BOUNDS;  // no plan, or no element to decode into
+    } else {
+        const uint32_t k = r.cls;
+        const uint64_t e = lo[j + 1];
+        y.o = lo[j];
+        if (!(y.o <= e && e <= buf_len) || e - y.o < 5) {
+            y.flag = SRPC_STATUS_BOUNDS;
+        } else {
+            const uint64_t len = e - y.o;
+            const uint64_t need = len == d.F[k] ? len : 5;
+            y.in_img = y.o >= sp.s0 && y.o - sp.s0 + need <= sp.staged;
+            y.q = static_cast<uint32_t>(y.o - sp.s0);
+            const uint8_t* h = y.in_img ? img + y.q : buf + y.o;
+            const uint32_t be = mix_be32(h), cb = h[4];
+            if (be != len - 4) {
+                y.flag = SRPC_STATUS_BOUNDS;
+            } else {
+                y.code = cb;
+                if (len == d.F[k]) {
+                    const uint32_t pl = d.prefix_len[k];
+                    const uint8_t* pre = tmpl + d.tmpl[k];
+                    bool eq = true;
+                    if (y.in_img) {
+                        for (uint32_t b = 0; b < pl; b += 8) {
+                            uint64_t m = pl - b >= 8 ? ~0ull : (1ull << (8 * (pl - b))) - 1;
+                            if (b == 0) m &= ~(0xffull << 32);  // the code byte
+                            eq &= ((lds_u64(img, y.q + b) ^ *reinterpret_cast<const uint64_t*>(pre + b)) & m) == 0;
+                        }
+                    } else {
+                        for (uint32_t b = 0; b < pl; ++b) eq &= b == 4 || buf[y.o + b] == pre[b];
+                    }
+                    if (eq) y.decoded = true;
+                    else y.flag = SRPC_STATUS_PREFIX;
+                } else if (!(len == 5 && cb != 0)) {
+                    y.flag = SRPC_STATUS_PREFIX;
+                }
+            }
+        }
+    }
+    return y;
 }
 
 // mixed.hip: the index over ncalls method bytes (k_mixed_hist, k_mixed_scan;

@@ -656,18 +656,19 @@ int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const*
     return SRPC_OK;
 }
 
-int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) {
-    for (uint32_t c = 0; c < kMvChunks; ++c) {
+int mix_upload(const void* src, size_t bytes, void* d_scratch, hipStream_t s) {
+    for (size_t at = 0; at < bytes; at += kMvChunk) {
         MvChunk ch;
-        const size_t at = static_cast<size_t>(c) * kMvChunk;
-        const size_t nbytes = std::min<size_t>(kMvChunk, sizeof(MvDesc) - at);
+        const size_t nbytes = std::min<size_t>(kMvChunk, bytes - at);
         std::memset(&ch, 0, sizeof ch);
-        std::memcpy(&ch, reinterpret_cast<const uint8_t*>(&d) + at, nbytes);
+        std::memcpy(&ch, static_cast<const uint8_t*>(src) + at, nbytes);
         launch(k_mv_upload, dim3(1), dim3(128), 0, s, ch, reinterpret_cast<uint4*>(static_cast<uint8_t*>(d_scratch) + at),
                static_cast<uint32_t>(nbytes / 16));
     }
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
+
+int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) { return mix_upload(&d, sizeof(MvDesc), d_scratch, s); }
 
 void mv_slots_launch(const MvDesc& d, const MvDesc* dd, const uint32_t* counts, uint64_t ncalls, uint64_t* partial,
                      uint32_t nb, uint64_t* d_ends, hipStream_t s) {

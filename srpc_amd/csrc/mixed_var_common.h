@@ -97,6 +97,10 @@ int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const*
             const uint64_t* h_cap, MvDesc* d);
 // d -> the head of d_scratch, in kMvChunks launches.
 int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s);
+// Any description (bytes: a multiple of 16) -> the head of d_scratch (16-byte
+// aligned), kMvChunk bytes per launch, each chunk a by-value kernel argument:
+// no host copy outlives the call (also mixed_aos.hip's tables and fills).
+int mix_upload(const void* src, size_t bytes, void* d_scratch, hipStream_t s);
 // The segmented scan over all string slots (three launches whatever K): the
 // lengths the parse left in the offsets arrays become offsets, d_ends[s] each
 // slot's end.  counts: the chunk's calls per plan (device, u32).

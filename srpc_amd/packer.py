@@ -567,6 +567,65 @@ class MixedFrames:
                                                             _stream(stream))
 
 
+class MixedAosFrames:
+    """``MixedFrames.pack`` / ``unpack`` with one device array of structs per
+    plan in place of its columns (srpc_frames_pack_requests_mixed_aos /
+    _unpack_replies_mixed_aos; the index is ``MixedFrames.index``).
+    ``strides[k]``: plan k's struct bytes, ``leaf_offsets[k][f]``: the byte
+    offset of leaf f in it.  Every call returns the C status (negative: refused,
+    nothing launched)."""
+
+    def __init__(self, plans: Sequence["GpuPacker"], strides: Sequence[int], leaf_offsets: Sequence[Sequence[int]]):
+        self.plans = list(plans)
+        self.k = len(self.plans)
+        self._plans = (C.c_void_p * self.k)(*[p._h.value for p in self.plans])
+        self._strides = (C.c_uint64 * self.k)(*[int(s) for s in strides])
+        self._keep_offs = [(C.c_uint32 * max(1, len(o)))(*[int(x) for x in o]) for o in leaf_offsets]
+        self._offs = (C.c_void_p * self.k)(*[C.cast(a, C.c_void_p).value for a in self._keep_offs])
+
+    @property
+    def scratch_bytes(self) -> int:
+        out = C.c_uint64()
+        check(_lib.lib().srpc_frames_mixed_aos_scratch_bytes(self._plans, self.k, self._strides, C.byref(out)),
+              "srpc_frames_mixed_aos_scratch_bytes")
+        return out.value
+
+    @property
+    def tile(self) -> int:
+        """Calls per workgroup tile of ``unpack`` (``pack`` tiles as ``MixedFrames.tile``)."""
+        out = C.c_uint32()
+        check(_lib.lib().srpc_frames_mixed_aos_tile(self._plans, self.k, self._strides, C.byref(out)),
+              "srpc_frames_mixed_aos_tile")
+        return out.value
+
+    def _args(self, recs, first, cap):
+        arr = (C.c_void_p * self.k)(*[_dptr(r) for r in recs])
+        h_first = None if first is None else (C.c_uint64 * self.k)(*[int(x) for x in first])
+        h_cap = (C.c_uint64 * self.k)(*[int(x) for x in cap])
+        return arr, h_first, h_cap
+
+    def pack(self, recs, first, cap, method, index, ncalls: int, out, out_cap: int, offs=None, status=None,
+             stream=None) -> int:
+        """recs[k]: plan k's request structs; first / cap: per plan, in structs (first may be None)."""
+        arr, h_first, h_cap = self._args(recs, first, cap)
+        return _lib.lib().srpc_frames_pack_requests_mixed_aos(self._plans, self.k, arr, self._strides, self._offs,
+                                                              h_first, h_cap, _dptr(method), _dptr(index), ncalls,
+                                                              _dptr(out), out_cap, _dptr(offs), _dptr(status),
+                                                              _stream(stream))
+
+    def unpack(self, buf, buf_len: int, offs, nframes: int, method, index, ncalls: int, unanswered: int, recs, fills,
+               first, cap, codes, scratch, scratch_bytes: int, status=None, stream=None) -> int:
+        """recs[k]: plan k's reply structs; fills[k]: ``strides[k]`` host bytes for what no leaf covers."""
+        arr, h_first, h_cap = self._args(recs, first, cap)
+        keep = [C.create_string_buffer(bytes(f), max(1, len(bytes(f)))) for f in fills]
+        h_fill = (C.c_void_p * self.k)(*[C.cast(b, C.c_void_p).value for b in keep])
+        return _lib.lib().srpc_frames_unpack_replies_mixed_aos(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                               nframes, _dptr(method), _dptr(index), ncalls, unanswered,
+                                                               arr, self._strides, self._offs, h_fill, h_first, h_cap,
+                                                               _dptr(codes), _dptr(status), _dptr(scratch),
+                                                               scratch_bytes, _stream(stream))
+
+
 class MixedVarFrames:
     """A batch of calls of several methods in call order, string-bodied ones
     included (srpc_frames_pack_requests_mixed_var / _unpack_replies_mixed_var;
