@@ -3,9 +3,15 @@ have an instance -- all_kinds (17 B), Number behind the square request (53 B)
 and response (19 B) envelopes, TwoNumbers behind request / response envelopes
 -- packed and unpacked with the specialised kernels (whole tiles) plus the
 generic ones (the tail), against the oracle and against the generic kernels
-alone (SRPC_TUNE_REC_KERNEL 0), at sizes around the tile (1024 / 512 records)
-and with prefix mismatches inside the specialised part and in the tail (the
-first bad record's absolute index)."""
+alone (SRPC_TUNE_REC_KERNEL 0), at sizes around 1024 / 512 records and with
+prefix mismatches inside the specialised part and in the tail (the first bad
+record's absolute index).
+
+The 1024 / 512 of LAYOUTS are this module's size units: two of the real tiles
+of every layout but all_kinds (512 records for the responses, 256 for the
+requests, 16 for the requests' chunk pack).  tests/test_gpu_rec_layouts.py has
+the real tile of every instance, sizes around one tile, and the instance these
+layouts leave out (TwoNumbers behind the subtract / multiply requests)."""
 import numpy as np
 import pytest
 
@@ -72,6 +78,12 @@ def test_rec_kernels_vs_oracle(name, tiles, extra):
     p.tune(rec_kernel=0)
     assert gpu_pack(p, cols, n) == want
     p.tune(rec_kernel=2)  # both directions, whichever the plan would choose
+    assert gpu_pack(p, cols, n) == want
+    st = status_buf()
+    rc, back = gpu_unpack(p, want, n, [c.dtype for c in cols], status=st)
+    assert rc == 0 and read_status(st) == (0, 2**64 - 1)
+    for c, b in zip(cols, back):
+        assert c.tobytes() == b.tobytes()
 
 
 @pytest.mark.parametrize("name", ["square_request", "add_response"])
