@@ -43,8 +43,8 @@
 // srpc_frames_scatter_var (`BE32 len | response` into request order).
 // Methods registered with register_record_method take the same steps with a
 // handler over arrays of the caller's own structs: srpc_gpu_unpack_aos_fill into
-// a Req array -> handler -> srpc_gpu_pack_aos from a Resp array (bucket route
-// only).
+// a Req array -> handler -> srpc_gpu_pack_aos from a Resp array (this route, or
+// the ordered records route below).
 //
 // The buckets are filled with atomics: a handler sees its requests in an order
 // that differs from run to run, and no handler sees the order across methods.
@@ -68,6 +68,19 @@
 //   var_handler_t on its n = counts[k] requests), or the one ordered handler
 //   -> srpc_frames_pack_requests_mixed_var over the response plans with
 //   d_method = d_class -> the total (and, with unknown frames, the offsets).
+//
+// The ordered route over record methods (set_ordered_records /
+// set_ordered_records_handler; every method a register_record_method one with
+// sizeof(Req) <= 256) is the same skeleton over the methods' struct arrays:
+//
+//   srpc_frames_unpack_requests_mixed_aos (every frame classified and decoded
+//   into element `arrival rank` of its method's Req array, the bytes no leaf
+//   covers a Req{}'s) -> the record handlers on their counts[k] requests, or the
+//   one ordered records handler -> srpc_frames_pack_requests_mixed_aos over the
+//   framed response plans from the Resp arrays with d_method = d_class.
+//
+// The reply stream's size is known from the counts, so two batches stay in
+// flight as on the fixed ordered route.
 //
 // On both routes that serve string methods the string responses' sizes are
 // checked on the host against their columns before anything reads the chars:
@@ -224,6 +237,25 @@ struct ordered_var_batch {
     const uint64_t* const* resp_cap = nullptr;             // per method: the bytes of each response column
 };
 
+/// A batch in ordered records mode (batch_server::set_ordered_records_handler):
+/// ordered_batch's n, d_method, d_rank, counts and methods, with one array of
+/// the caller's own structs per method and side in place of its columns.  Frame
+/// i is element d_rank[i] of method d_method[i]'s Req array -- req_recs[k] +
+/// d_rank[i] * req_stride[k], every byte no leaf covers a Req{}'s -- and the
+/// handler writes the leaves of element d_rank[i] of resp_recs[k] (zeroed when
+/// allocated; only leaves are read).  Unknown frames as in ordered_batch.
+struct ordered_records_batch {
+    uint64_t n = 0;
+    const uint8_t* d_method = nullptr;   // device, n
+    const uint32_t* d_rank = nullptr;    // device, n
+    const uint64_t* counts = nullptr;    // host, methods + 1: frames per method, then the unknown ones
+    size_t methods = 0;
+    const void* const* req_recs = nullptr;   // per method: its device Req array
+    void* const* resp_recs = nullptr;        // per method: its device Resp array
+    const uint64_t* req_stride = nullptr;    // host, per method: sizeof(Req)
+    const uint64_t* resp_stride = nullptr;   // host, per method: sizeof(Resp)
+};
+
 struct batch_stats {
     uint64_t requests = 0;           // frames answered
     uint64_t gpu_batches = 0;        // batches that went through the GPU path
@@ -300,8 +332,9 @@ public:
     /// leaves and nothing else matters.  Handlers must not call a virtual
     /// function on these objects: a vtable slot holds a host pointer (Req) or
     /// zero (Resp).  Record methods and column methods mix freely in one server.
-    /// Bucket route only: with a record method registered, serve_connection
-    /// throws plan_error(SRPC_E_UNSUPPORTED) in either ordered mode.
+    /// The bucket route, or arrival order with set_ordered_records: with a
+    /// record method registered, serve_connection throws
+    /// plan_error(SRPC_E_UNSUPPORTED) in set_ordered / set_ordered_var mode.
     template <SrpcMessage Req, SrpcMessage Resp>
     void register_record_method(std::string method, record_handler_t handler) {
         method_entry& m = add_method<Req, Resp>("batch_server::register_record_method", std::move(method), false, true);
@@ -347,7 +380,7 @@ public:
     void set_ordered(bool on) {
         if (on == _ordered) return;
         _ordered = on;
-        if (!on) _ordered_var = false;
+        if (!on) _ordered_var = _ordered_rec = false;
         release();
     }
     bool ordered() const { return _ordered; }
@@ -385,6 +418,7 @@ public:
         if (on == _ordered_var && on == _ordered) return;
         _ordered_var = on;
         _ordered = on;
+        _ordered_rec = false;
         release();
     }
     bool ordered_var() const { return _ordered_var; }
@@ -397,6 +431,42 @@ public:
     void set_ordered_var_handler(ordered_var_handler_t handler) {
         _ovhandler = std::move(handler);
         set_ordered_var(true);
+    }
+
+    /// handler(batch, stream) over a whole batch of every record method in
+    /// arrival order (ordered_records_batch).
+    using ordered_records_handler_t = std::function<int(ordered_records_batch const&, hipStream_t)>;
+
+    /// Ordered mode over register_record_method methods (off by default; implies
+    /// ordered mode; set_ordered(false) clears it).  Request r of a method's
+    /// batch is the method's r-th frame in arrival order: a record handler sees
+    /// (d_reqs, d_resps, counts[k]) with its requests in the order they came, in
+    /// every run and across batches.  A batch goes through one
+    /// srpc_frames_unpack_requests_mixed_aos into the methods' Req arrays (every
+    /// byte no leaf covers a Req{}'s) and one srpc_frames_pack_requests_mixed_aos
+    /// over the response plans from their Resp arrays: no gather, no scatter, two
+    /// batches in flight.  Every registered method must be a record method with
+    /// sizeof(Req) <= 256 (sizeof(Resp) is free): serve_connection throws
+    /// plan_error(SRPC_E_UNSUPPORTED) for a register_method or
+    /// register_var_method method beside them, or a larger Req.  set_ordered /
+    /// set_ordered_var keep refusing record methods.
+    void set_ordered_records(bool on) {
+        if (on == _ordered_rec && on == _ordered) return;
+        _ordered_rec = on;
+        _ordered = on;
+        _ordered_var = false;
+        release();
+    }
+    bool ordered_records() const { return _ordered_rec; }
+    /// One handler for every record method, run once per batch instead of the
+    /// per-method handlers; implies set_ordered_records(true).  Timing and
+    /// warm-up are set_ordered_handler's: batches reach it in connection order on
+    /// the server's stream, frames the GPU path does not take are answered by the
+    /// CPU server after the batch's handler ran, and at serve start it is run on
+    /// a batch of one unknown frame.
+    void set_ordered_records_handler(ordered_records_handler_t handler) {
+        _orhandler = std::move(handler);
+        set_ordered_records(true);
     }
 
     uint64_t request_frame_bytes(size_t k = 0) const { return _m.at(k)->fin; }
@@ -418,8 +488,20 @@ public:
         if (_ordered && !_ordered_var && any_var_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a string-bodied method)",
                              SRPC_E_UNSUPPORTED);
-        if (_ordered && any_record_method())
+        if (_ordered && !_ordered_rec && any_record_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a record method)", SRPC_E_UNSUPPORTED);
+        if (_ordered_rec)
+            for (auto const& m : _m) {
+                if (m->var)
+                    throw plan_error("batch_server::serve_connection (ordered records mode with a string-bodied method)",
+                                     SRPC_E_UNSUPPORTED);
+                if (!m->rec)
+                    throw plan_error("batch_server::serve_connection (ordered records mode with a column method)",
+                                     SRPC_E_UNSUPPORTED);
+                if (m->req_stride > kRecordFillMax)
+                    throw plan_error("batch_server::serve_connection (ordered records mode with a Req above 256 bytes)",
+                                     SRPC_E_UNSUPPORTED);
+            }
         check(hipSetDevice(_dev));
         ensure();
         batch_stats st;
@@ -694,6 +776,9 @@ private:
         device_buffer<void> d_mix_index;
         device_buffer<uint32_t> d_rank;
     };
+    struct ordered_records_buffers {
+        device_buffer<void> d_scratch;  // the decode's tables and fills
+    };
     struct ordered_var_buffers {
         device_buffer<void> d_scratch;
         device_buffer<uint64_t> d_ends, d_total;
@@ -713,6 +798,8 @@ private:
                 std::vector<uint8_t> all(_max * m.req_stride);
                 for (uint64_t i = 0; i < _max; ++i) std::memcpy(all.data() + i * m.req_stride, m.req_fill.data(), m.req_stride);
                 check(hipMemcpy(m.d_reqs, all.data(), all.size(), hipMemcpyHostToDevice));
+            } else {  // the ordered warm-up's handlers run on element 0 before any decode wrote it
+                check(hipMemset(m.d_reqs, 0, _max * m.req_stride + 16));
             }
             return;
         }
@@ -793,6 +880,12 @@ private:
                        "srpc_frames_mixed_index_bytes");
             _od.d_mix_index.alloc(_mix_index_bytes + 16);
             _od.d_rank.alloc(4 * _max + 16);
+            if (_ordered_rec) {
+                check_srpc(srpc_frames_mixed_aos_scratch_bytes(_ord_in_plans.data(), static_cast<int>(K),
+                                                               _or_req_stride.data(), &_or_scratch_bytes),
+                           "srpc_frames_mixed_aos_scratch_bytes");
+                _or.d_scratch.alloc(_or_scratch_bytes + 16);
+            }
             if (_ordered_var) {
                 if (out_cap > 0xffffffffull) throw plan_error("batch_server: reply buffer over 4 GiB", SRPC_E_UNSUPPORTED);
                 uint64_t a = 0, b = 0;
@@ -831,6 +924,8 @@ private:
         _req_tbl.clear(), _resp_tbl.clear(), _resp_mut_tbl.clear();
         _ov_req_offs.clear(), _ov_c_req_offs.clear(), _ov_resp_offs.clear(), _ov_c_resp_offs.clear();
         _ov_req_scap.clear(), _ov_resp_cap.clear();
+        _or_req_recs.clear(), _or_c_req_recs.clear(), _or_resp_recs.clear(), _or_c_resp_recs.clear();
+        _or_req_stride.clear(), _or_resp_stride.clear(), _or_req_loffs.clear(), _or_resp_loffs.clear(), _or_fill.clear();
         _caps.assign(_m.size(), _max);
         _ov_slots = 0;
         for (auto& m : _m) {
@@ -852,6 +947,16 @@ private:
             _ov_req_scap.push_back(m->req_scap.data());
             _ov_resp_cap.push_back(m->resp_bytes.data());
             for (uint64_t* o : m->req_offs) _ov_slots += o ? 1 : 0;
+            // a record method's struct arrays (null and zero for the others)
+            _or_req_recs.push_back(m->d_reqs);
+            _or_c_req_recs.push_back(m->d_reqs);
+            _or_resp_recs.push_back(m->d_resps);
+            _or_c_resp_recs.push_back(m->d_resps);
+            _or_req_stride.push_back(m->req_stride);
+            _or_resp_stride.push_back(m->resp_stride);
+            _or_req_loffs.push_back(m->req_loffs.data());
+            _or_resp_loffs.push_back(m->resp_loffs.data());
+            _or_fill.push_back(m->req_fill.data());
         }
     }
 
@@ -859,7 +964,7 @@ private:
         for (auto& m : _m) m->release();
         for (slot& z : _slots) z.reset();
         _nslots = 0;
-        _b = {}, _bk = {}, _od = {}, _ov = {};
+        _b = {}, _bk = {}, _od = {}, _or = {}, _ov = {};
     }
 
     // ---- the steps of a batch, shared by the batches and the warm-up ----
@@ -1150,13 +1255,15 @@ private:
         }
     }
 
-    // -- the ordered routes (set_ordered, set_ordered_var): one decode, the handlers, one pack --
+    // -- the ordered routes (set_ordered, set_ordered_var, set_ordered_records): one decode, the handlers, one pack --
 
-    bool whole_batch_handler() const { return _ordered_var ? bool(_ovhandler) : bool(_ohandler); }
+    bool whole_batch_handler() const {
+        return _ordered_var ? bool(_ovhandler) : _ordered_rec ? bool(_orhandler) : bool(_ohandler);
+    }
 
-    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed[_var]
+    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed[_var|_aos]
     /// over the nf frames in d_in[0, used) into the methods' request columns
-    /// (chars and offsets too), the ranks when the ordered handler is set, then
+    /// (chars and offsets too) or Req arrays, the ranks when the ordered handler is set, then
     /// the counts (and the string slots' ends) on the host after one sync.
     void ordered_decode(uint64_t nf, uint64_t used) {
         const int K = static_cast<int>(_m.size());
@@ -1167,6 +1274,12 @@ private:
                            _ov_req_scap.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, _mix_index_bytes,
                            _b.d_counts, _ov.d_ends, _b.d_status, _ov.d_scratch, _ov_scratch_bytes, _s),
                        "srpc_frames_unpack_requests_mixed_var");
+        else if (_ordered_rec)
+            check_srpc(srpc_frames_unpack_requests_mixed_aos(
+                           _ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf, _or_req_recs.data(), _or_req_stride.data(),
+                           _or_req_loffs.data(), _or_fill.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index,
+                           _mix_index_bytes, _b.d_counts, _b.d_status, _or.d_scratch, _or_scratch_bytes, _s),
+                       "srpc_frames_unpack_requests_mixed_aos");
         else
             check_srpc(srpc_frames_unpack_requests_mixed(_ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf,
                                                          _req_tbl.data(), nullptr, _caps.data(), _b.d_cls,
@@ -1184,6 +1297,20 @@ private:
     void ordered_handlers(uint64_t nf, bool warm) {
         if (whole_batch_handler()) {
             const char* what = warm ? "ordered batch handler (warm-up)" : "ordered batch handler";
+            if (_ordered_rec) {
+                ordered_records_batch b;
+                b.n = nf;
+                b.d_method = _b.d_cls;
+                b.d_rank = _od.d_rank;
+                b.counts = _b.h_counts;
+                b.methods = _m.size();
+                b.req_recs = _or_c_req_recs.data();
+                b.resp_recs = _or_resp_recs.data();
+                b.req_stride = _or_req_stride.data();
+                b.resp_stride = _or_resp_stride.data();
+                check_srpc(_orhandler(b, _s), what);
+                return;
+            }
             auto fill = [&](auto& b) {
                 b.n = nf;
                 b.d_method = _b.d_cls;
@@ -1211,7 +1338,9 @@ private:
             method_entry& m = *_m[k];
             const uint64_t n = warm ? 1 : _b.h_counts[k];
             if (!n) continue;
-            check_srpc(m.var ? run_var_handler(m, n) : m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s),
+            check_srpc(m.var   ? run_var_handler(m, n)
+                       : m.rec ? m.rhandler(m.d_reqs, m.d_resps, n, _s)
+                               : m.handler(m.req_cols.data(), m.resp_cols.data(), n, _s),
                        warm ? "batch handler (warm-up)" : "batch handler");
         }
     }
@@ -1222,6 +1351,14 @@ private:
     /// sync here.
     void ordered_pack(uint64_t nf, bool unknown) {
         const int K = static_cast<int>(_m.size());
+        if (_ordered_rec) {  // the same from the Resp arrays
+            check_srpc(srpc_frames_pack_requests_mixed_aos(_ord_out_plans.data(), K, _or_c_resp_recs.data(),
+                                                           _or_resp_stride.data(), _or_resp_loffs.data(), nullptr,
+                                                           _caps.data(), _b.d_cls, _od.d_mix_index, nf, _b.d_out, out_cap(),
+                                                           nullptr, nullptr, _s),
+                       "srpc_frames_pack_requests_mixed_aos (replies)");
+            return;
+        }
         if (!_ordered_var) {  // (the flag a bad call would raise is not asked for)
             check_srpc(srpc_frames_pack_requests_mixed(_ord_out_plans.data(), K, _resp_tbl.data(), nullptr, _caps.data(),
                                                        _b.d_cls, _od.d_mix_index, nf, _b.d_out, out_cap(), nullptr, nullptr,
@@ -1524,17 +1661,20 @@ private:
     std::vector<uint8_t> _flat;
     bool _trace = std::getenv("SRPC_SERVER_TRACE") != nullptr;  // per-recv / per-batch timeline on stderr
     trace_point _tp;
-    bool _ordered = false, _ordered_var = false;
+    bool _ordered = false, _ordered_var = false, _ordered_rec = false;
     ordered_handler_t _ohandler;
     ordered_var_handler_t _ovhandler;
+    ordered_records_handler_t _orhandler;
     // the buffers (ensure / release)
     slot _slots[2];
     int _nslots = 0;
     batch_buffers _b;
     bucket_buffers _bk;
     ordered_buffers _od;
+    ordered_records_buffers _or;
     ordered_var_buffers _ov;
     uint64_t _cap = 0, _scratch_bytes = 0, _var_scratch_bytes = 0, _mix_index_bytes = 0, _ov_scratch_bytes = 0;
+    uint64_t _or_scratch_bytes = 0;
     bool _var_methods = false;  // a string method is registered
     uint32_t _ov_slots = 0;     // string leaves of all requests
     // per method, in registration order (build_tables)
@@ -1548,6 +1688,11 @@ private:
     std::vector<uint64_t* const*> _ov_req_offs, _ov_resp_offs;  // its leaves' offsets arrays
     std::vector<const uint64_t* const*> _ov_c_req_offs, _ov_c_resp_offs;
     std::vector<const uint64_t*> _ov_req_scap, _ov_resp_cap;  // bytes a decode may fill / of its response columns
+    std::vector<void*> _or_req_recs, _or_resp_recs;           // its Req / Resp array (record methods)
+    std::vector<const void*> _or_c_req_recs, _or_c_resp_recs;
+    std::vector<uint64_t> _or_req_stride, _or_resp_stride;    // sizeof(Req), sizeof(Resp)
+    std::vector<const uint32_t*> _or_req_loffs, _or_resp_loffs;
+    std::vector<const void*> _or_fill;                        // a Req{}'s bytes
 };
 
 }  // namespace srpc::gpu

@@ -777,6 +777,14 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
  * values.  Only leaf bytes of the chunk's own structs are read; h_stride[k] is
  * any value below 2^32.  One launch; no scratch.
  *
+ * The ordered reply pack of a server over struct arrays is
+ * srpc_frames_pack_requests_mixed_aos itself, which by its contract writes the
+ * frames of any fixed-size plans with framed prefixes from struct arrays:
+ * called with the framed RESPONSE plans, the Resp arrays, d_method = d_class and
+ * the d_index srpc_frames_unpack_requests_mixed_aos wrote, it writes the reply
+ * stream in arrival order.  An unknown frame is that call's bad call: zero
+ * bytes, d_offs[i + 1] == d_offs[i], for the caller to answer in its place.
+ *
  * srpc_frames_unpack_replies_mixed_aos: d_codes, the flags and
  * first_bad_record are the column call's on the same input.  h_fill[k] is
  * h_stride[k] <= 256 host bytes (e.g. the image of a Resp{}), copied during the
@@ -786,7 +794,8 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
  * (which also get unanswered_code); every other byte comes from plan k's fill.
  * No byte outside elements [h_first[k], h_first[k] + calls of k in the chunk)
  * of any array is written, and nothing is written for a BAD call.
- * d_scratch (16-byte aligned, srpc_frames_mixed_aos_scratch_bytes: the plans'
+ * d_scratch (16-byte aligned, srpc_frames_mixed_aos_scratch_bytes, which takes
+ * the plans of either side, request prefixes of 4 bytes included: the plans'
  * per-struct-byte source tables and fills, 3 S16 + 16 bytes per plan, S16 =
  * h_stride[k] rounded up to 16) receives them by by-value launches: no host
  * copy outlives the call.
@@ -815,10 +824,11 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
  *   4. SRPC_E_ALIGN: d_buf, d_out, an array, d_scratch (16), the index (8),
  *      d_offs (4), or an offset or stride against its leaf's size;
  *   5. SRPC_E_CAPACITY: scratch_bytes or out_cap. */
-int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                         uint64_t* out);
-/* Testing hook: calls per workgroup tile of the decode (the pack's is srpc_frames_mixed_tile). */
-int srpc_frames_mixed_aos_tile(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+/* Testing hook: calls per workgroup tile of a decode into struct arrays with
+ * these plans (the pack's is srpc_frames_mixed_tile). */
+int srpc_frames_mixed_aos_tile(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                uint32_t* calls_per_tile);
 int srpc_frames_pack_requests_mixed_aos(const srpc_plan* const* req_plans, int nplans,
                                         const void* const* d_recs, const uint64_t* h_stride,
@@ -899,6 +909,75 @@ int srpc_frames_unpack_requests_mixed(const srpc_plan* const* req_plans, int npl
                                       void* d_index, uint64_t index_bytes,
                                       uint64_t* d_counts /* nplans + 1, out */,
                                       srpc_unpack_status* d_status, void* stream);
+
+/* ---- batches of request frames of several methods into struct arrays, in
+ * arrival order (server side; added within ABI 8) --------------------------------
+ * srpc_frames_unpack_requests_mixed with one device array of the caller's own
+ * structs per plan in place of its columns: the server's counterpart of
+ * srpc_frames_pack_requests_mixed_aos.  Everything that is not about where a
+ * frame's fields live is the section above, unchanged: K, the framed request
+ * plans, the frame extents, the classification rule (srpc_frames_classify's,
+ * the first matching plan wins), rank(i), d_counts and the status rules.
+ * d_class and d_index are byte-identical to what the column call writes for the
+ * same input, so the index serves srpc_frames_mixed_ranks and the reply pack
+ * (srpc_frames_pack_requests_mixed_aos over the response plans, see there).
+ *
+ * Structs: the conventions of srpc_frames_unpack_replies_mixed_aos.  Plan k's
+ * requests live in d_recs[k] (host array of K device pointers, 16-byte
+ * aligned), h_stride[k] <= 256 bytes each, leaf f at byte h_leaf_offs[k][f]
+ * (u32): natural alignment, no two leaves sharing a byte, no leaf past the
+ * stride.  h_fill[k] is h_stride[k] host bytes (e.g. the image of a Req{}),
+ * copied during the call.
+ *
+ * A frame of class k is element h_first[k] + rank(i) of plan k's array.  When
+ * that element is below h_cap[k] its struct is written whole, exactly once, and
+ * never read: leaf bytes come from the frame, raw little-endian, every other
+ * byte from plan k's fill.
+ *   - nothing is written for an unknown frame;
+ *   - nothing is written for a frame whose element is at or past h_cap[k]: it
+ *     keeps its class and raises SRPC_STATUS_BOUNDS, first_bad_record the
+ *     smallest such i;
+ *   - no byte outside elements [h_first[k], h_first[k] + frames of k) of any
+ *     array is written;
+ *   - no byte outside [d_buf, d_buf + buf_len) is read, whatever d_offs holds:
+ *     the decode pass checks every extent again and does not trust d_class;
+ *   - *d_status (may be NULL) is reset by the call;
+ *   - the call is stream-ordered, allocates nothing, waits on nothing on the
+ *     host or the device and can be captured; its launches (status reset, one
+ *     per 2 KiB of scratch, classify, the index's two, decode) do not depend on
+ *     the data; work is bounded by buf_len + nframes * max_k F_k.  The stream
+ *     is read twice.
+ *
+ * d_scratch (16-byte aligned) receives the plans' tables and fills by by-value
+ * launches; its size and the decode's frames per tile are
+ * srpc_frames_mixed_aos_scratch_bytes and srpc_frames_mixed_aos_tile, called
+ * with the request plans.  The classify pass keeps the column call's tile.  The
+ * decode stages and ranks as the column kernel; then, the frames of one plan
+ * that have an element being consecutive elements of its array, it assembles
+ * every 16-byte piece of those K slices from the image or the fill through the
+ * plan's table and stores it whole; a slice's first and last bytes that share a
+ * piece with a neighbouring tile's slice are stored bytewise.
+ *
+ * Refused with nothing launched, in this order:
+ *   1. SRPC_E_INVALID (before any plan is read): the column call's NULL and
+ *      range checks with d_recs, h_stride, h_leaf_offs, h_leaf_offs[k], h_fill,
+ *      h_fill[k], d_scratch and d_recs[k] (where h_cap[k] leaves an element)
+ *      among the pointers; h_stride[k] == 0 or >= 2^32;
+ *   2. SRPC_E_UNSUPPORTED: a string plan, a prefix under 4 bytes, more than
+ *      SRPC_FRAMES_MIXED_MAX_FIELDS leaves, a stride above 256;
+ *   3. SRPC_E_INVALID: overlapping leaves, or a leaf past the stride;
+ *   4. SRPC_E_ALIGN: d_buf, an array, d_scratch (16), the index, d_counts (8),
+ *      d_offs (4), or an offset or stride against its leaf's size;
+ *   5. SRPC_E_CAPACITY: the index or scratch_bytes. */
+int srpc_frames_unpack_requests_mixed_aos(const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
+                                          uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                          void* const* d_recs, const uint64_t* h_stride,
+                                          const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+                                          const uint64_t* h_first, const uint64_t* h_cap,
+                                          uint8_t* d_class /* nframes, out */, void* d_index,
+                                          uint64_t index_bytes, uint64_t* d_counts /* nplans + 1, out */,
+                                          srpc_unpack_status* d_status, void* d_scratch,
+                                          uint64_t scratch_bytes, void* stream);
 
 /* ---- batches of calls of several methods with string bodies, in call order
  * (client side; added within ABI 8) ----------------------------------------------

@@ -108,6 +108,8 @@ SIGNATURES = {
                                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_unpack_requests_mixed": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
                                                     _vp, _vp, _vp]),
+    "srpc_frames_unpack_requests_mixed_aos": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_mixed_var_scratch_bytes": (C.c_int, [_vp, C.c_int, _u64, C.POINTER(_u64)]),
     "srpc_frames_mixed_var_tile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "srpc_frames_pack_requests_mixed_var": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp,

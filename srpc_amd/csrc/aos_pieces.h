@@ -1,5 +1,6 @@
-// aos_pieces.h -- internal: what the reply decodes into struct arrays share
-// (frames_aos.hip: one plan; mixed_aos.hip: a plan per call): the per-struct-byte
+// aos_pieces.h -- internal: what the frame decodes into struct arrays share
+// (frames_aos.hip: one plan; mixed_aos.hip: a plan per call; mixed_req_aos.hip:
+// a plan per request frame, through mixed_aos_common.h): the per-struct-byte
 // source table a 16-byte piece of the array is assembled through, its host-side
 // builder and the layout checks of a struct with leaves at given offsets.
 #pragma once

@@ -5,7 +5,8 @@
 //
 // The index, mix_ranks, the tile, the granule's byte offset, the LDS lookups by
 // a lane's own plan, the prefix templates and the image are mixed.hip's
-// (mixed_common.h); only the field step differs.
+// (mixed_common.h); only the field step differs.  The slices and the piece
+// step of the decode are shared with the request decode (mixed_aos_common.h).
 //
 //   k_mixed_pack_aos    mix_pack_tile<true>: a lane's leaves come from
 //       recs[k] + e * stride[k] + loff[f]; lanes of one plan hold consecutive
@@ -37,6 +38,7 @@
 #include <cstring>
 
 #include "aos_pieces.h"
+#include "mixed_aos_common.h"
 #include "mixed_common.h"
 #include "mixed_var_common.h"
 #include "plan.h"
@@ -48,26 +50,6 @@ namespace {
 struct MixAosStride {
     uint32_t stride[kMixPlans];
 };
-
-struct MixAos {
-    uint8_t* recs[kMixPlans];     // plan k's struct array
-    uint32_t stride[kMixPlans];   // struct bytes
-    uint16_t tab[kMixPlans];      // byte offset of plan k's table inside the description
-    uint16_t fill[kMixPlans];     // ... of its fill record
-    uint32_t desc_bytes;          // tables and fills (a multiple of 16)
-};
-
-// Table and fill bytes of the plans' strides: 2 S16 + S16 + 16 each.
-inline uint32_t aos_desc_bytes(const uint64_t* h_stride, int nplans) {
-    uint32_t b = 0;
-    for (int k = 0; k < nplans; ++k) b += 3 * s16_of(static_cast<uint32_t>(h_stride[k])) + 16;
-    return b;
-}
-
-// Calls per tile of the decode: mix_tile with the tables and fills taken out of
-// the image's budget, so image + tables + fills stay within the column kernel's
-// image (at the floor of 16 calls: 16 * 1280 + 12.5 KiB, still under 33 KiB).
-inline uint32_t mix_aos_tile(uint32_t fmax, uint32_t desc_bytes) { return mix_tile(fmax, kMixImage - desc_bytes); }
 
 inline size_t mix_aos_lds(const MixArgs& a, uint32_t tb, uint32_t desc_bytes) {
     const size_t head = a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u) + tb + 4 * a.T + 2 * a.T;
@@ -91,15 +73,7 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     __shared__ uint32_t wcnt[kMixLds];
     __shared__ MixLds d;
-    // the tile's slice of plan k's array, and plan k's struct
-    __shared__ uint64_t sbyte0[kMixPlans];     // the slice's first byte inside the array
-    __shared__ uint8_t* srecs[kMixPlans];
-    __shared__ uint32_t sfirst[kMixPlans];     // rank of the slice's first call
-    __shared__ uint32_t scount[kMixPlans];     // its calls
-    __shared__ uint32_t sbase[kMixPlans];      // its first entry of slot[]
-    __shared__ uint32_t pbase[kMixPlans + 1];  // its first (plan, piece) pair
-    __shared__ uint32_t sstride[kMixPlans];
-    __shared__ uint16_t stab[kMixPlans], sfill[kMixPlans];
+    __shared__ MixAosSlices sl;
     const uint32_t K = a.nplans;
     const uint32_t lo_bytes = (4 * (a.T + 1) + 7) & ~7u;
     const uint32_t tb = a.tmpl[K - 1] + ((a.prefix_len[K - 1] + 7) & ~7u);
@@ -112,21 +86,12 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
 
     mix_lds_fill(d, a);
     mix_templates(tmpl, a);
-    if (threadIdx.x < K) {
-        const uint32_t k = threadIdx.x;
-        srecs[k] = x.recs[k];
-        sstride[k] = x.stride[k];
-        stab[k] = x.tab[k];
-        sfill[k] = x.fill[k];
-        sfirst[k] = 0xffffffffu;
-        scount[k] = 0;
-    }
+    mix_aos_slices_init(sl, x, K);
     for (uint32_t c = threadIdx.x; c < x.desc_bytes / 16; c += kBlock) reinterpret_cast<uint4*>(dsc)[c] = desc[c];
     const uint64_t c0 = static_cast<uint64_t>(blockIdx.x) * a.T;
     const uint64_t g = c0 / kMixGranule;
     const uint32_t j0 = static_cast<uint32_t>(c0 - g * kMixGranule);
     const uint64_t i = g * kMixGranule + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63;
     const uint32_t nr = c0 < nframes ? static_cast<uint32_t>(min<uint64_t>(a.T, nframes - c0)) : 0;
     req_offsets(lo, a.T, offs, nframes, c0, buf_len);
 
@@ -136,16 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
     const uint32_t j = threadIdx.x - j0;
 
     // the tile's slices: good calls of one plan are consecutive ranks, ascending with the lane
-    for (uint32_t k = 0; k < K; ++k) {
-        const uint64_t b = __ballot(good && r.cls == k);
-        if (b) {
-            const uint32_t rk = __shfl(r.rank, __ffsll(static_cast<long long>(b)) - 1, 64);
-            if (lane == 0) {
-                atomicMin(&sfirst[k], rk);
-                atomicAdd(&scount[k], static_cast<uint32_t>(__popcll(b)));
-            }
-        }
-    }
+    mix_aos_slices_count(sl, K, r, good);
 
     // 1. the span of the tile's frames -> image, from a 16-byte boundary (ends with a barrier)
     const ReqSpan sp = req_stage(img, lo, nr, a.img, buf, buf_len);
@@ -157,91 +113,9 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
         if (y.flag && st) report_bad(st, y.flag, i);
         pos[j] = !y.decoded ? kPosZero : y.in_img ? y.q : kPosGlobal;
     }
-    if (threadIdx.x <= K) {
-        uint32_t sb = 0, pb = 0;
-        for (uint32_t q = 0; q < threadIdx.x; ++q) {
-            const uint32_t n = scount[q];
-            const uint64_t b0 = (d.first[q] + sfirst[q]) * sstride[q];
-            sb += n;
-            pb += n ? static_cast<uint32_t>(((b0 & 15) + static_cast<uint64_t>(n) * sstride[q] + 15) >> 4) : 0;
-        }
-        pbase[threadIdx.x] = pb;
-        if (threadIdx.x < K) {
-            sbase[threadIdx.x] = sb;
-            sbyte0[threadIdx.x] = scount[threadIdx.x] ? (d.first[threadIdx.x] + sfirst[threadIdx.x]) * sstride[threadIdx.x] : 0;
-        }
-    }
-    __syncthreads();
-    if (good) slot[sbase[r.cls] + (r.rank - sfirst[r.cls])] = static_cast<uint16_t>(j);
-    __syncthreads();
 
     // 3. image, zero and fill -> the slices, one lane per (plan, 16-byte piece)
-    const uint32_t total = pbase[K];
-    for (uint32_t xx = threadIdx.x; xx < total; xx += kBlock) {
-        uint32_t k = 0;
-        for (uint32_t q = 1; q < K; ++q) k = pbase[q] <= xx ? q : k;
-        const uint32_t stride = sstride[k];
-        const uint64_t B0 = sbyte0[k];
-        const uint32_t a0 = static_cast<uint32_t>(B0 & 15);
-        const uint32_t nbytes = scount[k] * stride;     // <= 256 * 256
-        const uint32_t p0 = 16 * (xx - pbase[k]);       // the piece, from the slice's first piece on
-        const uint32_t x0 = p0 > a0 ? p0 - a0 : 0;      // its first byte of the slice
-        const uint32_t x1 = min(p0 + 16 - a0, nbytes);  // ... and past its last
-        const uint32_t b0 = x0 + a0 - p0, b1 = x1 + a0 - p0;  // the same, inside the piece
-        const uint16_t* tab = reinterpret_cast<const uint16_t*>(dsc + stab[k]);
-        const uint8_t* fill = dsc + sfill[k];
-        const uint16_t* sl = slot + sbase[k];
-        uint32_t e = x0 / stride;
-        uint32_t kk = x0 - e * stride;
-        uint32_t jj = sl[e];
-        uint32_t p = pos[jj];
-        uint64_t vlo = 0, vhi = 0;
-        uint32_t b = b0;
-        while (b < b1) {
-            const uint32_t t = tab[kk];
-            const uint32_t m = min(t >> 12, b1 - b), w = t & 0xfff;
-            uint64_t v = 0;
-            if (w == kSrcFill) {
-                v = lds_u64(fill, kk);
-            } else if (p < kPosGlobal) {
-                v = lds_u64(img, p + w);
-            } else if (p == kPosGlobal) {
-                const uint8_t* gp = buf + lo[jj] + w;  // inside the frame: w + m <= F
-                for (uint32_t y = 0; y < m; ++y) v |= static_cast<uint64_t>(gp[y]) << (8 * y);
-            }
-            piece_put(vlo, vhi, b, v, m);
-            b += m;
-            kk += m;
-            if (kk == stride) {  // runs end with their struct
-                kk = 0;
-                ++e;
-                if (b < b1) {  // b < b1 keeps e inside the slice
-                    jj = sl[e];
-                    p = pos[jj];
-                }
-            }
-        }
-        uint8_t* dst = srecs[k] + (B0 - a0) + p0;
-        if (b1 - b0 == 16) {
-            __builtin_nontemporal_store(aos_u32x4{static_cast<uint32_t>(vlo), static_cast<uint32_t>(vlo >> 32),
-                                                  static_cast<uint32_t>(vhi), static_cast<uint32_t>(vhi >> 32)},
-                                        reinterpret_cast<aos_u32x4*>(dst));
-        } else {  // a slice's first or last piece: its own bytes only
-            for (uint32_t y = b0; y < b1; ++y)
-                dst[y] = static_cast<uint8_t>(y < 8 ? vlo >> (8 * y) : vhi >> (8 * (y - 8)));
-        }
-    }
-}
-
-// The arguments both calls share, checked before any plan is read.
-bool aos_args_invalid(const void* const* d_recs, const uint64_t* h_stride, const uint32_t* const* h_leaf_offs,
-                      const uint64_t* h_first, const uint64_t* h_cap, int nplans) {
-    for (int k = 0; k < nplans; ++k) {
-        if (h_stride[k] == 0 || h_stride[k] >= (1ull << 32) || !h_leaf_offs[k]) return true;
-        const uint64_t first = h_first ? h_first[k] : 0;
-        if (h_cap[k] > first && !d_recs[k]) return true;
-    }
-    return false;
+    mix_aos_store<true>(sl, d, K, r, good, j, img, lo, pos, slot, dsc, buf);
 }
 
 // Every leaf inside the stride and no two sharing a byte (any stride below 2^32).
@@ -253,22 +127,6 @@ int aos_leaves_ok(const srpc_plan* p, const uint32_t* offs, uint64_t stride) {
                 return SRPC_E_INVALID;
     }
     return SRPC_OK;
-}
-
-// Each leaf's address inside element 0 of its plan's array, as mix_args's columns.
-struct AosCols {
-    const void* leaf[kMixFields];
-    const void* const* plan[kMixPlans];
-};
-
-void aos_cols(const srpc_plan* const* plans, int nplans, const void* const* d_recs,
-              const uint32_t* const* h_leaf_offs, AosCols* c) {
-    uint32_t nf = 0;
-    for (int k = 0; k < nplans; ++k) {
-        c->plan[k] = c->leaf + nf;
-        for (uint32_t f = 0; f < plans[k]->nfields; ++f)
-            c->leaf[nf++] = static_cast<const uint8_t*>(d_recs[k]) + h_leaf_offs[k][f];
-    }
 }
 
 __global__ void k_mixed_aos_reset_status(srpc_unpack_status* st) {
@@ -286,26 +144,26 @@ using namespace srpc_impl;
 
 extern "C" {
 
-int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                         uint64_t* out) {
-    if (!reply_plans || !h_stride || !out || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    if (!plans || !h_stride || !out || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] == 0) return SRPC_E_INVALID;
     uint32_t fmax = 0;
-    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    if (int rc = mix_plans_ok(plans, nplans, 4, &fmax)) return rc;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
     *out = aos_desc_bytes(h_stride, nplans);
     return SRPC_OK;
 }
 
-int srpc_frames_mixed_aos_tile(const srpc_plan* const* reply_plans, int nplans, const uint64_t* h_stride,
+int srpc_frames_mixed_aos_tile(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                uint32_t* calls_per_tile) {
-    if (!reply_plans || !h_stride || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    if (!plans || !h_stride || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] == 0) return SRPC_E_INVALID;
     uint32_t fmax = 0;
-    if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
+    if (int rc = mix_plans_ok(plans, nplans, 4, &fmax)) return rc;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
     *calls_per_tile = mix_aos_tile(fmax, aos_desc_bytes(h_stride, nplans));
@@ -366,26 +224,9 @@ int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, in
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] > kAosMaxStride) return SRPC_E_UNSUPPORTED;
     // the tables and the fills, as they will lie in scratch and in LDS
-    alignas(16) uint8_t desc[kMixPlans * (3 * kAosMaxStride + 16)] = {};
+    AosDesc desc;
     MixAos x{};
-    x.desc_bytes = aos_desc_bytes(h_stride, nplans);
-    uint32_t at = 0;
-    for (int k = 0; k < nplans; ++k) {
-        const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
-        int32_t from[kAosMaxStride];
-        if (int rc = aos_sources(reply_plans[k], h_leaf_offs[k], stride, from)) return rc;
-        aos_run_table(from, stride, reinterpret_cast<uint16_t*>(desc + at));
-        x.tab[k] = static_cast<uint16_t>(at);
-        at += 2 * s16_of(stride);
-    }
-    for (int k = 0; k < nplans; ++k) {
-        const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
-        std::memcpy(desc + at, h_fill[k], stride);
-        x.fill[k] = static_cast<uint16_t>(at);
-        x.recs[k] = static_cast<uint8_t*>(d_recs[k]);
-        x.stride[k] = stride;
-        at += s16_of(stride) + 16;
-    }
+    if (int rc = aos_describe(reply_plans, nplans, d_recs, h_stride, h_leaf_offs, h_fill, &desc, &x)) return rc;
     if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4) || !aligned(d_scratch, 16)) return SRPC_E_ALIGN;
     for (int k = 0; k < nplans; ++k)
         if (!aligned(d_recs[k], 16) || !aos_layout_aligned(reply_plans[k], h_leaf_offs[k], h_stride[k]))
@@ -404,7 +245,7 @@ int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, in
         if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
     }
     if (!ncalls) return SRPC_OK;
-    if (int rc = mix_upload(desc, x.desc_bytes, d_scratch, s)) return rc;
+    if (int rc = mix_upload(desc.bytes, x.desc_bytes, d_scratch, s)) return rc;
     const uint32_t grid = static_cast<uint32_t>((ncalls + a.T - 1) / a.T);
     launch(k_mixed_unpack_aos, dim3(grid), dim3(kBlock), static_cast<uint32_t>(mix_aos_lds(a, tb, x.desc_bytes)), s, a, x,
            static_cast<const uint4*>(d_scratch), d_method, static_cast<const uint32_t*>(d_index), mix_rows(ncalls), ncalls,

@@ -7,6 +7,7 @@
 // lookups and prefix templates; for mixed.hip and mixed_aos.hip (the client
 // side over columns and over struct arrays) the request pack of a tile
 // (mix_pack_tile) and the reply decode's judgement of a frame (mix_judge).
+// What the two decodes into struct arrays share is mixed_aos_common.h.
 #pragma once
 
 #include <algorithm>
@@ -449,5 +450,10 @@ __device__ __forceinline__ MixReply mix_judge(const MixLds& d, const MixLane& r,
 int mix_index_launch(const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* table, uint64_t* d_counts,
                      srpc_unpack_status* d_status, hipStream_t s);
 int mix_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
+
+// mixed_req.hip: the classify pass of the server-side decodes over fixed-size
+// plans (a.T = mix_tile: the column call's tile), nframes > 0.
+void req_classify_launch(const MixArgs& a, uint32_t tmpl_bytes, const uint8_t* d_buf, uint64_t buf_len,
+                         const uint32_t* d_offs, uint64_t nframes, uint8_t* d_class, hipStream_t s);
 
 }  // namespace srpc_impl

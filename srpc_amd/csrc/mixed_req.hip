@@ -132,6 +132,15 @@ __global__ __launch_bounds__(kBlock) void k_req_decode(MixArgs a, const uint8_t*
 }
 
 }  // namespace
+
+// k_req_classify over nframes frames (mixed_req_aos.hip's first pass too).
+void req_classify_launch(const MixArgs& a, uint32_t tmpl_bytes, const uint8_t* d_buf, uint64_t buf_len,
+                         const uint32_t* d_offs, uint64_t nframes, uint8_t* d_class, hipStream_t s) {
+    const uint32_t grid = static_cast<uint32_t>((nframes + a.T - 1) / a.T);
+    const uint32_t lds = a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
+    launch(k_req_classify, dim3(grid), dim3(kBlock), lds + tmpl_bytes, s, a, d_buf, buf_len, d_offs, nframes, d_class);
+}
+
 }  // namespace srpc_impl
 
 using namespace srpc_impl;
@@ -163,8 +172,7 @@ int srpc_frames_unpack_requests_mixed(const srpc_plan* const* req_plans, int npl
         if (int rc = mix_status_reset_launch(d_status, s)) return rc;
     const uint32_t grid = static_cast<uint32_t>((nframes + a.T - 1) / a.T);
     const uint32_t lds = a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
-    if (nframes)
-        launch(k_req_classify, dim3(grid), dim3(kBlock), lds + tb, s, a, d_buf, buf_len, d_offs, nframes, d_class);
+    if (nframes) req_classify_launch(a, tb, d_buf, buf_len, d_offs, nframes, d_class, s);
     // unknown frames (0xFF) are ids >= K: column K of the index; no status here
     if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
     if (nframes)

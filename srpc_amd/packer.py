@@ -570,7 +570,8 @@ class MixedFrames:
 class MixedAosFrames:
     """``MixedFrames.pack`` / ``unpack`` with one device array of structs per
     plan in place of its columns (srpc_frames_pack_requests_mixed_aos /
-    _unpack_replies_mixed_aos; the index is ``MixedFrames.index``).
+    _unpack_replies_mixed_aos; the index is ``MixedFrames.index``), and the
+    server's ``unpack_requests`` (srpc_frames_unpack_requests_mixed_aos).
     ``strides[k]``: plan k's struct bytes, ``leaf_offsets[k][f]``: the byte
     offset of leaf f in it.  Every call returns the C status (negative: refused,
     nothing launched)."""
@@ -592,7 +593,8 @@ class MixedAosFrames:
 
     @property
     def tile(self) -> int:
-        """Calls per workgroup tile of ``unpack`` (``pack`` tiles as ``MixedFrames.tile``)."""
+        """Calls per workgroup tile of ``unpack`` and of ``unpack_requests``'s decode
+        (``pack`` tiles as ``MixedFrames.tile``)."""
         out = C.c_uint32()
         check(_lib.lib().srpc_frames_mixed_aos_tile(self._plans, self.k, self._strides, C.byref(out)),
               "srpc_frames_mixed_aos_tile")
@@ -624,6 +626,23 @@ class MixedAosFrames:
                                                                arr, self._strides, self._offs, h_fill, h_first, h_cap,
                                                                _dptr(codes), _dptr(status), _dptr(scratch),
                                                                scratch_bytes, _stream(stream))
+
+    def unpack_requests(self, buf, buf_len: int, offs, nframes: int, recs, fills, first, cap, cls, index,
+                        index_bytes: int, counts, scratch, scratch_bytes: int, status=None, stream=None) -> int:
+        """Server side (srpc_frames_unpack_requests_mixed_aos): classify the
+        frames against these request plans and decode each into element
+        ``first[k] + rank`` of ``recs[k]``, its plan's request structs, bytes no
+        leaf covers from ``fills[k]``; ``cls``, ``index`` and ``counts`` are
+        outputs.  The ordered reply pack is ``pack`` of the response plans'
+        MixedAosFrames with ``method=cls`` and this ``index``."""
+        arr, h_first, h_cap = self._args(recs, first, cap)
+        keep = [C.create_string_buffer(bytes(f), max(1, len(bytes(f)))) for f in fills]
+        h_fill = (C.c_void_p * self.k)(*[C.cast(b, C.c_void_p).value for b in keep])
+        return _lib.lib().srpc_frames_unpack_requests_mixed_aos(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                                nframes, arr, self._strides, self._offs, h_fill, h_first,
+                                                                h_cap, _dptr(cls), _dptr(index), index_bytes,
+                                                                _dptr(counts), _dptr(status), _dptr(scratch),
+                                                                scratch_bytes, _stream(stream))
 
 
 class MixedVarFrames:
