@@ -61,7 +61,13 @@
 // request is the next struct of its leg's request array and its reply is
 // written whole into the next struct of its reply array, so a trace over
 // objects keeps its call order and its one exchange per chunk without a column
-// copy of any message.
+// copy of any message.  `call_mixed` takes record legs as all of its legs or
+// none.  `call_legs` is the same loop (run_mixed) without that restriction: any
+// mix of leg, leg_var and leg_records legs, with
+// srpc_frames_pack_requests_mixed_legs and
+// srpc_frames_unpack_replies_mixed_legs as its pack and decode calls, so a
+// client that keeps its objects as structs and has one string-bodied method
+// keeps its call order across all of them.
 //
 // Every loop counts a chunk's replies by one rule (tally_replies,
 // reply_walk.hpp): from the codes when the decode flagged nothing, otherwise
@@ -338,20 +344,50 @@ public:
     /// absolute over the whole call; the host makes no pass over them.
     call_stats call_mixed(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
                           var_call_limits lim, hipStream_t stream = nullptr) {
+        return run_mixed(legs, d_method, n, d_codes, lim, stream, false);
+    }
+
+    /// call_mixed without its restriction on the kinds of legs: any mix of
+    /// leg, leg_var and leg_records legs in one ordered batch, packed by
+    /// srpc_frames_pack_requests_mixed_legs and decoded by
+    /// srpc_frames_unpack_replies_mixed_legs, one exchange per chunk.  Every
+    /// leg keeps its own contract: a column leg's and a string leg's columns
+    /// and offsets as call_mixed states them; a record leg's d_resps[r] is
+    /// written whole -- the reply's leaves, every other byte from its `proto`
+    /// -- and both its arrays are 16-byte aligned.  `lim` is used when a leg is
+    /// string-bodied.  The errors, the capacity rules, the unanswered calls and
+    /// call_stats are call_mixed's; a flagged chunk is judged on the host frame
+    /// by frame, a record leg as the fixed plan it is.
+    call_stats call_legs(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
+                         var_call_limits lim = {}, hipStream_t stream = nullptr) {
+        return run_mixed(legs, d_method, n, d_codes, lim, stream, true);
+    }
+
+private:
+    /// The chunk loop of call_mixed and call_legs.  The form of the batch --
+    /// fixed columns, struct arrays, columns with strings, or (call_legs) legs
+    /// of any kind -- picks the pack call, the decode call and the scratch
+    /// sizing; everything else is one path.
+    call_stats run_mixed(std::vector<mixed_leg> const& legs, const uint8_t* d_method, uint64_t n, uint8_t* d_codes,
+                         var_call_limits lim, hipStream_t stream, bool any_kinds) {
         check(hipSetDevice(_dev));
+        const std::string who = any_kinds ? "batch_client::call_legs" : "batch_client::call_mixed";
+        auto error = [&who](const char* what, int code) { return plan_error((who + what).c_str(), code); };
         const size_t K = legs.size();
-        if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes)))
-            throw plan_error("batch_client::call_mixed", SRPC_E_INVALID);
-        bool any_var = false;
+        if (K == 0 || K > SRPC_FRAMES_MAX_PLANS || (n && (!d_method || !d_codes))) throw error("", SRPC_E_INVALID);
+        bool any_str = false;
         size_t nrec = 0;
         for (mixed_leg const& l : legs) {
-            any_var = any_var || l.req_var || l.resp_var;
+            any_str = any_str || l.req_var || l.resp_var;
             nrec += l.records;
         }
-        const bool recs = nrec != 0;  // struct-array legs: all of them, or none
-        if (recs && (nrec != K || any_var))
-            throw plan_error("batch_client::call_mixed (record legs beside column legs)", SRPC_E_UNSUPPORTED);
-        uint64_t fin = any_var ? lim.max_request_bytes : 0, fout = any_var ? lim.max_reply_bytes : 0;
+        // call_mixed: struct-array legs are all of the legs, or none
+        if (!any_kinds && nrec && (nrec != K || any_str))
+            throw error(" (record legs beside column legs)", SRPC_E_UNSUPPORTED);
+        const bool recs = !any_kinds && nrec != 0;
+        // the string-aware calls: u64 totals, frames found by their offsets, out_cap under 4 GiB
+        const bool any_var = any_kinds || any_str;
+        uint64_t fin = any_str ? lim.max_request_bytes : 0, fout = any_str ? lim.max_reply_bytes : 0;
         std::vector<const srpc_plan*> rq(K), rs(K);
         std::vector<const void* const*> rqc(K);
         std::vector<void* const*> rsc(K);
@@ -368,14 +404,14 @@ public:
         for (size_t k = 0; k < K; ++k) {
             mixed_leg const& l = legs[k];
             if (!l.req || !l.resp || !l.resp_prefix ||
-                (recs ? (l.calls && (!l.d_req_recs || !l.d_resp_recs)) || l.proto.size() != l.resp_stride
-                      : !l.d_req_cols || !l.d_resp_cols) ||
+                (l.records ? (l.calls && (!l.d_req_recs || !l.d_resp_recs)) || l.proto.size() != l.resp_stride
+                           : !l.d_req_cols || !l.d_resp_cols) ||
                 (l.req_var && !l.d_req_str_offs) || (l.resp_var && (!l.d_resp_str_offs || !l.resp_cap || !l.resp_leaf)))
-                throw plan_error("batch_client::call_mixed (leg)", SRPC_E_INVALID);
+                throw error(" (leg)", SRPC_E_INVALID);
             qrec[k] = l.d_req_recs;
             srec[k] = l.d_resp_recs;
-            qstride[k] = l.req_stride;
-            sstride[k] = l.resp_stride;
+            qstride[k] = l.records ? l.req_stride : 0;  // call_legs: 0 names a column leg
+            sstride[k] = l.records ? l.resp_stride : 0;
             qoff[k] = l.req_offs.data();
             soff[k] = l.resp_offs.data();
             fill[k] = l.proto.data();
@@ -407,10 +443,10 @@ public:
         }
         const int nk = static_cast<int>(K);
         // staging by the largest frame of each side
-        if (any_var) ensure_bytes(_max * fin + 4096, _max * fout + 4096);
+        if (any_str) ensure_bytes(_max * fin + 4096, _max * fout + 4096);
         else ensure(fin, fout);
         ensure_mixed();
-        if (any_var) ensure_mixed_var(rq.data(), rs.data(), nk);
+        if (any_var) ensure_mixed_var(rq.data(), rs.data(), nk, any_kinds ? qstride.data() : nullptr, sstride.data());
         if (recs) {  // the decode's tables and fills
             uint64_t b = 0;
             check_srpc(srpc_frames_mixed_aos_scratch_bytes(rs.data(), nk, sstride.data(), &b),
@@ -430,7 +466,13 @@ public:
                                                stream),
                        "srpc_frames_mixed_index");
             // the pack runs even after the peer closed: its status says whether the chunk is well formed
-            if (any_var)
+            if (any_kinds)
+                check_srpc(srpc_frames_pack_requests_mixed_legs(rq.data(), nk, rqc.data(), rqo.data(), qrec.data(),
+                                                                qstride.data(), qoff.data(), first.data(), cap.data(),
+                                                                d_method + lo, _s.d_mindex, m, _s.d_out, out_cap, _s.d_moffs,
+                                                                _s.d_mv, _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
+                           "srpc_frames_pack_requests_mixed_legs");
+            else if (any_var)
                 check_srpc(srpc_frames_pack_requests_mixed_var(rq.data(), nk, rqc.data(), rqo.data(), first.data(), cap.data(),
                                                                d_method + lo, _s.d_mindex, m, _s.d_out, out_cap, _s.d_moffs,
                                                                _s.d_mv, _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
@@ -456,15 +498,15 @@ public:
             for (size_t k = 0; any_var && k < K; ++k) fits = fits && h_counts[k] <= cap[k] - std::min(cap[k], first[k]);
             if (!fits) {
                 _last = st;
-                throw plan_error("batch_client::call_mixed (d_method does not match the legs)", SRPC_E_INVALID);
+                throw error(" (d_method does not match the legs)", SRPC_E_INVALID);
             }
             if (any_var && _s.h_mv[0] > out_cap) {
                 _last = st;
-                throw plan_error("batch_client::call_mixed (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
+                throw error(" (requests outgrow max_request_bytes)", SRPC_E_CAPACITY);
             }
             if (any_var && _s.h_status->flags) {
                 _last = st;
-                throw plan_error("batch_client::call_mixed (a request string's offsets decrease)", SRPC_E_INVALID);
+                throw error(" (a request string's offsets decrease)", SRPC_E_INVALID);
             }
             const uint64_t packed =
                 any_var ? _s.h_mv[0] : *reinterpret_cast<const uint32_t*>(h_counts + SRPC_FRAMES_MAX_PLANS + 1);
@@ -483,7 +525,14 @@ public:
                 check(hipMemcpyAsync(_s.d_offs, _s.h_offs, 4 * nf, hipMemcpyHostToDevice, stream));
             }
             // calls without a reply get RPC_ERR_RECV_TIMEOUT, zero fields and empty strings from the decode itself
-            if (any_var)
+            if (any_kinds)
+                check_srpc(srpc_frames_unpack_replies_mixed_legs(
+                               rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo, _s.d_mindex, m,
+                               static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT), rsc.data(), rso.data(), scapp.data(), srec.data(),
+                               sstride.data(), soff.data(), fill.data(), first.data(), cap.data(), d_codes + lo, _s.d_mv + 1,
+                               _s.d_status, _s.d_vscratch, _s.vscratch_cap, stream),
+                           "srpc_frames_unpack_replies_mixed_legs");
+            else if (any_var)
                 check_srpc(srpc_frames_unpack_replies_mixed_var(rs.data(), nk, _s.d_in, w.walked, _s.d_offs, nf, d_method + lo,
                                                                 _s.d_mindex, m, static_cast<uint8_t>(RPC_ERR_RECV_TIMEOUT),
                                                                 rsc.data(), rso.data(), scapp.data(), first.data(), cap.data(),
@@ -529,10 +578,10 @@ public:
             for (size_t s = 0; s < nslots; ++s)
                 if (_s.h_mv[1 + s] > slot_cap[s]) {
                     _last = st;
-                    throw plan_error("batch_client::call_mixed (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
+                    throw error(" (reply chars outgrow resp_cap)", SRPC_E_CAPACITY);
                 }
         }
-        if (!n && any_var) {  // no chunk ran: the offsets of no calls
+        if (!n && any_str) {  // no chunk ran: the offsets of no calls
             for (size_t k = 0; k < K; ++k)
                 for (size_t f = 0; legs[k].resp_var && f < legs[k].resp_leaf->size(); ++f)
                     if ((*legs[k].resp_leaf)[f] == 0) check(hipMemsetAsync(legs[k].d_resp_str_offs[f], 0, 8, stream));
@@ -541,11 +590,10 @@ public:
         _last = st;
         for (size_t k = 0; k < K; ++k)
             if (first[k] != legs[k].calls)
-                throw plan_error("batch_client::call_mixed (a leg declares more calls than d_method holds)", SRPC_E_INVALID);
+                throw error(" (a leg declares more calls than d_method holds)", SRPC_E_INVALID);
         return st;
     }
 
-private:
     using clock = std::chrono::steady_clock;
 
     /// A method's plans and leaf sizes, whichever form calls it: a side with
@@ -958,10 +1006,16 @@ private:
     /// The string form's staging beside ensure_mixed's: the scratch of both
     /// calls and, device and pinned, the chunk's request bytes followed by the
     /// end offset of every reply string slot.
-    void ensure_mixed_var(const srpc_plan* const* rq, const srpc_plan* const* rs, int nk) {
+    void ensure_mixed_var(const srpc_plan* const* rq, const srpc_plan* const* rs, int nk, const uint64_t* qstride,
+                          const uint64_t* sstride) {
         uint64_t a = 0, b = 0;
-        check_srpc(srpc_frames_mixed_var_scratch_bytes(rq, nk, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
-        check_srpc(srpc_frames_mixed_var_scratch_bytes(rs, nk, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
+        if (qstride) {  // call_legs: the record legs' tables and fills behind the same layout
+            check_srpc(srpc_frames_mixed_legs_scratch_bytes(rq, nk, qstride, _max, &a), "srpc_frames_mixed_legs_scratch_bytes");
+            check_srpc(srpc_frames_mixed_legs_scratch_bytes(rs, nk, sstride, _max, &b), "srpc_frames_mixed_legs_scratch_bytes");
+        } else {
+            check_srpc(srpc_frames_mixed_var_scratch_bytes(rq, nk, _max, &a), "srpc_frames_mixed_var_scratch_bytes");
+            check_srpc(srpc_frames_mixed_var_scratch_bytes(rs, nk, _max, &b), "srpc_frames_mixed_var_scratch_bytes");
+        }
         ensure_vscratch(std::max(a, b));
         if (!_s.d_mv) {
             _s.d_mv.alloc(8 * (1 + SRPC_FRAMES_MIXED_MAX_FIELDS));

@@ -1087,6 +1087,120 @@ int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, in
                                          uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
                                          uint64_t scratch_bytes, void* stream);
 
+/* ---- batches of calls of several methods in call order, each plan's calls in
+ * columns or in a struct array (client side; added within ABI 8) ----------------
+ * srpc_frames_pack_requests_mixed_var and srpc_frames_unpack_replies_mixed_var
+ * with, per plan, the choice srpc_frames_*_mixed_aos offers for all plans at
+ * once: one device array of the caller's own structs in place of the plan's
+ * columns.  The arguments are the _mixed_var calls' plus the struct-array
+ * arrays of the _mixed_aos calls (d_recs, h_stride, h_leaf_offs; h_fill on the
+ * decode), all host arrays of K entries.  The contract is the union of the two
+ * sections above, per plan, and nothing new.
+ *
+ * Plan k is a RECORD plan exactly when h_stride[k] != 0.  It must be a
+ * fixed-size plan with a framed prefix; its calls live in d_recs[k] as the
+ * section "from struct arrays" states (16-byte aligned array, h_stride[k] bytes
+ * a struct, leaf f at byte h_leaf_offs[k][f], natural alignment, no two leaves
+ * sharing a byte, none past the stride; call i's struct is element h_first[k] +
+ * rank(i), h_cap[k] the elements the array has).  Its d_cols[k], d_str_offs[k]
+ * and h_str_cap[k] are not read and may be NULL.
+ * Every other plan is a COLUMN plan, fixed-size or string, exactly as the
+ * _mixed_var calls take it; its d_recs[k], h_leaf_offs[k] and h_fill[k] are not
+ * read.  Any combination of kinds in any plan order is one valid call, all of
+ * one kind included.  K, d_method, rank(i), BAD calls and the index of
+ * srpc_frames_mixed_index are unchanged.
+ *
+ * srpc_frames_pack_requests_mixed_legs: the output bytes, d_offs, *d_total, the
+ * status, the handling of BAD calls and the out_cap rule are
+ * srpc_frames_pack_requests_mixed_var's on the same values: the frames lie back
+ * to back in call order, each byte-identical to `BE32 | pack_request` of the
+ * scalar packer, whichever form its plan's fields live in.  Of a record plan
+ * only leaf bytes of the chunk's own structs are read; h_stride[k] is any value
+ * below 2^32.  Given the RESPONSE plans, d_method = d_class and the index a
+ * request decode wrote, it is a server's ordered reply pack, as the calls above.
+ *
+ * srpc_frames_unpack_replies_mixed_legs: d_codes, the flags, first_bad_record,
+ * d_ends, the string offsets and unanswered_code are
+ * srpc_frames_unpack_replies_mixed_var's on the same input (string slots are
+ * numbered over the string plans as there), and a column plan's columns are
+ * written as that call writes them.  A record plan's structs follow
+ * srpc_frames_unpack_replies_mixed_aos: h_fill[k] is h_stride[k] <= 256 host
+ * bytes, copied during the call; every struct of the chunk's calls that is not
+ * BAD is written whole, exactly once, and never read -- leaf bytes from a full
+ * frame, zero for any other frame and for calls nframes <= i < ncalls, every
+ * other byte from h_fill[k]; no byte outside the plan's elements of this chunk
+ * is written and nothing is written for a BAD call.
+ *
+ * Scratch: srpc_frames_mixed_legs_scratch_bytes(plans of that call, h_stride,
+ * ncalls), 16-byte aligned: the _mixed_var layout, then the record plans'
+ * per-struct-byte source tables and fills (3 S16 + 16 bytes per record plan,
+ * S16 = h_stride[k] rounded up to 16), which the decode writes there by
+ * by-value launches: no host copy outlives the call.  A stride above 256, which
+ * only a pack takes, counts no table; h_stride == NULL sizes a call without
+ * record plans.
+ *
+ * Both calls are stream-ordered, allocate nothing, wait on nothing on the host
+ * or the device and can be captured.  Their launches are the _mixed_var calls'
+ * (the decode's: plus one per 2 KiB of tables and fills) and depend on neither
+ * the data nor the order of the plans; work is bounded by the bytes plus ncalls
+ * * the largest fixed part, on any input.
+ *
+ * Tile rule.  A workgroup of the pack takes srpc_frames_mixed_var_tile's calls
+ * and image window.  A workgroup of the decode takes
+ * srpc_frames_mixed_legs_tile's: the record plans' tables and fills lie in the
+ * tail of the 32 KiB image, so the image window is 32 KiB minus their bytes and
+ * the calls per tile are 256, or the power of two >= 16 whose frames without
+ * their chars fit that window.  The workgroup's dynamic LDS is that of the
+ * _mixed_var decode, whatever the record plans.  Without record plans both are
+ * srpc_frames_mixed_var_tile's values, and both calls launch the _mixed_var
+ * calls' own kernels.  The decode stages and judges as the
+ * _mixed_var kernel; a lane of a column plan stores its fields and string
+ * lengths, a lane of a record plan leaves where its leaves are, and the
+ * workgroup then writes the record plans' slices of the tile as whole 16-byte
+ * pieces, as the _mixed_aos kernel does (a full frame that a long string pushed
+ * out of the window is read from d_buf).
+ *
+ * Refused with nothing launched, in this order:
+ *   1. SRPC_E_INVALID (before any plan is read): the _mixed_var calls' NULL and
+ *      range checks with d_recs, h_stride, h_leaf_offs (decode: h_fill) among
+ *      the pointers; h_stride[k] >= 2^32; for a record plan a NULL
+ *      h_leaf_offs[k] (decode: h_fill[k]), or a NULL d_recs[k] where h_cap[k]
+ *      leaves an element;
+ *   2. SRPC_E_UNSUPPORTED: what the _mixed_var calls refuse so; a string plan
+ *      with a non-zero stride; a decode stride above 256;
+ *   3. SRPC_E_INVALID: a record plan's leaves overlapping or past the stride;
+ *   4. SRPC_E_ALIGN: d_buf, d_out, an array, d_scratch (16), the index, d_total,
+ *      d_ends (8), d_offs (4), an offset or stride against its leaf's size; then
+ *      the column plans' pointers as the _mixed_var calls check them (a NULL
+ *      one: SRPC_E_INVALID);
+ *   5. SRPC_E_CAPACITY: scratch_bytes. */
+int srpc_frames_mixed_legs_scratch_bytes(const srpc_plan* const* plans, int nplans,
+                                         const uint64_t* h_stride /* may be NULL */, uint64_t ncalls,
+                                         uint64_t* out);
+/* Testing hook: calls per workgroup tile of a decode with these plans and the
+ * bytes of its LDS image window (h_stride may be NULL: no record plan). */
+int srpc_frames_mixed_legs_tile(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
+                                uint32_t* calls_per_tile, uint32_t* image_bytes);
+int srpc_frames_pack_requests_mixed_legs(const srpc_plan* const* req_plans, int nplans,
+                                         const void* const* const* d_cols,
+                                         const uint64_t* const* const* d_str_offs, const void* const* d_recs,
+                                         const uint64_t* h_stride, const uint32_t* const* h_leaf_offs,
+                                         const uint64_t* h_first, const uint64_t* h_cap, const uint8_t* d_method,
+                                         const void* d_index, uint64_t ncalls, uint8_t* d_out, uint64_t out_cap,
+                                         uint32_t* d_offs /* ncalls + 1 */, uint64_t* d_total,
+                                         srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
+                                         void* stream);
+int srpc_frames_unpack_replies_mixed_legs(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
+                                          uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                          const uint8_t* d_method, const void* d_index, uint64_t ncalls,
+                                          uint8_t unanswered_code, void* const* const* d_cols,
+                                          uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap,
+                                          void* const* d_recs, const uint64_t* h_stride,
+                                          const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+                                          const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
+                                          uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
+                                          uint64_t scratch_bytes, void* stream);
+
 /* ---- batches of request frames of several methods with string bodies, in
  * arrival order (server side; added within ABI 8) --------------------------------
  * srpc_frames_unpack_requests_mixed with string plans allowed beside the

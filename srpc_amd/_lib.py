@@ -118,6 +118,13 @@ SIGNATURES = {
                                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "srpc_frames_unpack_requests_mixed_var": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
                                                         _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "srpc_frames_mixed_legs_scratch_bytes": (C.c_int, [_vp, C.c_int, _vp, _u64, C.POINTER(_u64)]),
+    "srpc_frames_mixed_legs_tile": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "srpc_frames_pack_requests_mixed_legs": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64,
+                                                       _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "srpc_frames_unpack_replies_mixed_legs": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _u64, C.c_uint8,
+                                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                        _vp, _u64, _vp]),
     "srpc_status_string": (C.c_char_p, [C.c_int]),
     "srpc_gpu_abi_version": (C.c_int, []),
 }

@@ -118,17 +118,6 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
     mix_aos_store<true>(sl, d, K, r, good, j, img, lo, pos, slot, dsc, buf);
 }
 
-// Every leaf inside the stride and no two sharing a byte (any stride below 2^32).
-int aos_leaves_ok(const srpc_plan* p, const uint32_t* offs, uint64_t stride) {
-    for (uint32_t f = 0; f < p->nfields; ++f) {
-        if (offs[f] + static_cast<uint64_t>(p->size[f]) > stride) return SRPC_E_INVALID;
-        for (uint32_t g = 0; g < f; ++g)
-            if (offs[f] < offs[g] + static_cast<uint64_t>(p->size[g]) && offs[g] < offs[f] + static_cast<uint64_t>(p->size[f]))
-                return SRPC_E_INVALID;
-    }
-    return SRPC_OK;
-}
-
 __global__ void k_mixed_aos_reset_status(srpc_unpack_status* st) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         st->flags = 0;

@@ -48,6 +48,17 @@ inline bool aos_args_invalid(const void* const* d_recs, const uint64_t* h_stride
     return false;
 }
 
+// Every leaf inside the stride and no two sharing a byte (any stride below 2^32).
+inline int aos_leaves_ok(const srpc_plan* p, const uint32_t* offs, uint64_t stride) {
+    for (uint32_t f = 0; f < p->nfields; ++f) {
+        if (offs[f] + static_cast<uint64_t>(p->size[f]) > stride) return SRPC_E_INVALID;
+        for (uint32_t g = 0; g < f; ++g)
+            if (offs[f] < offs[g] + static_cast<uint64_t>(p->size[g]) && offs[g] < offs[f] + static_cast<uint64_t>(p->size[f]))
+                return SRPC_E_INVALID;
+    }
+    return SRPC_OK;
+}
+
 // Each leaf's address inside element 0 of its plan's array, as mix_args's columns.
 struct AosCols {
     const void* leaf[kMixFields];
@@ -149,9 +160,10 @@ __device__ __forceinline__ void mix_aos_slices_count(MixAosSlices& s, uint32_t K
 // and stored whole, non-temporally when NT.  A slice starts and ends at any
 // byte: its first and last piece, where they are shared with a neighbouring
 // tile's slice (or lie at the array's edge), are stored bytewise, own bytes
-// only.  dsc: the K tables and fills in LDS.
-template <bool NT>
-__device__ __forceinline__ void mix_aos_store(MixAosSlices& s, const MixLds& d, uint32_t K, const MixLane& r, bool good,
+// only.  dsc: the K tables and fills in LDS.  d: the kernel's plan lookups
+// (MixLds, or MvDesc in mixed_var_tile.h), of which first[] is read.
+template <bool NT, class D>
+__device__ __forceinline__ void mix_aos_store(MixAosSlices& s, const D& d, uint32_t K, const MixLane& r, bool good,
                                               uint32_t j, const uint8_t* img, const uint32_t* lo, const uint32_t* pos,
                                               uint16_t* slot, const uint8_t* dsc, const uint8_t* __restrict__ buf) {
     if (threadIdx.x <= K) {

@@ -91,16 +91,35 @@ inline size_t mv_lds(const MvDesc& d) { return kMixImage + 16 + d.tmpl_bytes + 1
 // The plans of one side into d's layout part.  min_fixed_prefix: 4 (request) or
 // 5 (reply).
 int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefix, MvDesc* d);
-// Columns, offsets arrays and rooms.
+// Columns, offsets arrays and rooms.  A plan with h_stride[k] != 0 (h_stride
+// may be nullptr) gets its first and room only: its d_cols[k], d_str_offs[k]
+// and h_str_cap[k] are not read and its leaves' entries are left to the caller
+// (mixed_legs.hip: a record plan).
 int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
             const uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap, const uint64_t* h_first,
-            const uint64_t* h_cap, MvDesc* d);
+            const uint64_t* h_cap, MvDesc* d, const uint64_t* h_stride = nullptr);
 // d -> the head of d_scratch, in kMvChunks launches.
 int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s);
 // Any description (bytes: a multiple of 16) -> the head of d_scratch (16-byte
 // aligned), kMvChunk bytes per launch, each chunk a by-value kernel argument:
 // no host copy outlives the call (also mixed_aos.hip's tables and fills).
 int mix_upload(const void* src, size_t bytes, void* d_scratch, hipStream_t s);
+// The pack's first two launches: every granule's frame bytes, then their scan
+// (gsum: rows + 1 u64 of scratch; the total to *d_total, d_offs[ncalls]).
+void mv_sizes_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
+                     uint64_t* gsum, uint64_t out_cap, uint32_t* d_offs, uint64_t* d_total, hipStream_t s);
+// The two tile kernels over plans that all live in columns (k_mv_pack,
+// k_mv_parse: d.T calls a workgroup), ncalls > 0.  mixed_legs.hip launches them
+// too, for a batch without a record plan.
+void mv_pack_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows,
+                    uint64_t ncalls, const uint64_t* gsum, uint8_t* d_out, uint64_t out_cap, uint32_t* d_offs,
+                    srpc_unpack_status* d_status, hipStream_t s);
+void mv_parse_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows,
+                     uint64_t ncalls, const uint8_t* d_buf, uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                     uint32_t unanswered, uint8_t* d_codes, uint32_t* srcs, uint32_t* counts, srpc_unpack_status* d_status,
+                     hipStream_t s);
+// *d_status = no flag, no bad record.
+void mv_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
 // The segmented scan over all string slots (three launches whatever K): the
 // lengths the parse left in the offsets arrays become offsets, d_ends[s] each
 // slot's end.  counts: the chunk's calls per plan (device, u32).

@@ -15,7 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 from dataclasses import dataclass, field
-from typing import Iterable, Sequence
+from typing import Iterable, Optional, Sequence
 
 from . import _lib
 from ._lib import SrpcError, check
@@ -725,7 +725,72 @@ class MixedVarFrames:
                                                                 scratch_bytes, _stream(stream))
 
 
+class MixedLegFrames(MixedVarFrames):
+    """``MixedVarFrames.pack`` / ``unpack`` with, per plan, the choice between
+    columns and one device array of the caller's structs
+    (srpc_frames_pack_requests_mixed_legs / _unpack_replies_mixed_legs; the
+    index is ``MixedFrames.index``).  ``strides[k]``: plan k's struct bytes, or 0
+    for a plan held in columns (fixed-size or string); ``leaf_offsets[k][f]``:
+    the byte offset of leaf f in the struct (None for a column plan).
+    ``cols[k]`` / ``str_offs[k]`` / ``str_cap[k]`` are ``MixedVarFrames``'s and
+    may be None for a record plan; ``recs[k]`` / ``fills[k]`` are
+    ``MixedAosFrames``'s and may be None for a column plan.  Every call returns
+    the C status (negative: refused, nothing launched)."""
+
+    def __init__(self, plans: Sequence["GpuPacker"], strides: Sequence[int],
+                 leaf_offsets: Sequence[Optional[Sequence[int]]]):
+        super().__init__(plans)
+        self.strides = [int(s) for s in strides]
+        self._strides = (C.c_uint64 * self.k)(*self.strides)
+        self._keep_offs = [None if o is None else (C.c_uint32 * max(1, len(o)))(*[int(x) for x in o])
+                           for o in leaf_offsets]
+        self._offs = (C.c_void_p * self.k)(*[None if a is None else C.cast(a, C.c_void_p).value
+                                             for a in self._keep_offs])
+
+    def scratch_bytes(self, ncalls: int) -> int:
+        out = C.c_uint64()
+        check(_lib.lib().srpc_frames_mixed_legs_scratch_bytes(self._plans, self.k, self._strides, ncalls,
+                                                              C.byref(out)), "srpc_frames_mixed_legs_scratch_bytes")
+        return out.value
+
+    @property
+    def tile(self) -> tuple[int, int]:
+        """(calls per workgroup tile of ``unpack``, bytes of its LDS image window);
+        ``pack`` tiles as ``MixedVarFrames.tile``."""
+        t, img = C.c_uint32(), C.c_uint32()
+        check(_lib.lib().srpc_frames_mixed_legs_tile(self._plans, self.k, self._strides, C.byref(t), C.byref(img)),
+              "srpc_frames_mixed_legs_tile")
+        return t.value, img.value
+
+    def _recs(self, recs):
+        return (C.c_void_p * self.k)(*[None if r is None else _dptr(r) for r in recs])
+
+    def pack(self, cols, str_offs, recs, first, cap, method, index, ncalls: int, out, out_cap: int, offs, total,
+             status, scratch, scratch_bytes: int, stream=None) -> int:
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        return _lib.lib().srpc_frames_pack_requests_mixed_legs(self._plans, self.k, c_arr, s_arr, self._recs(recs),
+                                                               self._strides, self._offs, h_first, h_cap,
+                                                               _dptr(method), _dptr(index), ncalls, _dptr(out), out_cap,
+                                                               _dptr(offs), _dptr(total), _dptr(status),
+                                                               _dptr(scratch), scratch_bytes, _stream(stream))
+
+    def unpack(self, buf, buf_len: int, offs, nframes: int, method, index, ncalls: int, unanswered: int, cols,
+               str_offs, str_cap, recs, fills, first, cap, codes, ends, status, scratch, scratch_bytes: int,
+               stream=None) -> int:
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        cap_arr, k3 = self._table(str_cap, lambda x: 0 if x is None else int(x), C.c_uint64)
+        keep = [None if f is None else C.create_string_buffer(bytes(f), max(1, len(bytes(f)))) for f in fills]
+        h_fill = (C.c_void_p * self.k)(*[None if b is None else C.cast(b, C.c_void_p).value for b in keep])
+        self._keep += (k3, keep)
+        return _lib.lib().srpc_frames_unpack_replies_mixed_legs(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                                nframes, _dptr(method), _dptr(index), ncalls,
+                                                                unanswered, c_arr, s_arr, cap_arr, self._recs(recs),
+                                                                self._strides, self._offs, h_fill, h_first, h_cap,
+                                                                _dptr(codes), _dptr(ends), _dptr(status),
+                                                                _dptr(scratch), scratch_bytes, _stream(stream))
+
+
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
            "fill_splitmix_i32", "time_next_call", "framed_request_prefix", "framed_response_prefix",
-           "FrameClassifier", "frame_var", "MixedFrames", "MixedVarFrames", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
+           "FrameClassifier", "frame_var", "MixedFrames", "MixedVarFrames", "MixedLegFrames", "BOOL", "INT8", "CHAR", "INT16", "INT32", "INT64", "STRING",
            "RPC_SUCCESS", "RPC_ERR_FUNCTION_NOT_REGISTERED", "RPC_ERR_RECV_TIMEOUT"]
