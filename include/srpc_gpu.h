@@ -243,7 +243,16 @@ int srpc_gpu_unpack_aos_fill(const srpc_plan* plan, const uint8_t* d_wire, uint6
  * Both calls need `scratch_bytes` of device scratch (8-byte aligned) from
  * srpc_plan_var_scratch_bytes(plan, n, wire_bytes), wire_bytes being the
  * pack call's wire_cap or the unpack call's wire_len; like the fixed calls
- * they are stream-ordered and allocate nothing. */
+ * they are stream-ordered and allocate nothing.
+ * The scratch contract, here and for every later call that takes d_scratch
+ * (the frame calls below included): what the scratch holds on entry is
+ * arbitrary -- uninitialised memory, or whatever another call, of any plan,
+ * kind or size, finished or failed, left in it -- and every call resets the
+ * words it reads before it reads them; a scratch larger than the size asked
+ * for is fine, and the bytes past that size are not touched; nothing in the
+ * scratch carries from one call to the next, so one buffer sized for the
+ * largest need may serve any sequence of calls on one stream
+ * (tests/test_gpu_scratch_reuse.py). */
 int srpc_plan_var_scratch_bytes(const srpc_plan* plan, uint64_t n, uint64_t wire_bytes,
                                 uint64_t* out);
 

@@ -232,11 +232,12 @@ def _rand_vals(schema, rng, maxlen):
     return out
 
 
-def _mixed_var_frames(n, rng, foreign_frac, maxlen=40):
-    """Fixed methods (METHODS), string methods (VAR_METHODS) and foreign frames
-    near the string ones: a string length past the frame, one trailing byte, a
-    BE32 that disagrees with the frame, a payload shorter than the fixed part,
-    a method name of the same length.  Returns (buf, offs, classes, values)."""
+def _mixed_var_frames(n, rng, foreign_frac, maxlen=40, var_frac=0.5):
+    """Fixed methods (METHODS), string methods (VAR_METHODS; var_frac of the
+    frames) and foreign frames near the string ones: a string length past the
+    frame, one trailing byte, a BE32 that disagrees with the frame, a payload
+    shorter than the fixed part, a method name of the same length.  Returns
+    (buf, offs, classes, values)."""
     pres = [framed_request_prefix(s, m) for s, m, _ in METHODS]
     K = len(METHODS)
     parts, cls, vals = [], [], []
@@ -263,7 +264,7 @@ def _mixed_var_frames(n, rng, foreign_frac, maxlen=40):
             parts.append(bytes(f))
             cls.append(UNKNOWN)
             vals.append(None)
-        elif u < foreign_frac + 0.5:
+        elif u < foreign_frac + var_frac:
             j = int(rng.integers(0, 2))
             s, m = VAR_METHODS[j]
             v = _rand_vals(s, rng, maxlen)

@@ -107,11 +107,15 @@ def _upload(cols, offs):
     return [dev(c) for c in cols], [dev(np.ascontiguousarray(o, np.uint64)) if o is not None else None for o in offs]
 
 
-def _pack_guarded(p, dcols, doffs, n, wire_bytes, wire_cap):
-    """pack_var into guarded wire / rec_offs slices.  Returns (Checked, status)."""
+def _pack_guarded(p, dcols, doffs, n, wire_bytes, wire_cap, scratch=None):
+    """pack_var into guarded wire / rec_offs slices (scratch: the caller's own,
+    at least var_scratch_bytes long, instead of a fresh one).  Returns
+    (Checked, status)."""
     g = Checked([wire_bytes, 8 * (n + 1)])
     sb = p.var_scratch_bytes(n, wire_cap)
-    scratch = empty(sb + 16)
+    if scratch is None:
+        scratch = empty(sb + 16)
+    assert scratch.numel() >= sb
     st = status_buf()
     p.pack_var(dcols, doffs, n, g.slices[0], wire_cap, g.slices[1], scratch, sb, st)
     return g, read_status(st)
@@ -191,9 +195,10 @@ IMAGE_BYTES = [8192, 8208, 32768, 65536]
 CHARS_BYTES = [0, 16, 4096, 65536]
 
 
-def _unpack_guarded(p, kinds, dwire, wire_len, n, drec, table=None):
-    """unpack_var (or _tiled) into guarded columns and offsets.  Returns
-    (cols, offs, status) as host arrays, string chars cut to their length."""
+def _unpack_guarded(p, kinds, dwire, wire_len, n, drec, table=None, scratch=None):
+    """unpack_var (or _tiled) into guarded columns and offsets (scratch: the
+    caller's own instead of a fresh one).  Returns (cols, offs, status) as host
+    arrays, string chars cut to their length."""
     sizes = []
     for k in kinds:
         sizes.append(wire_len if k == oracle.STRING else n * oracle.KIND_SIZE[k])
@@ -204,7 +209,9 @@ def _unpack_guarded(p, kinds, dwire, wire_len, n, drec, table=None):
     for j, f in enumerate(sidx):
         so[f] = g.slices[len(kinds) + j]
     sb = p.var_scratch_bytes(n, wire_len)
-    scratch = empty(sb + 16)
+    if scratch is None:
+        scratch = empty(sb + 16)
+    assert scratch.numel() >= sb
     st = status_buf()
     if table is None:
         p.unpack_var(dwire, wire_len, n, drec, outs, so, scratch, sb, st)

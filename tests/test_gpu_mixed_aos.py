@@ -247,9 +247,10 @@ def test_pack_out_cap_one_byte_short():
 # ---- decode -------------------------------------------------------------------------------------
 
 def run_unpack_aos(S, method, buf, buf_len, offs, nframes, first=None, cap=None, index=None, recs=None,
-                   scratch_bytes=None, stream=None):
+                   scratch_bytes=None, stream=None, scratch=None):
     """One decode on 0xA5-filled outputs (or into `recs`) -> (rc, codes, recs[k] as
-    (cap[k], stride) bytes, flags, first bad, the device arrays); guards checked."""
+    (cap[k], stride) bytes, flags, first bad, the device arrays); guards checked
+    (scratch: the caller's own, which may be larger, instead of a fresh one)."""
     R = S.R
     n = len(method)
     d_method, d_index = index or build_index(method, R.K)[:2]
@@ -260,7 +261,8 @@ def run_unpack_aos(S, method, buf, buf_len, offs, nframes, first=None, cap=None,
     d_recs = recs or [empty(cap[k] * S.stride[k] + 16) for k in range(R.K)]
     d_codes = empty(n + 16)
     sb = S.mf.scratch_bytes
-    d_scratch = empty(sb + 16)
+    d_scratch = empty(sb + 16) if scratch is None else scratch
+    behind = d_scratch[sb:].clone()
     st = status_buf()
     rc = S.mf.unpack(d_buf, buf_len, d_offs, nframes, d_method, d_index, n, TIMEOUT, d_recs, S.fill, first, cap,
                      d_codes, d_scratch, sb if scratch_bytes is None else scratch_bytes, st, stream=stream)
@@ -270,7 +272,7 @@ def run_unpack_aos(S, method, buf, buf_len, offs, nframes, first=None, cap=None,
         raw = host(d_recs[k], cap[k] * S.stride[k] + 16)
         assert (raw[cap[k] * S.stride[k]:] == 0xA5).all(), "wrote past an array"
         out.append(raw[:cap[k] * S.stride[k]].reshape(cap[k], S.stride[k]))
-    assert (host(d_codes, n + 16)[n:] == 0xA5).all() and (host(d_scratch, sb + 16)[sb:] == 0xA5).all()
+    assert (host(d_codes, n + 16)[n:] == 0xA5).all() and torch.equal(d_scratch[sb:], behind)
     return rc, host(d_codes, n), out, flags, bad, d_recs
 
 
@@ -302,13 +304,14 @@ def same_structs(got, exp):
         assert bad.size == 0, f"plan {k} struct {bad[0]}: {g[bad[0]].tolist()} != {e[bad[0]].tolist()}"
 
 
-def check(S, method, buf, buf_len, offs, nframes, first=None, cap=None, columns=True):
+def check(S, method, buf, buf_len, offs, nframes, first=None, cap=None, columns=True, scratch=None):
     """The AoS decode against `model` and numpy, and against the column call on the same bytes."""
     R = S.R
     n = len(method)
     first = first or [0] * R.K
     index = build_index(method, R.K)[:2]
-    rc, codes, recs, flags, bad, _ = run_unpack_aos(S, method, buf, buf_len, offs, nframes, first, cap, index)
+    rc, codes, recs, flags, bad, _ = run_unpack_aos(S, method, buf, buf_len, offs, nframes, first, cap, index,
+                                                    scratch=scratch)
     ncap = [len(r) for r in recs]
     want, full, wflags, wbad = model(buf, buf_len, offs, nframes, method, first, ncap, R)
     print(f"{R.name} n={n} nframes={nframes} rc={rc} flags={flags} first={bad} want flags={wflags} first={wbad}")

@@ -164,7 +164,7 @@ def dev_req(L, B):
     return cols, so, recs
 
 
-def run_pack_legs(L, B, method=None, out_cap=None, first=None, cap=None, args=None, want=None):
+def run_pack_legs(L, B, method=None, out_cap=None, first=None, cap=None, args=None, want=None, scratch=None):
     """As test_gpu_mixed_var.run_pack -> (rc, out bytes, d_offs, total, flags, first bad)."""
     method = B.method if method is None else method
     n = len(method)
@@ -176,7 +176,8 @@ def run_pack_legs(L, B, method=None, out_cap=None, first=None, cap=None, args=No
     d_offs = empty(4 * (n + 1) + 16)
     d_total = empty(8 + 16)
     sb = L.req.scratch_bytes(n)
-    d_scratch = empty(sb + 16)
+    d_scratch = empty(sb + 16) if scratch is None else scratch  # the caller's own may be larger
+    behind = d_scratch[sb:].clone()
     st = status_buf()
     st[8:] = 0xFF  # the pack does not reset the status: flags 0, no bad record
     rc = L.req.pack(cols, so, recs, first, cap or B.counts[:L.K], d_method, d_index, n, d_out, out_cap, d_offs, d_total,
@@ -185,7 +186,7 @@ def run_pack_legs(L, B, method=None, out_cap=None, first=None, cap=None, args=No
     raw = host(d_out, out_cap + 16)
     assert (raw[out_cap:] == 0xA5).all(), "wrote at or past out_cap"
     assert (host(d_offs, 4 * (n + 1) + 16)[-16:] == 0xA5).all() and (host(d_total, 24)[8:] == 0xA5).all()
-    assert (host(d_scratch, sb + 16)[sb:] == 0xA5).all(), "wrote past the scratch"
+    assert torch.equal(d_scratch[sb:], behind), "wrote past the scratch"
     return rc, raw[:out_cap], host(d_offs, 4 * (n + 1), np.uint32), int(host(d_total, 8, np.uint64)[0]), flags, bad
 
 
@@ -338,7 +339,7 @@ class LegOuts(Outs):
             self.cols[k] = self.offs[k] = self.scap[k] = None
 
 
-def run_unpack_legs(L, B, O, buf, buf_len, offs, nframes, lo=0, hi=None, first=None, stream=None):
+def run_unpack_legs(L, B, O, buf, buf_len, offs, nframes, lo=0, hi=None, first=None, stream=None, scratch=None):
     """One decode of calls [lo, hi) -> (rc, codes, ends, flags, first bad)."""
     method = B.method[lo:hi]
     n = len(method)
@@ -348,13 +349,14 @@ def run_unpack_legs(L, B, O, buf, buf_len, offs, nframes, lo=0, hi=None, first=N
     d_codes = empty(n + 16)
     d_ends = empty(8 * O.nslots + 16)
     sb = L.rep.scratch_bytes(n)
-    d_scratch = empty(sb + 16)
+    d_scratch = empty(sb + 16) if scratch is None else scratch  # the caller's own may be larger
+    behind = d_scratch[sb:].clone()
     st = status_buf()
     rc = L.rep.unpack(d_buf, buf_len, d_offs, nframes, d_method, d_index, n, TIMEOUT, O.cols, O.offs, O.scap, O.recs,
                       L.fill, first, O.cap, d_codes, d_ends, st, d_scratch, sb, stream=stream)
     flags, bad = read_status(st)
     assert (host(d_codes, n + 16)[n:] == 0xA5).all() and (host(d_ends, 8 * O.nslots + 16)[8 * O.nslots:] == 0xA5).all()
-    assert (host(d_scratch, sb + 16)[sb:] == 0xA5).all(), "wrote past the scratch"
+    assert torch.equal(d_scratch[sb:], behind), "wrote past the scratch"
     return rc, host(d_codes, n).copy(), host(d_ends, 8 * O.nslots, np.uint64).copy(), flags, bad
 
 
@@ -389,7 +391,7 @@ def check_legs(L, B, O, full, touched=None, ends=None, cap=None):
         assert bad.size == 0, f"plan {k} struct {bad[0]}: {got[bad[0]].tolist()} != {exp[bad[0]].tolist()}"
 
 
-def decode_and_check(L, B, parts, nframes=None, buf_len_cut=0, offs_edit=None, str_cap_cut=0):
+def decode_and_check(L, B, parts, nframes=None, buf_len_cut=0, offs_edit=None, str_cap_cut=0, scratch=None):
     nframes = B.n if nframes is None else nframes
     buf, offs = joined(parts[:nframes])
     offs = offs[:nframes].copy()
@@ -397,7 +399,7 @@ def decode_and_check(L, B, parts, nframes=None, buf_len_cut=0, offs_edit=None, s
         offs_edit(offs)
     buf_len = len(buf) - buf_len_cut
     O = LegOuts(L, B, str_cap_cut)
-    rc, codes, ends, flags, bad = run_unpack_legs(L, B, O, buf, buf_len, offs, nframes)
+    rc, codes, ends, flags, bad = run_unpack_legs(L, B, O, buf, buf_len, offs, nframes, scratch=scratch)
     wc, full, wflags, wbad = model(buf, buf_len, offs, nframes, B, [0] * B.P.K, O.cap)
     print(f"n={B.n} nframes={nframes} rc={rc} flags={flags} first={bad} want flags={wflags} first={wbad}")
     assert rc == 0

@@ -423,10 +423,18 @@ def test_pack_in_two_chunks(name):
 
 
 def test_pack_dirty_scratch_same_output():
+    """The scratch another batch left behind (more calls, another method mix,
+    another length regime: a stale word equal to the right one would hide a
+    missing reset), then the same batch twice."""
     B = batch("calc_echo", 1000, "uniform", "mid")
-    sb = B.P.req.scratch_bytes(B.n)
+    A = batch("calc_echo", 1537, "skew99", "short")
+    assert A.n != B.n and A.counts != B.counts
+    sb = max(B.P.req.scratch_bytes(B.n), A.P.req.scratch_bytes(A.n))
     scratch = empty(sb + 16)
+    check_pack(A, run_pack(A, scratch=scratch))
+    assert (host(scratch, B.P.req.scratch_bytes(B.n)) != 0xA5).any(), "the first batch left the scratch untouched"
     a = run_pack(B, scratch=scratch)
+    check_pack(B, a)
     b = run_pack(B, scratch=scratch)
     check_pack(B, b)
     assert a[1].tobytes() == b[1].tobytes() and np.array_equal(a[2], b[2])
@@ -593,7 +601,7 @@ def check_outs(B, O, full, touched=None, ends=None, skip=()):
                 assert np.array_equal(raw[:O.cap[k] * sz].view(dt), want), (k, f)
 
 
-def decode_and_check(B, parts, nframes=None, buf_len_cut=0, offs_edit=None, str_cap_cut=0):
+def decode_and_check(B, parts, nframes=None, buf_len_cut=0, offs_edit=None, str_cap_cut=0, scratch=None):
     nframes = B.n if nframes is None else nframes
     buf, offs = joined(parts[:nframes])
     offs = offs[:nframes].copy()
@@ -601,7 +609,7 @@ def decode_and_check(B, parts, nframes=None, buf_len_cut=0, offs_edit=None, str_
         offs_edit(offs)
     buf_len = len(buf) - buf_len_cut
     O = Outs(B, str_cap_cut)
-    rc, codes, ends, flags, bad = run_unpack(B, O, buf, buf_len, offs, nframes)
+    rc, codes, ends, flags, bad = run_unpack(B, O, buf, buf_len, offs, nframes, scratch=scratch)
     wc, full, wflags, wbad = model(buf, buf_len, offs, nframes, B, [0] * B.P.K, O.cap)
     assert rc == 0
     assert np.array_equal(codes[:nframes], wc) and (codes[nframes:] == TIMEOUT).all()
@@ -779,9 +787,14 @@ def test_decode_in_two_chunks_and_dirty_scratch(name):
     B = batch(name, 1000, "uniform", "mid")
     codes = np.random.default_rng(3).integers(0, 3, B.n)
     parts = B.rep_frames(codes)
+    # the scratch starts as another batch's decode left it: more calls, another mix and length regime
+    A = batch(name, 1537, "skew99", "short")
+    assert A.n != B.n and A.counts != B.counts
     for a in (1, 256, 999):
         O = Outs(B)
-        scratch = empty(B.P.rep.scratch_bytes(B.n) + 16)
+        scratch = empty(max(B.P.rep.scratch_bytes(B.n), A.P.rep.scratch_bytes(A.n)) + 16)
+        decode_and_check(A, A.rep_frames(np.random.default_rng(a).integers(0, 3, A.n)), scratch=scratch)
+        assert (host(scratch, B.P.rep.scratch_bytes(B.n)) != 0xA5).any(), "the first batch left the scratch untouched"
         buf, offs = joined(parts[:a])
         rc, c1, _, flags, _ = run_unpack(B, O, buf, len(buf), offs[:-1], a, lo=0, hi=a, scratch=scratch)
         assert rc == 0 and flags == 0

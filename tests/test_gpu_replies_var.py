@@ -184,9 +184,10 @@ def model(buf, buf_len, offs, n, prefix, kinds):
     return codes, full, flags, first
 
 
-def run(p, buf, buf_len, offs, n, tail=b"", stream_=None, call=True):
+def run(p, buf, buf_len, offs, n, tail=b"", stream_=None, call=True, scratch=None):
     """One call on fresh 0xA5-filled outputs -> (codes, cols, str offs, flags, first);
-    the frames' allocation holds `tail` after buf_len."""
+    the frames' allocation holds `tail` after buf_len (scratch: the caller's own,
+    which may be larger than the call needs, instead of a fresh one)."""
     kinds = p.schema.kinds
     d_buf = dev(np.frombuffer(buf + tail, np.uint8)) if buf or tail else empty(16)
     d_offs = dev(offs) if n else empty(16)
@@ -200,11 +201,13 @@ def run(p, buf, buf_len, offs, n, tail=b"", stream_=None, call=True):
             d_so.append(None)
     d_codes = empty(n + 16)
     sb = p.replies_var_scratch_bytes(n)
-    scratch = empty(sb)
+    scratch = empty(sb) if scratch is None else scratch
+    behind = scratch[sb:].clone()
     st = status_buf()
     args = (d_buf, buf_len, d_offs, n, d_cols, d_so, d_codes, scratch, sb, st)
     if call:
         p.unpack_replies_var(*args)
+        assert torch.equal(scratch[sb:], behind), "wrote past the scratch"
     else:
         return args
 
@@ -252,14 +255,14 @@ def check(name, n, lens, got, want_codes, full, want_flags, want_first):
     assert (flags, first) == (want_flags, want_first)
 
 
-def decode_and_check(name, n, lens, codes, special=None, buf_len_cut=0, offs_edit=None):
+def decode_and_check(name, n, lens, codes, special=None, buf_len_cut=0, offs_edit=None, scratch=None):
     p = packer(name, code=2)  # the plan's own code byte is ignored
     buf, offs = stream(name, n, lens, codes, special)
     if offs_edit:
         offs_edit(offs)
     buf_len = len(buf) - buf_len_cut
     want = model(buf, buf_len, offs, n, p.prefix, p.schema.kinds)
-    got = run(p, buf, buf_len, offs, n)
+    got = run(p, buf, buf_len, offs, n, scratch=scratch)
     check(name, n, lens, got, *want)
     return want
 

@@ -106,8 +106,9 @@ def test_tile_rule():
     assert lay_for("big", "natural").T == 64 and lay_for("calc", "natural").T == 256
 
 
-def run(L, buf, buf_len, offs, first, cap, alloc, status=True, recs=None):
-    """One decode on 0xA5-filled outputs (or into `recs`) -> everything it wrote; guards checked."""
+def run(L, buf, buf_len, offs, first, cap, alloc, status=True, recs=None, scratch=None):
+    """One decode on 0xA5-filled outputs (or into `recs`) -> everything it wrote; guards checked
+    (scratch: the caller's own, which may be larger, instead of a fresh one)."""
     S = L.S
     n, K = len(offs), S.K
     d_buf = dev(buf[:buf_len]) if buf_len else empty(16)  # the stream ends with its allocation
@@ -116,7 +117,8 @@ def run(L, buf, buf_len, offs, first, cap, alloc, status=True, recs=None):
     nb = MixedFrames.index_bytes(n, K)
     d_cls, d_index, d_counts = empty(n + GUARD), empty(nb + GUARD), empty(8 * (K + 1) + GUARD)
     sb = L.mf.scratch_bytes
-    d_scratch = empty(sb + GUARD)
+    d_scratch = empty(sb + GUARD) if scratch is None else scratch
+    behind = d_scratch[sb:].clone()
     st = status_buf()
     st[:] = 0x5A  # the call resets it
     rc = L.mf.unpack_requests(d_buf, buf_len, d_offs, n, d_recs, L.fill, first, cap, d_cls, d_index, nb, d_counts,
@@ -127,7 +129,7 @@ def run(L, buf, buf_len, offs, first, cap, alloc, status=True, recs=None):
     raw_index = host(d_index, nb + GUARD)
     raw_counts = host(d_counts, 8 * (K + 1) + GUARD)
     assert (raw_cls[n:] == 0xA5).all() and (raw_index[nb:] == 0xA5).all() and (raw_counts[-GUARD:] == 0xA5).all()
-    assert (host(d_scratch, sb + GUARD)[sb:] == 0xA5).all()
+    assert torch.equal(d_scratch[sb:], behind)
     out = []
     for k in range(K):
         raw = host(d_recs[k], alloc[k] * L.stride[k] + GUARD)
@@ -166,7 +168,7 @@ def same_structs(got, exp):
         assert bad.size == 0, f"plan {k} struct {bad[0]}: {g[bad[0]].tolist()} != {e[bad[0]].tolist()}"
 
 
-def check(L, buf, buf_len, offs, intent, elem, first=None, cap=None, alloc=None, others=True):
+def check(L, buf, buf_len, offs, intent, elem, first=None, cap=None, alloc=None, others=True, scratch=None):
     """Run the call and compare everything it wrote with the host's expectation,
     with srpc_frames_classify's classes and with the column call's classes,
     index, counts and status.  cap defaults to the elements the frames need,
@@ -179,7 +181,7 @@ def check(L, buf, buf_len, offs, intent, elem, first=None, cap=None, alloc=None,
     f0 = [0] * K if first is None else list(first)
     cap = [f0[k] + counts[k] for k in range(K)] if cap is None else list(cap)
     alloc = [max(cap[k], f0[k] + counts[k]) + EXTRA for k in range(K)] if alloc is None else list(alloc)
-    got = run(L, buf, buf_len, offs, first, cap, alloc)
+    got = run(L, buf, buf_len, offs, first, cap, alloc, scratch=scratch)
     exp, bad = expected(L, want, elem, f0, cap, alloc)
     print(f"{n} frames, buf_len {buf_len}: counts {got['counts'].tolist()} flags {got['flags']} first bad {got['bad']}")
     assert np.array_equal(got["cls"], want)

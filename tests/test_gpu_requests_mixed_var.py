@@ -134,15 +134,17 @@ class Outs:
         self.nslots = sum(nstr(rq) for _, rq, _ in P.methods)
 
 
-def run(P, O, raw, buf_len, offs, first, cap, scap, status=True):
-    """One call -> dict of what it wrote besides the columns (guards checked)."""
+def run(P, O, raw, buf_len, offs, first, cap, scap, status=True, scratch=None):
+    """One call -> dict of what it wrote besides the columns (guards checked;
+    scratch: the caller's own, which may be larger, instead of a fresh one)."""
     n, K = len(offs), P.K
     d_buf = dev(np.frombuffer(raw, np.uint8)) if len(raw) else empty(16)
     d_offs = dev(np.asarray(offs, np.uint32)) if n else empty(16)
     nb = MixedFrames.index_bytes(n, K)
     sb = P.req.scratch_bytes(n)
     d_cls, d_index, d_counts = empty(n + GUARD), empty(nb + GUARD), empty(8 * (K + 1) + GUARD)
-    d_ends, d_scratch = empty(8 * O.nslots + GUARD), empty(sb + GUARD)
+    d_ends, d_scratch = empty(8 * O.nslots + GUARD), empty(sb + GUARD) if scratch is None else scratch
+    behind = d_scratch[sb:].clone()
     st = status_buf()
     st[:] = 0x5A  # the call resets it
     rc = P.req.unpack_requests(d_buf, buf_len, d_offs, n, O.cols, O.offs, scap, first, cap, d_cls, d_index, nb, d_counts,
@@ -154,7 +156,7 @@ def run(P, O, raw, buf_len, offs, first, cap, scap, status=True):
     raw_counts = host(d_counts, 8 * (K + 1) + GUARD)
     raw_ends = host(d_ends, 8 * O.nslots + GUARD)
     assert (raw_counts[-GUARD:] == 0xA5).all() and (raw_ends[-GUARD:] == 0xA5).all()
-    assert (host(d_scratch, sb + GUARD)[sb:] == 0xA5).all(), "wrote past the scratch"
+    assert torch.equal(d_scratch[sb:], behind), "wrote past the scratch"
     return dict(cls=raw_cls[:n].copy(), counts=raw_counts[:8 * (K + 1)].view(np.uint64).copy(),
                 ends=raw_ends[:8 * O.nslots].view(np.uint64).copy(), flags=flags, bad=bad, d_cls=d_cls, d_index=d_index,
                 d_buf=d_buf, d_offs=d_offs)
@@ -219,7 +221,7 @@ def compare(P, legs, O, want, src, f0, cap, base, scap, ends=None, flags_bad=Non
 
 
 def check(P, legs, frames, intent, src, buf_len=None, offs=None, first=None, cap=None, alloc=None, base=None, scap_cut=0,
-          raw=None):
+          raw=None, scratch=None):
     """Run the call on the frames and compare everything it wrote with the
     host's expectation.  intent[i]: the class frame i was built to have; src[i]:
     the element of its plan's leg it was built from.  -> the run."""
@@ -258,7 +260,7 @@ def check(P, legs, frames, intent, src, buf_len=None, offs=None, first=None, cap
             for t in O.offs[k]:
                 if t is not None:
                     t[8 * f0[k]:8 * f0[k] + 8] = torch.from_numpy(np.array([base[k]], np.uint64).view(np.uint8).copy())
-    got = run(P, O, raw, buf_len, offs, first, cap, scap)
+    got = run(P, O, raw, buf_len, offs, first, cap, scap, scratch=scratch)
     assert np.array_equal(got["cls"], want)
     assert np.array_equal(classify_cls(P, got["d_buf"], buf_len, got["d_offs"], n), want)
     assert got["counts"].tolist() == counts + [int((want == UNKNOWN).sum())]
