@@ -82,7 +82,19 @@
 // The reply stream's size is known from the counts, so two batches stay in
 // flight as on the fixed ordered route.
 //
-// On both routes that serve string methods the string responses' sizes are
+// The ordered route over methods of all three kinds side by side
+// (set_ordered_legs / set_ordered_legs_handler; a record method's sizeof(Req)
+// <= 256) is the string route's skeleton through the calls that take, per
+// method, columns or a struct array:
+//
+//   srpc_frames_unpack_requests_mixed_legs (a column or string method's leaves,
+//   chars and offsets, a record method's Req structs, all at their arrival
+//   ranks) -> the handlers of each kind on their counts[k] requests, or the one
+//   ordered legs handler -> srpc_frames_pack_requests_mixed_legs over the
+//   response plans with d_method = d_class -> the total (and, with unknown
+//   frames, the offsets).  One batch in flight, as on the string route.
+//
+// On the routes that serve string methods the string responses' sizes are
 // checked on the host against their columns before anything reads the chars:
 // a method that overflows is answered on the CPU for this batch, its frames
 // turned into unknown ones (demote_overflowing).
@@ -256,6 +268,29 @@ struct ordered_records_batch {
     const uint64_t* resp_stride = nullptr;   // host, per method: sizeof(Resp)
 };
 
+/// A batch in ordered legs mode (batch_server::set_ordered_legs_handler): the
+/// union of ordered_var_batch and ordered_records_batch.  Method k is a column
+/// method (fixed-size or string-bodied: the column fields are
+/// ordered_var_batch's, the record fields null / 0) or a record method (the
+/// record fields are ordered_records_batch's, entry k of every column field
+/// null).  Unknown frames as in ordered_batch.
+struct ordered_legs_batch {
+    uint64_t n = 0;
+    const uint8_t* d_method = nullptr;   // device, n
+    const uint32_t* d_rank = nullptr;    // device, n
+    const uint64_t* counts = nullptr;    // host, methods + 1: frames per method, then the unknown ones
+    size_t methods = 0;
+    void* const* const* req_cols = nullptr;   // per column method: its device columns
+    void* const* const* resp_cols = nullptr;
+    const uint64_t* const* const* req_str_offs = nullptr;  // per column method: per-leaf device pointers
+    uint64_t* const* const* resp_str_offs = nullptr;
+    const uint64_t* const* resp_cap = nullptr;             // per column method: the bytes of each response column
+    const void* const* req_recs = nullptr;   // per record method: its device Req array
+    void* const* resp_recs = nullptr;        // per record method: its device Resp array
+    const uint64_t* req_stride = nullptr;    // host, per method: sizeof(Req), 0 for a column method
+    const uint64_t* resp_stride = nullptr;   // host, per method: sizeof(Resp), 0 for a column method
+};
+
 struct batch_stats {
     uint64_t requests = 0;           // frames answered
     uint64_t gpu_batches = 0;        // batches that went through the GPU path
@@ -332,8 +367,9 @@ public:
     /// leaves and nothing else matters.  Handlers must not call a virtual
     /// function on these objects: a vtable slot holds a host pointer (Req) or
     /// zero (Resp).  Record methods and column methods mix freely in one server.
-    /// The bucket route, or arrival order with set_ordered_records: with a
-    /// record method registered, serve_connection throws
+    /// The bucket route, or arrival order with set_ordered_records (record
+    /// methods only) or set_ordered_legs (beside column and string methods):
+    /// with a record method registered, serve_connection throws
     /// plan_error(SRPC_E_UNSUPPORTED) in set_ordered / set_ordered_var mode.
     template <SrpcMessage Req, SrpcMessage Resp>
     void register_record_method(std::string method, record_handler_t handler) {
@@ -380,7 +416,7 @@ public:
     void set_ordered(bool on) {
         if (on == _ordered) return;
         _ordered = on;
-        if (!on) _ordered_var = _ordered_rec = false;
+        if (!on) _ordered_var = _ordered_rec = _ordered_legs = false;
         release();
     }
     bool ordered() const { return _ordered; }
@@ -418,7 +454,7 @@ public:
         if (on == _ordered_var && on == _ordered) return;
         _ordered_var = on;
         _ordered = on;
-        _ordered_rec = false;
+        _ordered_rec = _ordered_legs = false;
         release();
     }
     bool ordered_var() const { return _ordered_var; }
@@ -454,7 +490,7 @@ public:
         if (on == _ordered_rec && on == _ordered) return;
         _ordered_rec = on;
         _ordered = on;
-        _ordered_var = false;
+        _ordered_var = _ordered_legs = false;
         release();
     }
     bool ordered_records() const { return _ordered_rec; }
@@ -467,6 +503,46 @@ public:
     void set_ordered_records_handler(ordered_records_handler_t handler) {
         _orhandler = std::move(handler);
         set_ordered_records(true);
+    }
+
+    /// handler(batch, stream) over a whole batch of every method of any kind in
+    /// arrival order (ordered_legs_batch).
+    using ordered_legs_handler_t = std::function<int(ordered_legs_batch const&, hipStream_t)>;
+
+    /// Ordered mode that admits register_method, register_var_method and
+    /// register_record_method methods side by side (off by default; implies
+    /// ordered mode and clears set_ordered_var / set_ordered_records;
+    /// set_ordered(false) clears it).  Request r of a method's batch is the
+    /// method's r-th frame in arrival order, whatever its kind: a column method
+    /// keeps its handler_t, a string method's var_handler_t gets a var_batch with
+    /// n = counts[k] (its request offsets start at 0), a record method's handler
+    /// gets (const Req*, Resp*, counts[k]) with every byte no leaf covers a
+    /// Req{}'s.  A batch goes through one srpc_frames_unpack_requests_mixed_legs
+    /// and one srpc_frames_pack_requests_mixed_legs over the response plans.
+    /// Timing and overflow handling are set_ordered_var's: one batch is in flight,
+    /// the route syncs for the reply stream's size, and a string method whose
+    /// responses do not fit their columns is answered by the CPU server for that
+    /// batch (batch_stats::overflow_batches) while the other methods' elements do
+    /// not move.  serve_connection throws plan_error(SRPC_E_UNSUPPORTED) for a
+    /// record method with sizeof(Req) > 256 (sizeof(Resp) is free).  set_ordered,
+    /// set_ordered_var and set_ordered_records keep refusing what they refuse.
+    void set_ordered_legs(bool on) {
+        if (on == _ordered_legs && on == _ordered) return;
+        _ordered_legs = on;
+        _ordered = on;
+        _ordered_var = _ordered_rec = false;
+        release();
+    }
+    bool ordered_legs() const { return _ordered_legs; }
+    /// One handler for every method of any kind, run once per batch instead of
+    /// the per-method handlers; implies set_ordered_legs(true).  Timing, warm-up
+    /// and the treatment of unknown frames are set_ordered_handler's: batches
+    /// reach it in connection order on the server's stream, frames the GPU path
+    /// does not take are answered by the CPU server after the batch's handler ran,
+    /// and at serve start it is run on a batch of one unknown frame.
+    void set_ordered_legs_handler(ordered_legs_handler_t handler) {
+        _olhandler = std::move(handler);
+        set_ordered_legs(true);
     }
 
     uint64_t request_frame_bytes(size_t k = 0) const { return _m.at(k)->fin; }
@@ -485,10 +561,10 @@ public:
     /// waiting.  Answers leave in request order.
     batch_stats serve_connection(int fd) {
         if (_m.empty()) throw plan_error("batch_server::serve_connection (no methods)", SRPC_E_INVALID);
-        if (_ordered && !_ordered_var && any_var_method())
+        if (_ordered && !strings_route() && any_var_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a string-bodied method)",
                              SRPC_E_UNSUPPORTED);
-        if (_ordered && !_ordered_rec && any_record_method())
+        if (_ordered && !_ordered_rec && !_ordered_legs && any_record_method())
             throw plan_error("batch_server::serve_connection (ordered mode with a record method)", SRPC_E_UNSUPPORTED);
         if (_ordered_rec)
             for (auto const& m : _m) {
@@ -502,6 +578,11 @@ public:
                     throw plan_error("batch_server::serve_connection (ordered records mode with a Req above 256 bytes)",
                                      SRPC_E_UNSUPPORTED);
             }
+        if (_ordered_legs)
+            for (auto const& m : _m)
+                if (m->rec && m->req_stride > kRecordFillMax)
+                    throw plan_error("batch_server::serve_connection (ordered legs mode with a Req above 256 bytes)",
+                                     SRPC_E_UNSUPPORTED);
         check(hipSetDevice(_dev));
         ensure();
         batch_stats st;
@@ -733,6 +814,9 @@ private:
             if (m->rec) return true;
         return false;
     }
+    /// An ordered route that serves string methods: one batch in flight, the
+    /// replies sized on the device (set_ordered_var, set_ordered_legs).
+    bool strings_route() const { return _ordered_var || _ordered_legs; }
     static constexpr uint64_t kRecordFillMax = 256;  // struct bytes srpc_gpu_unpack_aos_fill takes
 
     // ---- the buffers: owned in groups, built by ensure(), dropped by release() ----
@@ -829,7 +913,7 @@ private:
         for (size_t f = 0; f < m.resp_string.size(); ++f)
             if (m.resp_string[f]) m.resp_wire_cap += m.resp_bytes[f];
         m.h_ends.alloc(16 * m.resp_string.size() + 16);
-        if (_ordered_var) return;  // the replies are packed straight into the reply stream
+        if (strings_route()) return;  // the replies are packed straight into the reply stream
         m.resp_wire.alloc(m.resp_wire_cap);
         m.resp_rec.alloc(8 * (_max + 1) + 16);
         uint64_t a = 0, b = 0;
@@ -856,7 +940,7 @@ private:
         // batches need the host between their kernels (SRPC_SERVER_SLOTS=1:
         // one batch at a time, the A/B baseline)
         const char* slots_env = std::getenv("SRPC_SERVER_SLOTS");
-        _nslots = _var_methods || _ordered_var || (slots_env && slots_env[0] == '1') ? 1 : 2;
+        _nslots = _var_methods || strings_route() || (slots_env && slots_env[0] == '1') ? 1 : 2;
         for (int i = 0; i < _nslots; ++i) {
             slot& z = _slots[i];
             z.h_in.alloc(_cap + 16);
@@ -886,13 +970,22 @@ private:
                            "srpc_frames_mixed_aos_scratch_bytes");
                 _or.d_scratch.alloc(_or_scratch_bytes + 16);
             }
-            if (_ordered_var) {
+            if (strings_route()) {
                 if (out_cap > 0xffffffffull) throw plan_error("batch_server: reply buffer over 4 GiB", SRPC_E_UNSUPPORTED);
                 uint64_t a = 0, b = 0;
-                check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_in_plans.data(), static_cast<int>(K), _max, &a),
-                           "srpc_frames_mixed_var_scratch_bytes");
-                check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_out_plans.data(), static_cast<int>(K), _max, &b),
-                           "srpc_frames_mixed_var_scratch_bytes");
+                if (_ordered_legs) {  // the same layout, then the record methods' tables and fills
+                    check_srpc(srpc_frames_mixed_legs_scratch_bytes(_ord_in_plans.data(), static_cast<int>(K),
+                                                                    _or_req_stride.data(), _max, &a),
+                               "srpc_frames_mixed_legs_scratch_bytes");
+                    check_srpc(srpc_frames_mixed_legs_scratch_bytes(_ord_out_plans.data(), static_cast<int>(K),
+                                                                    _or_resp_stride.data(), _max, &b),
+                               "srpc_frames_mixed_legs_scratch_bytes");
+                } else {
+                    check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_in_plans.data(), static_cast<int>(K), _max, &a),
+                               "srpc_frames_mixed_var_scratch_bytes");
+                    check_srpc(srpc_frames_mixed_var_scratch_bytes(_ord_out_plans.data(), static_cast<int>(K), _max, &b),
+                               "srpc_frames_mixed_var_scratch_bytes");
+                }
                 _ov_scratch_bytes = std::max(a, b);
                 _ov.d_scratch.alloc(_ov_scratch_bytes + 16);
                 _ov.d_ends.alloc(8 * (_ov_slots + 1) + 16);
@@ -929,23 +1022,24 @@ private:
         _caps.assign(_m.size(), _max);
         _ov_slots = 0;
         for (auto& m : _m) {
-            if (_ordered_var && m->var && !m->in_str()) m->ord_in = std::make_unique<raw_plan>(m->in_kinds, m->framed_in, _dev);
-            if (_ordered_var && m->var && !m->out_str())
+            if (strings_route() && m->var && !m->in_str()) m->ord_in = std::make_unique<raw_plan>(m->in_kinds, m->framed_in, _dev);
+            if (strings_route() && m->var && !m->out_str())
                 m->ord_out = std::make_unique<raw_plan>(m->out_kinds, m->framed_out, _dev);
             _in_plans.push_back(m->in->get());
             _ord_in_plans.push_back(m->ord_in ? m->ord_in->get() : m->in->get());
             _ord_out_plans.push_back(m->ord_out ? m->ord_out->get() : m->out->get());
             _resp_bytes.push_back(static_cast<uint32_t>(m->fout));
             _var_rec.push_back(m->resp_rec);
-            _req_tbl.push_back(m->req_cols.data());
-            _resp_mut_tbl.push_back(m->resp_cols.data());
-            _resp_tbl.push_back(m->c_resp_cols.data());
-            _ov_req_offs.push_back(m->req_offs.data());
-            _ov_c_req_offs.push_back(m->c_req_offs.data());
-            _ov_resp_offs.push_back(m->resp_offs.data());
-            _ov_c_resp_offs.push_back(m->c_resp_offs.data());
-            _ov_req_scap.push_back(m->req_scap.data());
-            _ov_resp_cap.push_back(m->resp_bytes.data());
+            // a column method's columns and offsets arrays (null for a record method)
+            _req_tbl.push_back(m->rec ? nullptr : m->req_cols.data());
+            _resp_mut_tbl.push_back(m->rec ? nullptr : m->resp_cols.data());
+            _resp_tbl.push_back(m->rec ? nullptr : m->c_resp_cols.data());
+            _ov_req_offs.push_back(m->rec ? nullptr : m->req_offs.data());
+            _ov_c_req_offs.push_back(m->rec ? nullptr : m->c_req_offs.data());
+            _ov_resp_offs.push_back(m->rec ? nullptr : m->resp_offs.data());
+            _ov_c_resp_offs.push_back(m->rec ? nullptr : m->c_resp_offs.data());
+            _ov_req_scap.push_back(m->rec ? nullptr : m->req_scap.data());
+            _ov_resp_cap.push_back(m->rec ? nullptr : m->resp_bytes.data());
             for (uint64_t* o : m->req_offs) _ov_slots += o ? 1 : 0;
             // a record method's struct arrays (null and zero for the others)
             _or_req_recs.push_back(m->d_reqs);
@@ -1255,20 +1349,30 @@ private:
         }
     }
 
-    // -- the ordered routes (set_ordered, set_ordered_var, set_ordered_records): one decode, the handlers, one pack --
+    // -- the ordered routes (set_ordered, set_ordered_var, set_ordered_records, set_ordered_legs): one decode, the handlers, one pack --
 
     bool whole_batch_handler() const {
-        return _ordered_var ? bool(_ovhandler) : _ordered_rec ? bool(_orhandler) : bool(_ohandler);
+        return _ordered_legs ? bool(_olhandler)
+               : _ordered_var ? bool(_ovhandler)
+               : _ordered_rec ? bool(_orhandler)
+                              : bool(_ohandler);
     }
 
-    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed[_var|_aos]
+    /// The decode half of a batch: one srpc_frames_unpack_requests_mixed[_var|_aos|_legs]
     /// over the nf frames in d_in[0, used) into the methods' request columns
     /// (chars and offsets too) or Req arrays, the ranks when the ordered handler is set, then
     /// the counts (and the string slots' ends) on the host after one sync.
     void ordered_decode(uint64_t nf, uint64_t used) {
         const int K = static_cast<int>(_m.size());
         clear_status();
-        if (_ordered_var)
+        if (_ordered_legs)
+            check_srpc(srpc_frames_unpack_requests_mixed_legs(
+                           _ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf, _req_tbl.data(), _ov_req_offs.data(),
+                           _ov_req_scap.data(), _or_req_recs.data(), _or_req_stride.data(), _or_req_loffs.data(),
+                           _or_fill.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, _mix_index_bytes,
+                           _b.d_counts, _ov.d_ends, _b.d_status, _ov.d_scratch, _ov_scratch_bytes, _s),
+                       "srpc_frames_unpack_requests_mixed_legs");
+        else if (_ordered_var)
             check_srpc(srpc_frames_unpack_requests_mixed_var(
                            _ord_in_plans.data(), K, _b.d_in, used, _b.d_offs, nf, _req_tbl.data(), _ov_req_offs.data(),
                            _ov_req_scap.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, _mix_index_bytes,
@@ -1288,7 +1392,7 @@ private:
         if (whole_batch_handler())
             check_srpc(srpc_frames_mixed_ranks(_od.d_mix_index, _b.d_cls, nf, K, _od.d_rank, _s), "srpc_frames_mixed_ranks");
         check(hipMemcpyAsync(_b.h_counts, _b.d_counts, 8 * (static_cast<uint64_t>(K) + 1), hipMemcpyDeviceToHost, _s));
-        if (_ordered_var && _ov_slots)
+        if (strings_route() && _ov_slots)
             check(hipMemcpyAsync(_ov.h_ends, _ov.d_ends, 8 * _ov_slots, hipMemcpyDeviceToHost, _s));
         check(hipStreamSynchronize(_s));
     }
@@ -1320,12 +1424,24 @@ private:
                 b.req_cols = _req_tbl.data();
                 b.resp_cols = _resp_mut_tbl.data();
             };
-            if (_ordered_var) {
-                ordered_var_batch b;
-                fill(b);
+            auto fill_strings = [&](auto& b) {
                 b.req_str_offs = _ov_c_req_offs.data();
                 b.resp_str_offs = _ov_resp_offs.data();
                 b.resp_cap = _ov_resp_cap.data();
+            };
+            if (_ordered_legs) {
+                ordered_legs_batch b;
+                fill(b);
+                fill_strings(b);
+                b.req_recs = _or_c_req_recs.data();
+                b.resp_recs = _or_resp_recs.data();
+                b.req_stride = _or_req_stride.data();
+                b.resp_stride = _or_resp_stride.data();
+                check_srpc(_olhandler(b, _s), what);
+            } else if (_ordered_var) {
+                ordered_var_batch b;
+                fill(b);
+                fill_strings(b);
                 check_srpc(_ovhandler(b, _s), what);
             } else {
                 ordered_batch b;
@@ -1359,7 +1475,7 @@ private:
                        "srpc_frames_pack_requests_mixed_aos (replies)");
             return;
         }
-        if (!_ordered_var) {  // (the flag a bad call would raise is not asked for)
+        if (!strings_route()) {  // (the flag a bad call would raise is not asked for)
             check_srpc(srpc_frames_pack_requests_mixed(_ord_out_plans.data(), K, _resp_tbl.data(), nullptr, _caps.data(),
                                                        _b.d_cls, _od.d_mix_index, nf, _b.d_out, out_cap(), nullptr, nullptr,
                                                        _s),
@@ -1367,12 +1483,19 @@ private:
             return;
         }
         // an unknown frame is the pack's "bad call" and would raise its flag: asked for only without one
-        check_srpc(srpc_frames_pack_requests_mixed_var(_ord_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(),
-                                                       nullptr, _caps.data(), _b.d_cls, _od.d_mix_index, nf, _b.d_out,
-                                                       out_cap(), _ov.d_offs, _ov.d_total,
-                                                       unknown ? nullptr : _b.d_status + K, _ov.d_scratch,
-                                                       _ov_scratch_bytes, _s),
-                   "srpc_frames_pack_requests_mixed_var (replies)");
+        if (_ordered_legs)  // a record method's replies from its Resp array
+            check_srpc(srpc_frames_pack_requests_mixed_legs(
+                           _ord_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(), _or_c_resp_recs.data(),
+                           _or_resp_stride.data(), _or_resp_loffs.data(), nullptr, _caps.data(), _b.d_cls, _od.d_mix_index,
+                           nf, _b.d_out, out_cap(), _ov.d_offs, _ov.d_total, unknown ? nullptr : _b.d_status + K,
+                           _ov.d_scratch, _ov_scratch_bytes, _s),
+                       "srpc_frames_pack_requests_mixed_legs (replies)");
+        else
+            check_srpc(srpc_frames_pack_requests_mixed_var(
+                           _ord_out_plans.data(), K, _resp_tbl.data(), _ov_c_resp_offs.data(), nullptr, _caps.data(),
+                           _b.d_cls, _od.d_mix_index, nf, _b.d_out, out_cap(), _ov.d_offs, _ov.d_total,
+                           unknown ? nullptr : _b.d_status + K, _ov.d_scratch, _ov_scratch_bytes, _s),
+                       "srpc_frames_pack_requests_mixed_var (replies)");
         check(hipMemcpyAsync(_ov.h_total, _ov.d_total, 8, hipMemcpyDeviceToHost, _s));
         if (unknown) check(hipMemcpyAsync(_ov.h_offs, _ov.d_offs, 4 * (nf + 1), hipMemcpyDeviceToHost, _s));
     }
@@ -1396,7 +1519,7 @@ private:
         }
         ordered_handlers(nf, false);
         mark("handler");
-        if (!_ordered_var) {
+        if (!strings_route()) {
             if (total) ordered_pack(nf, false);
             mark("pack");
             pd.d2h_extra = unknown ? nf : 0;
@@ -1439,7 +1562,7 @@ private:
         if (_ordered) {
             check(hipMemsetAsync(_od.d_mix_index, 0, _mix_index_bytes + 16, _s));
             check(hipMemsetAsync(_od.d_rank, 0, 4 * _max + 16, _s));
-            if (_ordered_var) {
+            if (strings_route()) {
                 check(hipMemsetAsync(_ov.d_scratch, 0, _ov_scratch_bytes, _s));
                 check(hipMemsetAsync(_ov.d_offs, 0, 4 * (_max + 1) + 16, _s));
             }
@@ -1661,10 +1784,11 @@ private:
     std::vector<uint8_t> _flat;
     bool _trace = std::getenv("SRPC_SERVER_TRACE") != nullptr;  // per-recv / per-batch timeline on stderr
     trace_point _tp;
-    bool _ordered = false, _ordered_var = false, _ordered_rec = false;
+    bool _ordered = false, _ordered_var = false, _ordered_rec = false, _ordered_legs = false;
     ordered_handler_t _ohandler;
     ordered_var_handler_t _ovhandler;
     ordered_records_handler_t _orhandler;
+    ordered_legs_handler_t _olhandler;
     // the buffers (ensure / release)
     slot _slots[2];
     int _nslots = 0;

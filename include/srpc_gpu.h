@@ -1294,7 +1294,92 @@ int srpc_frames_unpack_requests_mixed_var(
     uint64_t* d_counts /* nplans + 1, out */, uint64_t* d_ends /* one per string slot, out */,
     srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
 
-/* ---- utilities --------------------------------------------------------------*/
+/* ---- batches of request frames of several methods in arrival order, each plan's
+ * requests into columns or into a struct array (server side; added within ABI 8) --
+ * srpc_frames_unpack_requests_mixed_var with, per plan, the choice
+ * srpc_frames_unpack_requests_mixed_aos offers for all plans at once: one device
+ * array of the caller's own structs in place of the plan's columns.  It is the
+ * mirror of srpc_frames_pack_requests_mixed_legs.  The arguments are the
+ * _mixed_var request call's plus d_recs, h_stride, h_leaf_offs and h_fill of the
+ * _mixed_aos request call, all host arrays of K entries.  The contract is the
+ * union of the two sections above ("with string bodies, in arrival order" and
+ * "into struct arrays, in arrival order"), per plan, and nothing new.
+ *
+ * Plan k is a RECORD plan exactly when h_stride[k] != 0, the rule of the
+ * _mixed_legs client calls.  It must be a fixed-size plan with a framed prefix
+ * and h_stride[k] <= 256; its d_cols[k], d_str_offs[k] and h_str_cap[k] are not
+ * read and may be NULL.  Every other plan is a COLUMN plan, fixed-size or
+ * string, exactly as srpc_frames_unpack_requests_mixed_var takes it; its
+ * d_recs[k], h_leaf_offs[k] and h_fill[k] are not read.  Any combination of
+ * kinds in any plan order is one valid call, all of one kind included.
+ *
+ *   d_class, d_index, d_counts and d_ends are byte-identical to what
+ *     srpc_frames_unpack_requests_mixed_var writes for the same plans and bytes
+ *     (string slots are numbered over the string plans, as there): the class is
+ *     srpc_frames_classify's, the first matching plan wins.  A frame whose
+ *     element h_first[k] + rank(i) would be at or past h_cap[k] keeps its class
+ *     and writes nothing: SRPC_STATUS_BOUNDS, first_bad_record the smallest such
+ *     i; *d_status (may be NULL) is reset by the call.
+ *   A column plan's fixed leaves, chars and absolute string offsets are written
+ *     as srpc_frames_unpack_requests_mixed_var writes them, the continuation
+ *     from entry h_first[k] included.
+ *   A record plan's structs are written as srpc_frames_unpack_requests_mixed_aos
+ *     writes them: element h_first[k] + rank(i), when below h_cap[k], is written
+ *     whole, exactly once, and never read -- leaf bytes from the frame, every
+ *     other byte from h_fill[k] (h_stride[k] host bytes, copied during the
+ *     call).  Nothing is written for an unknown frame or an element past the
+ *     cap, and no byte outside the plan's elements of this batch is written.
+ *   - no byte outside [d_buf, d_buf + buf_len) is read, whatever d_offs holds:
+ *     the decode pass checks every extent again and does not trust d_class;
+ *   - the call is stream-ordered, allocates nothing and waits on no other
+ *     workgroup; its launches are the _mixed_var request call's plus one per
+ *     2 KiB of tables and fills, and depend on neither the data nor the order
+ *     of the plans, so it can be captured.
+ *
+ * Scratch: srpc_frames_mixed_legs_scratch_bytes(req_plans, K, h_stride, nframes),
+ * 16-byte aligned.  Tile rule: both passes take srpc_frames_mixed_legs_tile's
+ * frames per tile, called with the request plans, and the parse pass its image
+ * window: the record plans' tables and fills lie in the tail of the 32 KiB
+ * image, so the workgroup's dynamic LDS is that of the _mixed_var request
+ * decode.  A lane of a column plan walks and stores its frame as that decode's
+ * does; a lane of a record plan leaves where its frame is, and the workgroup
+ * writes the record plans' slices of the tile as whole 16-byte pieces with
+ * non-temporal stores (a frame that a long string pushed out of the window is
+ * read from d_buf, at most F_k bytes, its extent checked again).  Without a
+ * record plan the call launches the _mixed_var request call's own kernels.
+ *
+ * Refused with nothing launched, in the order of
+ * srpc_frames_unpack_replies_mixed_legs:
+ *   1. SRPC_E_INVALID (before any plan is read): the _mixed_var request call's
+ *      NULL and range checks with d_recs, h_stride, h_leaf_offs and h_fill among
+ *      the pointers; h_stride[k] >= 2^32; for a record plan a NULL
+ *      h_leaf_offs[k] or h_fill[k], or a NULL d_recs[k] where h_cap[k] leaves an
+ *      element;
+ *   2. SRPC_E_UNSUPPORTED: what the _mixed_var request call refuses so; a string
+ *      plan with a non-zero stride; a stride above 256;
+ *   3. SRPC_E_INVALID: a record plan's leaves overlapping or past the stride;
+ *   4. SRPC_E_ALIGN: d_buf, an array, d_scratch (16), the index, d_counts, d_ends
+ *      (8), d_offs (4), an offset or stride against its leaf's size; then the
+ *      column plans' pointers as the _mixed_var request call checks them (a NULL
+ *      one: SRPC_E_INVALID);
+ *   5. SRPC_E_CAPACITY: index_bytes or scratch_bytes.
+ *
+ * The ordered reply pack needs no call of its own: it is
+ * srpc_frames_pack_requests_mixed_legs with the RESPONSE plans (each in columns
+ * or in a struct array, whatever its request plan's kind), d_method = d_class
+ * and the d_index this call wrote; it writes the reply stream in arrival order,
+ * zero bytes for an unknown frame. */
+int srpc_frames_unpack_requests_mixed_legs(
+    const srpc_plan* const* req_plans, int nplans,
+    const uint8_t* d_buf, uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+    void* const* const* d_cols, uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap,
+    void* const* d_recs, const uint64_t* h_stride, const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+    const uint64_t* h_first, const uint64_t* h_cap,
+    uint8_t* d_class /* nframes, out */, void* d_index, uint64_t index_bytes,
+    uint64_t* d_counts /* nplans + 1, out */, uint64_t* d_ends /* one per string slot, out */,
+    srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes, void* stream);
+
+/* ---- utilities--------------------------------------------------------------*/
 
 /* Synthetic input of SURVEY.md §8c: nfields int32 columns, record i field f =
  * low 32 bits of splitmix64 draw number (first_record + i) * nfields + f + 1

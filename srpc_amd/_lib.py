@@ -125,6 +125,9 @@ SIGNATURES = {
     "srpc_frames_unpack_replies_mixed_legs": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _u64, C.c_uint8,
                                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                         _vp, _u64, _vp]),
+    "srpc_frames_unpack_requests_mixed_legs": (C.c_int, [_vp, C.c_int, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                                         _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64,
+                                                         _vp]),
     "srpc_status_string": (C.c_char_p, [C.c_int]),
     "srpc_gpu_abi_version": (C.c_int, []),
 }

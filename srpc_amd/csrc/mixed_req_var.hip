@@ -25,7 +25,11 @@
 //       (mix_ranks); a lane per frame stores its fixed leaves, each string's
 //       length into its offsets entry and its chars' stream offset to scratch.
 //       Every read is bounded by the frame's own extent again: the class is
-//       not trusted to keep the walk inside buf_len.
+//       not trusted to keep the walk inside buf_len.  The lane's frame and its
+//       walk (MrvFrame, mrv_lane_walk) live in mixed_req_var_tile.h, which
+//       mixed_req_legs.hip's parse kernel shares; that file also launches
+//       k_mrv_classify and, for a batch without a record plan, this kernel
+//       (mrv_classify_launch, mrv_parse_launch).
 //   the slot scan and the char copy of mixed_var.hip (mv_slots_launch,
 //       mv_copy_launch) with d_class as the method vector.
 #include <hip/hip_runtime.h>
@@ -34,6 +38,7 @@
 #include <cstdint>
 
 #include "mixed_common.h"
+#include "mixed_req_var_tile.h"
 #include "mixed_var_common.h"
 #include "plan.h"
 #include "srpc_gpu.h"
@@ -42,27 +47,6 @@ namespace srpc_impl {
 namespace {
 
 constexpr uint32_t kMrvUnknown = SRPC_FRAME_UNKNOWN;
-
-// The frame of a lane: in the image when it lies whole inside it, else in
-// global memory.
-struct MrvFrame {
-    const uint8_t* img;  // the image
-    const uint8_t* g;    // the frame in global memory
-    uint32_t q;          // the frame's image offset
-    bool in_img;
-};
-
-// 8 bytes at frame byte c (c + 8 <= the frame's length).
-__device__ __forceinline__ uint64_t mrv_u64(const MrvFrame& fr, uint64_t c) {
-    return fr.in_img ? lds_u64(fr.img, fr.q + static_cast<uint32_t>(c)) : mv_get(fr.g + c, 8);
-}
-
-// The s <= 8 bytes at frame byte c.
-__device__ __forceinline__ uint64_t mrv_field(const MrvFrame& fr, uint64_t c, uint32_t s) {
-    if (!fr.in_img) return mv_get(fr.g + c, s);
-    const uint32_t at = fr.q + static_cast<uint32_t>(c);
-    return s == 1 ? fr.img[at] : lds_u64(fr.img, at) & (s == 8 ? ~0ull : (1ull << (8 * s)) - 1);
-}
 
 // Frame bytes [at, at + pl) == the template (8-byte aligned in LDS, pl > 0).
 __device__ __forceinline__ bool mrv_prefix_eq(const MrvFrame& fr, uint32_t at, const uint8_t* pre, uint32_t pl) {
@@ -175,44 +159,24 @@ __global__ __launch_bounds__(kBlock) void k_mrv_parse(const MvDesc* __restrict__
         if (st) report_bad(st, SRPC_STATUS_BOUNDS, i);
         return;
     }
-    const uint32_t j = threadIdx.x - j0;
-    const uint64_t o = lo[j], end = lo[j + 1];
-    // the class says the frame is one record of plan k; every read below is still
-    // bounded by the frame's own extent, and what does not fit decodes to zero / empty
-    bool ok = o <= end && end <= buf_len;
-    const uint64_t len = ok ? end - o : 0;
-    MrvFrame fr;
-    fr.img = img;
-    fr.g = buf + o;
-    fr.in_img = ok && o >= sp.s0 && o - sp.s0 + len <= sp.staged;
-    fr.q = static_cast<uint32_t>(o - sp.s0);
-    const uint64_t e = d->first[k] + r.rank;
-    uint64_t c = (d->var[k] ? 4 : 0) + d->prefix_len[k];
-    ok = ok && c <= len;
-    uint32_t t = 0;
-    for (uint32_t f = d->field0[k]; f < d->field0[k + 1]; ++f) {
-        const uint32_t s = d->size[f];
-        if (s) {
-            ok = ok && s <= len - c;
-            store_elem(d->col[f] + e * s, s, ok ? mrv_field(fr, c, s) : 0);
-            if (ok) c += s;
-        } else {
-            ok = ok && 8 <= len - c;
-            uint64_t sl = ok ? mrv_u64(fr, c) : 0;
-            if (ok) c += 8;
-            if (sl > len - c) {
-                sl = 0;
-                ok = false;
-            }
-            d->soffs[f][e + 1] = sl;  // its length: the slot scan turns lengths into offsets
-            srcs[t * nframes + i] = static_cast<uint32_t>(o + c);
-            c += sl;
-            ++t;
-        }
-    }
+    mrv_lane_walk(d, k, r.rank, threadIdx.x - j0, i, lo, img, sp, buf, buf_len, nframes, srcs);
 }
 
 }  // namespace
+
+void mrv_classify_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_buf, uint64_t buf_len,
+                         const uint32_t* d_offs, uint64_t nframes, uint8_t* d_class, hipStream_t s) {
+    launch(k_mrv_classify, dim3(static_cast<uint32_t>((nframes + d.T - 1) / d.T)), dim3(kBlock), mv_lds(d), s, dd, d_buf,
+           buf_len, d_offs, nframes, d_class);
+}
+
+void mrv_parse_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_class, const uint32_t* table, uint64_t rows,
+                      const uint8_t* d_buf, uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes, uint32_t* srcs,
+                      uint32_t* counts, srpc_unpack_status* d_status, hipStream_t s) {
+    launch(k_mrv_parse, dim3(static_cast<uint32_t>((nframes + d.T - 1) / d.T)), dim3(kBlock), kMixImage + 16, s, dd,
+           d_class, table, rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status);
+}
+
 }  // namespace srpc_impl
 
 using namespace srpc_impl;
@@ -251,17 +215,14 @@ int srpc_frames_unpack_requests_mixed_var(const srpc_plan* const* req_plans, int
     auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
     auto* table = static_cast<uint32_t*>(d_index);
     const uint64_t rows = mix_rows(nframes);
-    const uint32_t grid = static_cast<uint32_t>((nframes + d.T - 1) / d.T);
     if (d_status)
         if (int rc = mix_status_reset_launch(d_status, s)) return rc;
     if (int rc = mv_upload(d, d_scratch, s)) return rc;
-    if (nframes)
-        launch(k_mrv_classify, dim3(grid), dim3(kBlock), mv_lds(d), s, dd, d_buf, buf_len, d_offs, nframes, d_class);
+    if (nframes) mrv_classify_launch(d, dd, d_buf, buf_len, d_offs, nframes, d_class, s);
     // unknown frames (0xFF) are ids >= K: column K of the index; no status here
     if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
     if (nframes)
-        launch(k_mrv_parse, dim3(grid), dim3(kBlock), kMixImage + 16, s, dd, static_cast<const uint8_t*>(d_class),
-               static_cast<const uint32_t*>(table), rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status);
+        mrv_parse_launch(d, dd, d_class, table, rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status, s);
     if (d.nslots) {
         mv_slots_launch(d, dd, counts, nframes, partial, sc.nb, d_ends, s);
         if (nframes)

@@ -1,6 +1,7 @@
 // mixed_var_common.h -- internal: what mixed_var.hip (client side: request pack,
-// reply decode) and mixed_req_var.hip (server side: request decode) share: the
-// description of the plans that both put into scratch (MvDesc), its host-side
+// reply decode), mixed_req_var.hip (server side: request decode) and the two
+// files over plans of both kinds (mixed_legs.hip, mixed_req_legs.hip) share: the
+// description of the plans that they put into scratch (MvDesc), its host-side
 // builders, the scratch layout, and the launches of the kernels that stay in
 // mixed_var.hip -- the description upload, the segmented scan over the string
 // slots and the char copy.

@@ -729,7 +729,8 @@ class MixedLegFrames(MixedVarFrames):
     """``MixedVarFrames.pack`` / ``unpack`` with, per plan, the choice between
     columns and one device array of the caller's structs
     (srpc_frames_pack_requests_mixed_legs / _unpack_replies_mixed_legs; the
-    index is ``MixedFrames.index``).  ``strides[k]``: plan k's struct bytes, or 0
+    index is ``MixedFrames.index``), and the server's ``unpack_requests``
+    (srpc_frames_unpack_requests_mixed_legs).  ``strides[k]``: plan k's struct bytes, or 0
     for a plan held in columns (fixed-size or string); ``leaf_offsets[k][f]``:
     the byte offset of leaf f in the struct (None for a column plan).
     ``cols[k]`` / ``str_offs[k]`` / ``str_cap[k]`` are ``MixedVarFrames``'s and
@@ -788,6 +789,28 @@ class MixedLegFrames(MixedVarFrames):
                                                                 self._strides, self._offs, h_fill, h_first, h_cap,
                                                                 _dptr(codes), _dptr(ends), _dptr(status),
                                                                 _dptr(scratch), scratch_bytes, _stream(stream))
+
+    def unpack_requests(self, buf, buf_len: int, offs, nframes: int, cols, str_offs, str_cap, recs, fills, first, cap,
+                        cls, index, index_bytes: int, counts, ends, status, scratch, scratch_bytes: int,
+                        stream=None) -> int:
+        """Server side (srpc_frames_unpack_requests_mixed_legs): classify the
+        frames against these request plans and decode each at its arrival rank
+        into its plan's columns, or into element ``first[k] + rank`` of
+        ``recs[k]`` for a record plan, bytes no leaf covers from ``fills[k]``;
+        ``cls``, ``index``, ``counts`` and ``ends`` are outputs.  The ordered
+        reply pack is ``pack`` of the response plans' MixedLegFrames with
+        ``method=cls`` and this ``index``."""
+        c_arr, s_arr, h_first, h_cap = self._args(cols, str_offs, first, cap)
+        cap_arr, k3 = self._table(str_cap, lambda x: 0 if x is None else int(x), C.c_uint64)
+        keep = [None if f is None else C.create_string_buffer(bytes(f), max(1, len(bytes(f)))) for f in fills]
+        h_fill = (C.c_void_p * self.k)(*[None if b is None else C.cast(b, C.c_void_p).value for b in keep])
+        self._keep += (k3, keep)
+        return _lib.lib().srpc_frames_unpack_requests_mixed_legs(self._plans, self.k, _dptr(buf), buf_len, _dptr(offs),
+                                                                 nframes, c_arr, s_arr, cap_arr, self._recs(recs),
+                                                                 self._strides, self._offs, h_fill, h_first, h_cap,
+                                                                 _dptr(cls), _dptr(index), index_bytes, _dptr(counts),
+                                                                 _dptr(ends), _dptr(status), _dptr(scratch),
+                                                                 scratch_bytes, _stream(stream))
 
 
 __all__ = ["Schema", "GpuPacker", "SrpcError", "request_prefix", "response_prefix",
