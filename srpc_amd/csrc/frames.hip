@@ -877,6 +877,12 @@ __global__ void k_reset_status(srpc_unpack_status* st) {
 }
 
 }  // namespace
+
+int status_reset_launch(srpc_unpack_status* d_status, hipStream_t s) {
+    hipLaunchKernelGGL(k_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+}
+
 }  // namespace srpc_impl
 
 using namespace srpc_impl;
@@ -1013,10 +1019,7 @@ int srpc_frames_unpack_replies(const srpc_plan* reply_plan, const uint8_t* d_buf
         if (!aligned(d_cols[f], 16)) return SRPC_E_ALIGN;
     }
     auto s = static_cast<hipStream_t>(stream);
-    if (d_status) {
-        hipLaunchKernelGGL(k_reset_status, dim3(1), dim3(64), 0, s, d_status);
-        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    }
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (!nframes) return SRPC_OK;
     ReplyArgs a{};
     for (uint32_t f = 0; f < p->nfields; ++f) {
@@ -1092,10 +1095,7 @@ int srpc_frames_unpack_replies_var(const srpc_plan* reply_plan, const uint8_t* d
     a.nstr = p->nstrings;
     a.prefix_len = p->prefix_len;
     auto s = static_cast<hipStream_t>(stream);
-    if (d_status) {
-        hipLaunchKernelGGL(k_reset_status, dim3(1), dim3(64), 0, s, d_status);
-        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    }
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     auto* lens = static_cast<uint32_t*>(d_scratch);
     auto* srcs = lens + a.nstr * nframes;
     auto* part = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(d_scratch) + 8 * a.nstr * nframes);

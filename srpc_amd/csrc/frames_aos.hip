@@ -234,14 +234,6 @@ __global__ __launch_bounds__(kBlock) void k_unpack_replies_aos(ReplyAosArgs a, c
     }
 }
 
-__global__ void k_reset_status_aos(srpc_unpack_status* st) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        st->flags = 0;
-        st->reserved = 0;
-        st->first_bad_record = ~0ull;
-    }
-}
-
 int reply_aos_plan_ok(const srpc_plan* p, uint64_t record_stride) {
     if (p->has_string || p->prefix_len < 5 || record_stride > kAosMaxStride) return SRPC_E_UNSUPPORTED;
     return SRPC_OK;
@@ -281,10 +273,7 @@ int srpc_frames_unpack_replies_aos(const srpc_plan* reply_plan, const uint8_t* d
     if (!aligned(d_buf, 16) || !aligned(d_records, 16)) return SRPC_E_ALIGN;
     if (!aos_layout_aligned(p, field_offsets, stride)) return SRPC_E_ALIGN;  // as in C++ structs
     auto s = static_cast<hipStream_t>(stream);
-    if (d_status) {
-        hipLaunchKernelGGL(k_reset_status_aos, dim3(1), dim3(64), 0, s, d_status);
-        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    }
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (!nframes) return SRPC_OK;
     ReplyAosArgs a{};
     a.prefix = p->d_prefix;

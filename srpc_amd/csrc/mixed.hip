@@ -182,30 +182,17 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack(MixArgs a, const uint8_
     }
 }
 
-__global__ void k_mixed_reset_status(srpc_unpack_status* st) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        st->flags = 0;
-        st->reserved = 0;
-        st->first_bad_record = ~0ull;
-    }
-}
-
 }  // namespace
 
 int mix_index_launch(const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* table, uint64_t* d_counts,
                      srpc_unpack_status* d_status, hipStream_t s) {
     const uint64_t rows = mix_rows(ncalls);
-    if (d_status) hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (rows)
         launch(k_mixed_hist, dim3(static_cast<uint32_t>(mix_super_rows(rows))), dim3(kBlock), 0, s, d_method, ncalls,
                static_cast<uint32_t>(nplans), table, rows, d_status);
     launch(k_mixed_scan, dim3(1), dim3(kMixScanBlock), 0, s, table + rows * (nplans + 1), mix_super_rows(rows),
            static_cast<uint32_t>(nplans + 1), d_counts);
-    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
-}
-
-int mix_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s) {
-    hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
 
@@ -216,7 +203,7 @@ using namespace srpc_impl;
 extern "C" {
 
 int srpc_frames_mixed_index_bytes(uint64_t ncalls, int nplans, uint64_t* out) {
-    if (!out || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32)) return SRPC_E_INVALID;
+    if (!out || mix_nplans_bad(nplans) || past_u32(ncalls)) return SRPC_E_INVALID;
     *out = mix_index_bytes(ncalls, nplans);
     return SRPC_OK;
 }
@@ -224,7 +211,7 @@ int srpc_frames_mixed_index_bytes(uint64_t ncalls, int nplans, uint64_t* out) {
 int srpc_frames_mixed_index(const uint8_t* d_method, uint64_t ncalls, int nplans, void* d_index, uint64_t index_bytes,
                             uint64_t* d_counts, srpc_unpack_status* d_status, void* stream) {
     const TimedCall timed;
-    if (!d_index || !d_counts || (ncalls && !d_method) || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32))
+    if (any_null(d_index, d_counts) || (ncalls && !d_method) || mix_nplans_bad(nplans) || past_u32(ncalls))
         return SRPC_E_INVALID;
     if (!aligned(d_index, 8) || !aligned(d_counts, 8)) return SRPC_E_ALIGN;
     if (index_bytes < mix_index_bytes(ncalls, nplans)) return SRPC_E_CAPACITY;
@@ -234,7 +221,7 @@ int srpc_frames_mixed_index(const uint8_t* d_method, uint64_t ncalls, int nplans
 
 int srpc_frames_mixed_ranks(const void* d_index, const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* d_rank,
                             void* stream) {
-    if (!d_index || (ncalls && (!d_method || !d_rank)) || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32))
+    if (!d_index || (ncalls && any_null(d_method, d_rank)) || mix_nplans_bad(nplans) || past_u32(ncalls))
         return SRPC_E_INVALID;
     if (!aligned(d_index, 8) || !aligned(d_rank, 4)) return SRPC_E_ALIGN;
     if (!ncalls) return SRPC_OK;
@@ -245,7 +232,7 @@ int srpc_frames_mixed_ranks(const void* d_index, const uint8_t* d_method, uint64
 }
 
 int srpc_frames_mixed_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile) {
-    if (!plans || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    if (any_null(plans, calls_per_tile) || mix_nplans_bad(nplans)) return SRPC_E_INVALID;
     uint32_t fmax = 0;
     if (int rc = mix_plans_ok(plans, nplans, 4, &fmax)) return rc;
     *calls_per_tile = mix_tile(fmax);
@@ -258,8 +245,8 @@ int srpc_frames_pack_requests_mixed(const srpc_plan* const* req_plans, int nplan
                                     uint32_t* d_offs, srpc_unpack_status* d_status, void* stream) {
     const TimedCall timed;
     // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_cols || !h_cap || !d_index || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32) ||
-        (ncalls && (!d_method || !d_out)))
+    if (any_null(req_plans, d_cols, h_cap, d_index) || mix_nplans_bad(nplans) || past_u32(ncalls) ||
+        (ncalls && any_null(d_method, d_out)))
         return SRPC_E_INVALID;
     uint32_t fmax = 0;
     if (int rc = mix_plans_ok(req_plans, nplans, 4, &fmax)) return rc;
@@ -281,9 +268,9 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
                                      void* const* const* d_cols, const uint64_t* h_first, const uint64_t* h_cap,
                                      uint8_t* d_codes, srpc_unpack_status* d_status, void* stream) {
     const TimedCall timed;
-    if (!reply_plans || !d_cols || !h_cap || !d_index || !d_codes || nplans <= 0 || nplans > kMixPlans ||
-        nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) || (ncalls && !d_method) ||
-        (nframes && (!d_buf || !d_offs)))
+    if (any_null(reply_plans, d_cols, h_cap, d_index, d_codes) ||
+        mix_nplans_bad(nplans) || nframes > ncalls || past_u32(buf_len) || past_u32(ncalls) ||
+        (ncalls && !d_method) || (nframes && any_null(d_buf, d_offs)))
         return SRPC_E_INVALID;
     uint32_t fmax = 0;
     if (int rc = mix_plans_ok(reply_plans, nplans, 5, &fmax)) return rc;
@@ -294,10 +281,7 @@ int srpc_frames_unpack_replies_mixed(const srpc_plan* const* reply_plans, int np
                           &a, &tb))
         return rc;
     auto s = static_cast<hipStream_t>(stream);
-    if (d_status) {
-        hipLaunchKernelGGL(k_mixed_reset_status, dim3(1), dim3(64), 0, s, d_status);
-        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    }
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (!ncalls) return SRPC_OK;
     const uint32_t grid = static_cast<uint32_t>((ncalls + a.T - 1) / a.T);
     launch(k_mixed_unpack, dim3(grid), dim3(kBlock), a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u) + tb, s, a, d_method,

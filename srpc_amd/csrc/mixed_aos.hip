@@ -118,14 +118,6 @@ __global__ __launch_bounds__(kBlock) void k_mixed_unpack_aos(MixArgs a, MixAos x
     mix_aos_store<true>(sl, d, K, r, good, j, img, lo, pos, slot, dsc, buf);
 }
 
-__global__ void k_mixed_aos_reset_status(srpc_unpack_status* st) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        st->flags = 0;
-        st->reserved = 0;
-        st->first_bad_record = ~0ull;
-    }
-}
-
 }  // namespace
 }  // namespace srpc_impl
 
@@ -135,7 +127,7 @@ extern "C" {
 
 int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                         uint64_t* out) {
-    if (!plans || !h_stride || !out || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    if (any_null(plans, h_stride, out) || mix_nplans_bad(nplans)) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] == 0) return SRPC_E_INVALID;
     uint32_t fmax = 0;
@@ -148,7 +140,7 @@ int srpc_frames_mixed_aos_scratch_bytes(const srpc_plan* const* plans, int nplan
 
 int srpc_frames_mixed_aos_tile(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride,
                                uint32_t* calls_per_tile) {
-    if (!plans || !h_stride || !calls_per_tile || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
+    if (any_null(plans, h_stride, calls_per_tile) || mix_nplans_bad(nplans)) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
         if (h_stride[k] == 0) return SRPC_E_INVALID;
     uint32_t fmax = 0;
@@ -166,8 +158,8 @@ int srpc_frames_pack_requests_mixed_aos(const srpc_plan* const* req_plans, int n
                                         uint32_t* d_offs, srpc_unpack_status* d_status, void* stream) {
     const TimedCall timed;
     // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_recs || !h_stride || !h_leaf_offs || !h_cap || !d_index || nplans <= 0 || nplans > kMixPlans ||
-        ncalls >= (1ull << 32) || (ncalls && (!d_method || !d_out)))
+    if (any_null(req_plans, d_recs, h_stride, h_leaf_offs, h_cap, d_index) ||
+        mix_nplans_bad(nplans) || past_u32(ncalls) || (ncalls && any_null(d_method, d_out)))
         return SRPC_E_INVALID;
     if (aos_args_invalid(d_recs, h_stride, h_leaf_offs, h_first, h_cap, nplans)) return SRPC_E_INVALID;
     uint32_t fmax = 0;
@@ -175,8 +167,7 @@ int srpc_frames_pack_requests_mixed_aos(const srpc_plan* const* req_plans, int n
     for (int k = 0; k < nplans; ++k)
         if (int rc = aos_leaves_ok(req_plans[k], h_leaf_offs[k], h_stride[k])) return rc;
     if (!aligned(d_out, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4)) return SRPC_E_ALIGN;
-    for (int k = 0; k < nplans; ++k)
-        if (!aligned(d_recs[k], 16) || !aos_layout_aligned(req_plans[k], h_leaf_offs[k], h_stride[k])) return SRPC_E_ALIGN;
+    if (!aos_recs_aligned(req_plans, nplans, d_recs, h_stride, h_leaf_offs)) return SRPC_E_ALIGN;
     AosCols cols;
     aos_cols(req_plans, nplans, d_recs, h_leaf_offs, &cols);
     MixArgs a{};
@@ -201,9 +192,9 @@ int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, in
                                          srpc_unpack_status* d_status, void* d_scratch, uint64_t scratch_bytes,
                                          void* stream) {
     const TimedCall timed;
-    if (!reply_plans || !d_recs || !h_stride || !h_leaf_offs || !h_fill || !h_cap || !d_index || !d_codes || !d_scratch ||
-        nplans <= 0 || nplans > kMixPlans || nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) ||
-        (ncalls && !d_method) || (nframes && (!d_buf || !d_offs)))
+    if (any_null(reply_plans, d_recs, h_stride, h_leaf_offs, h_fill, h_cap, d_index, d_codes, d_scratch) ||
+        mix_nplans_bad(nplans) || nframes > ncalls || past_u32(buf_len) || past_u32(ncalls) ||
+        (ncalls && !d_method) || (nframes && any_null(d_buf, d_offs)))
         return SRPC_E_INVALID;
     if (aos_args_invalid(d_recs, h_stride, h_leaf_offs, h_first, h_cap, nplans)) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
@@ -217,9 +208,7 @@ int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, in
     MixAos x{};
     if (int rc = aos_describe(reply_plans, nplans, d_recs, h_stride, h_leaf_offs, h_fill, &desc, &x)) return rc;
     if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_offs, 4) || !aligned(d_scratch, 16)) return SRPC_E_ALIGN;
-    for (int k = 0; k < nplans; ++k)
-        if (!aligned(d_recs[k], 16) || !aos_layout_aligned(reply_plans[k], h_leaf_offs[k], h_stride[k]))
-            return SRPC_E_ALIGN;
+    if (!aos_recs_aligned(reply_plans, nplans, d_recs, h_stride, h_leaf_offs)) return SRPC_E_ALIGN;
     if (scratch_bytes < x.desc_bytes) return SRPC_E_CAPACITY;
     AosCols cols;
     aos_cols(reply_plans, nplans, d_recs, h_leaf_offs, &cols);
@@ -229,10 +218,7 @@ int srpc_frames_unpack_replies_mixed_aos(const srpc_plan* const* reply_plans, in
     a.T = mix_aos_tile(fmax, x.desc_bytes);
     a.img = (a.T * fmax + 16 + 15) & ~15u;
     auto s = static_cast<hipStream_t>(stream);
-    if (d_status) {
-        hipLaunchKernelGGL(k_mixed_aos_reset_status, dim3(1), dim3(64), 0, s, d_status);
-        if (hipGetLastError() != hipSuccess) return SRPC_E_HIP;
-    }
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (!ncalls) return SRPC_OK;
     if (int rc = mix_upload(desc.bytes, x.desc_bytes, d_scratch, s)) return rc;
     const uint32_t grid = static_cast<uint32_t>((ncalls + a.T - 1) / a.T);

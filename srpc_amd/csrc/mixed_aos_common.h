@@ -25,10 +25,14 @@ struct MixAos {
     uint32_t desc_bytes;          // tables and fills (a multiple of 16)
 };
 
-// Table and fill bytes of the plans' strides: 2 S16 + S16 + 16 each.
+// Table and fill bytes of the plans' strides: 2 S16 + S16 + 16 each.  A plan
+// without a table is skipped, here and in aos_describe: stride 0 (a column plan
+// of mixed_legs_common.h) or above kAosMaxStride (a pack's: decodes refuse it).
+inline bool aos_has_table(uint64_t stride) { return stride && stride <= kAosMaxStride; }
 inline uint32_t aos_desc_bytes(const uint64_t* h_stride, int nplans) {
     uint32_t b = 0;
-    for (int k = 0; k < nplans; ++k) b += 3 * s16_of(static_cast<uint32_t>(h_stride[k])) + 16;
+    for (int k = 0; k < nplans; ++k)
+        if (aos_has_table(h_stride[k])) b += 3 * s16_of(static_cast<uint32_t>(h_stride[k])) + 16;
     return b;
 }
 
@@ -59,6 +63,15 @@ inline int aos_leaves_ok(const srpc_plan* p, const uint32_t* offs, uint64_t stri
     return SRPC_OK;
 }
 
+// Every struct array (h_stride[k] != 0) on a 16-byte boundary, its layout naturally aligned.
+inline bool aos_recs_aligned(const srpc_plan* const* plans, int nplans, const void* const* d_recs,
+                             const uint64_t* h_stride, const uint32_t* const* h_leaf_offs) {
+    for (int k = 0; k < nplans; ++k)
+        if (h_stride[k] && (!aligned(d_recs[k], 16) || !aos_layout_aligned(plans[k], h_leaf_offs[k], h_stride[k])))
+            return false;
+    return true;
+}
+
 // Each leaf's address inside element 0 of its plan's array, as mix_args's columns.
 struct AosCols {
     const void* leaf[kMixFields];
@@ -75,9 +88,9 @@ inline void aos_cols(const srpc_plan* const* plans, int nplans, const void* cons
     }
 }
 
-// The tables and the fills of plans with strides <= kAosMaxStride, as they will
-// lie in scratch and in LDS, and the kernel's view of them.  SRPC_E_INVALID: a
-// leaf past its stride, or two leaves sharing a byte.
+// The tables and the fills of the plans that have them, as they will lie in
+// scratch and in LDS, and the kernel's view of them (*x comes in zeroed: a plan
+// without a table keeps stride 0).  SRPC_E_INVALID: as aos_sources.
 struct AosDesc {
     alignas(16) uint8_t bytes[kMixPlans * (3 * kAosMaxStride + 16)];
 };
@@ -88,6 +101,7 @@ inline int aos_describe(const srpc_plan* const* plans, int nplans, void* const* 
     x->desc_bytes = aos_desc_bytes(h_stride, nplans);
     uint32_t at = 0;
     for (int k = 0; k < nplans; ++k) {
+        if (!aos_has_table(h_stride[k])) continue;
         const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
         int32_t from[kAosMaxStride];
         if (int rc = aos_sources(plans[k], h_leaf_offs[k], stride, from)) return rc;
@@ -96,6 +110,7 @@ inline int aos_describe(const srpc_plan* const* plans, int nplans, void* const* 
         at += 2 * s16_of(stride);
     }
     for (int k = 0; k < nplans; ++k) {
+        if (!aos_has_table(h_stride[k])) continue;
         const uint32_t stride = static_cast<uint32_t>(h_stride[k]);
         std::memcpy(desc->bytes + at, h_fill[k], stride);
         x->fill[k] = static_cast<uint16_t>(at);

@@ -444,12 +444,16 @@ __device__ __forceinline__ MixReply mix_judge(const MixLds& d, const MixLane& r,
     return y;
 }
 
+// What every mixed call checks of its arguments before a plan is read (SRPC_E_INVALID).
+template <class... P>
+inline bool any_null(const P*... p) { return (... || !p); }
+inline bool past_u32(uint64_t v) { return v >= (1ull << 32); }
+inline bool mix_nplans_bad(int nplans) { return nplans <= 0 || nplans > kMixPlans; }
+
 // mixed.hip: the index over ncalls method bytes (k_mixed_hist, k_mixed_scan;
-// ids >= nplans land in column nplans), d_status reset and flagged when given;
-// and the status reset alone.
+// ids >= nplans land in column nplans), d_status reset and flagged when given.
 int mix_index_launch(const uint8_t* d_method, uint64_t ncalls, int nplans, uint32_t* table, uint64_t* d_counts,
                      srpc_unpack_status* d_status, hipStream_t s);
-int mix_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
 
 // mixed_req.hip: the classify pass of the server-side decodes over fixed-size
 // plans (a.T = mix_tile: the column call's tile), nframes > 0.

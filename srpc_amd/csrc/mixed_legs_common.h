@@ -2,7 +2,7 @@
 // both kinds share (mixed_legs.hip: the client's request pack and reply decode;
 // mixed_req_legs.hip: the server's request decode): which plans are record
 // plans (h_stride[k] != 0), the checks of their arguments, their leaves as
-// columns of MvDesc, and where their tables and fills lie in scratch.
+// columns of MvDesc, their description (legs_describe) and its place in scratch.
 #pragma once
 
 #include <algorithm>
@@ -12,40 +12,20 @@
 #include "mixed_aos_common.h"
 #include "mixed_common.h"
 #include "mixed_var_common.h"
+#include "mixed_var_tile.h"
 #include "plan.h"
 #include "srpc_gpu.h"
 
 namespace srpc_impl {
 
-// The record plans of a call, compacted: what aos_describe and aos_desc_bytes take.
-struct LegRecs {
-    int n = 0;
-    int plan[kMixPlans];  // record plan r is plan plan[r]
-    const srpc_plan* plans[kMixPlans];
-    void* recs[kMixPlans];
-    uint64_t stride[kMixPlans];
-    const uint32_t* leaf_offs[kMixPlans];
-    const void* fill[kMixPlans];
-};
-
-inline void leg_recs(const srpc_plan* const* plans, int nplans, void* const* d_recs, const uint64_t* h_stride,
-                     const uint32_t* const* h_leaf_offs, const void* const* h_fill, LegRecs* out) {
-    for (int k = 0; k < nplans; ++k) {
-        if (!h_stride[k]) continue;
-        const int r = out->n++;
-        out->plan[r] = k;
-        out->plans[r] = plans[k];
-        out->recs[r] = d_recs[k];
-        out->stride[r] = h_stride[k];
-        out->leaf_offs[r] = h_leaf_offs[k];
-        out->fill[r] = h_fill ? h_fill[k] : nullptr;
-    }
-}
+// h_stride of a call without record arguments: every plan in columns.
+constexpr uint64_t kAllColumns[kMixPlans] = {};
 
 // What is checked of the struct-array arguments before any plan is read.
 inline bool legs_args_invalid(const void* const* d_recs, const uint64_t* h_stride, const uint32_t* const* h_leaf_offs,
                               const void* const* h_fill, bool decode, const uint64_t* h_first, const uint64_t* h_cap,
                               int nplans) {
+    if (any_null(d_recs, h_stride, h_leaf_offs) || (decode && !h_fill)) return true;
     for (int k = 0; k < nplans; ++k) {
         if (h_stride[k] >= (1ull << 32)) return true;
         if (!h_stride[k]) continue;
@@ -62,6 +42,15 @@ inline int legs_plans_ok(const srpc_plan* const* plans, int nplans, const uint64
         if (h_stride && h_stride[k] && (plans[k]->has_string || (decode && h_stride[k] > kAosMaxStride)))
             return SRPC_E_UNSUPPORTED;
     return SRPC_OK;
+}
+
+// The plans of a size query into d's layout part (h_stride may be nullptr: no record plan).
+inline int legs_query_plans(const srpc_plan* const* plans, int nplans, const uint64_t* h_stride, bool decode,
+                            MvDesc* d) {
+    for (int k = 0; h_stride && k < nplans; ++k)
+        if (past_u32(h_stride[k])) return SRPC_E_INVALID;
+    if (int rc = mv_plans(plans, nplans, 4, d)) return rc;
+    return legs_plans_ok(plans, nplans, h_stride, decode);
 }
 
 // The record plans' leaves as columns of d: each leaf's address inside element 0.
@@ -86,5 +75,28 @@ inline uint32_t legs_fmax(const MvDesc& d) {
 }
 
 inline uint64_t legs_tables_at(const MvScratch& sc) { return (sc.bytes + 15) & ~15ull; }
+
+// A decode's image window and tile once desc_bytes of tables and fills share the image's budget.
+inline void legs_window(uint32_t desc_bytes, MvDesc* d, MvLegs* x) {
+    x->x.desc_bytes = desc_bytes;
+    x->window = kMixImage - desc_bytes;
+    d->T = mix_tile(legs_fmax(*d), x->window);
+}
+
+// The record plans of a decode, described (mv_plans and legs_plans_ok have
+// passed): their tables and fills as they will lie in scratch and in LDS, the
+// kernel's argument, and in *d the tile that the window they leave allows.
+struct LegsTables {
+    AosDesc desc;
+    MvLegs x{};  // x.x.desc_bytes == 0: no record plan, the batch is the column-only parse kernel's
+};
+
+inline int legs_describe(const srpc_plan* const* plans, int nplans, void* const* d_recs, const uint64_t* h_stride,
+                         const uint32_t* const* h_leaf_offs, const void* const* h_fill, MvDesc* d, LegsTables* t) {
+    if (aos_desc_bytes(h_stride, nplans))
+        if (int rc = aos_describe(plans, nplans, d_recs, h_stride, h_leaf_offs, h_fill, &t->desc, &t->x.x)) return rc;
+    legs_window(t->x.x.desc_bytes, d, &t->x);
+    return SRPC_OK;
+}
 
 }  // namespace srpc_impl

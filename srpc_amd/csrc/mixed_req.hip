@@ -154,8 +154,9 @@ int srpc_frames_unpack_requests_mixed(const srpc_plan* const* req_plans, int npl
                                       srpc_unpack_status* d_status, void* stream) {
     const TimedCall timed;
     // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_cols || !h_cap || !d_index || !d_counts || nplans <= 0 || nplans > kMixPlans ||
-        buf_len >= (1ull << 32) || nframes >= (1ull << 32) || (nframes && (!d_buf || !d_offs || !d_class)))
+    if (any_null(req_plans, d_cols, h_cap, d_index, d_counts) ||
+        mix_nplans_bad(nplans) || past_u32(buf_len) || past_u32(nframes) ||
+        (nframes && any_null(d_buf, d_offs, d_class)))
         return SRPC_E_INVALID;
     uint32_t fmax = 0;
     if (int rc = mix_plans_ok(req_plans, nplans, 4, &fmax)) return rc;
@@ -168,8 +169,7 @@ int srpc_frames_unpack_requests_mixed(const srpc_plan* const* req_plans, int npl
     if (index_bytes < mix_index_bytes(nframes, nplans)) return SRPC_E_CAPACITY;
     auto s = static_cast<hipStream_t>(stream);
     auto* table = static_cast<uint32_t*>(d_index);
-    if (d_status)
-        if (int rc = mix_status_reset_launch(d_status, s)) return rc;
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     const uint32_t grid = static_cast<uint32_t>((nframes + a.T - 1) / a.T);
     const uint32_t lds = a.img + 32 + ((4 * (a.T + 1) + 7) & ~7u);
     if (nframes) req_classify_launch(a, tb, d_buf, buf_len, d_offs, nframes, d_class, s);

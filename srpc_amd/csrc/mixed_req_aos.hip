@@ -129,9 +129,9 @@ int srpc_frames_unpack_requests_mixed_aos(const srpc_plan* const* req_plans, int
                                           void* stream) {
     const TimedCall timed;
     // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_recs || !h_stride || !h_leaf_offs || !h_fill || !h_cap || !d_index || !d_counts || !d_scratch ||
-        nplans <= 0 || nplans > kMixPlans || buf_len >= (1ull << 32) || nframes >= (1ull << 32) ||
-        (nframes && (!d_buf || !d_offs || !d_class)))
+    if (any_null(req_plans, d_recs, h_stride, h_leaf_offs, h_fill, h_cap, d_index, d_counts, d_scratch) ||
+        mix_nplans_bad(nplans) || past_u32(buf_len) || past_u32(nframes) ||
+        (nframes && any_null(d_buf, d_offs, d_class)))
         return SRPC_E_INVALID;
     if (aos_args_invalid(d_recs, h_stride, h_leaf_offs, h_first, h_cap, nplans)) return SRPC_E_INVALID;
     for (int k = 0; k < nplans; ++k)
@@ -147,8 +147,7 @@ int srpc_frames_unpack_requests_mixed_aos(const srpc_plan* const* req_plans, int
     if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_counts, 8) || !aligned(d_offs, 4) ||
         !aligned(d_scratch, 16))
         return SRPC_E_ALIGN;
-    for (int k = 0; k < nplans; ++k)
-        if (!aligned(d_recs[k], 16) || !aos_layout_aligned(req_plans[k], h_leaf_offs[k], h_stride[k])) return SRPC_E_ALIGN;
+    if (!aos_recs_aligned(req_plans, nplans, d_recs, h_stride, h_leaf_offs)) return SRPC_E_ALIGN;
     if (index_bytes < mix_index_bytes(nframes, nplans) || scratch_bytes < x.desc_bytes) return SRPC_E_CAPACITY;
     AosCols cols;
     aos_cols(req_plans, nplans, d_recs, h_leaf_offs, &cols);
@@ -160,8 +159,7 @@ int srpc_frames_unpack_requests_mixed_aos(const srpc_plan* const* req_plans, int
     b.img = (b.T * fmax + 16 + 15) & ~15u;
     auto s = static_cast<hipStream_t>(stream);
     auto* table = static_cast<uint32_t*>(d_index);
-    if (d_status)
-        if (int rc = mix_status_reset_launch(d_status, s)) return rc;
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
     if (int rc = mix_upload(desc.bytes, x.desc_bytes, d_scratch, s)) return rc;
     if (nframes) req_classify_launch(a, tb, d_buf, buf_len, d_offs, nframes, d_class, s);
     // unknown frames (0xFF) are ids >= K: column K of the index; no status here

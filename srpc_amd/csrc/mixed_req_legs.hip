@@ -1,17 +1,18 @@
-// mixed_req_legs.hip -- a batch of request frames of several methods decoded in
-// arrival order, each plan's requests into columns (fixed-size or string plans,
-// as mixed_req_var.hip takes them) or into one device array of the caller's own
-// structs (fixed-size plans, as mixed_req_aos.hip takes them), any combination
-// in one batch (server side; srpc_frames_unpack_requests_mixed_legs of
-// include/srpc_gpu.h): the server's mirror of mixed_legs.hip's request pack.
-// Plan k is a record plan exactly when h_stride[k] != 0.
+// mixed_req_legs.hip -- the server's string-aware decode of a batch of request
+// frames of several methods in arrival order: one host path
+// (mv_unpack_requests), the mirror of mixed_legs.hip's request pack.  The entry
+// points of include/srpc_gpu.h are adapters over it:
+// srpc_frames_unpack_requests_mixed_legs, where a plan's requests go into
+// columns (fixed-size or string plans) or into one device array of the caller's
+// own structs (fixed-size plans; a record plan: h_stride[k] != 0), and
+// srpc_frames_unpack_requests_mixed_var, which has no record arguments.
 //
 // Nothing here is a second implementation.  The description of the plans, the
 // scratch, the slot scan and the char copy are mixed_var.hip's
 // (mixed_var_common.h); the record plans' checks, tables and fills are
-// mixed_legs.hip's (mixed_legs_common.h); the classify pass is
-// mixed_req_var.hip's k_mrv_classify and the index mixed.hip's, so d_class,
-// d_index and d_counts are that call's whatever the plans' kinds.
+// mixed_legs_common.h's; the classify pass is mixed_req_var.hip's
+// k_mrv_classify and the index mixed.hip's, so d_class, d_index and d_counts
+// are the same whatever the plans' kinds.
 //
 //   k_mrl_parse   k_mrv_parse's tile -- the offsets, the granule's ranks from the
 //       index, the span staged into the image -- with the record half of
@@ -24,12 +25,8 @@
 //       slices of the tile as whole 16-byte pieces, non-temporally
 //       (mix_aos_slices_*, mix_aos_store of mixed_aos_common.h).
 //
-// A batch without a record plan is mixed_req_var.hip's problem and launches its
-// kernel (mrv_parse_launch): a kind-aware kernel keeps more scalars live across
-// the slice steps and is slower for column lanes too (see k_ml_parse).
-//
-// Scratch: mixed_legs.hip's layout: mv_scratch, rounded up to 16 bytes, then the
-// record plans' tables and fills.
+// A batch without a record plan launches k_mrv_parse itself (mrv_parse_launch),
+// for k_ml_parse's reason.  Scratch: mixed_legs.hip's layout.
 // LDS of k_mrl_parse: image[W + 16] | tables and fills [desc_bytes],
 // W = kMixImage - desc_bytes: the dynamic LDS of k_mrv_parse; then static wcnt,
 // the tile's offsets, pos[], slot[] and the slices.
@@ -113,6 +110,64 @@ __global__ __launch_bounds__(kBlock) void k_mrl_parse(const MvDesc* __restrict__
     mix_aos_store<true>(sl, *d, K, r, rec, j, img, lo, pos, slot, dsc, buf);
 }
 
+// The request decode: `legs` as at mv_pack_requests (mixed_legs.hip).
+int mv_unpack_requests(bool legs, const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
+                       uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes, void* const* const* d_cols,
+                       uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap, void* const* d_recs,
+                       const uint64_t* h_stride, const uint32_t* const* h_leaf_offs, const void* const* h_fill,
+                       const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_class, void* d_index,
+                       uint64_t index_bytes, uint64_t* d_counts, uint64_t* d_ends, srpc_unpack_status* d_status,
+                       void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    const TimedCall timed;
+    if (any_null(req_plans, d_cols, d_str_offs, h_str_cap, h_cap, d_index, d_counts, d_ends, d_scratch) ||
+        mix_nplans_bad(nplans) || past_u32(buf_len) || past_u32(nframes) ||
+        (nframes && any_null(d_buf, d_offs, d_class)))
+        return SRPC_E_INVALID;
+    if (legs && legs_args_invalid(d_recs, h_stride, h_leaf_offs, h_fill, true, h_first, h_cap, nplans))
+        return SRPC_E_INVALID;
+    if (!legs) h_stride = kAllColumns;
+    static thread_local MvDesc d;
+    d = MvDesc{};
+    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
+    if (int rc = legs_plans_ok(req_plans, nplans, h_stride, true)) return rc;
+    LegsTables t;  // d.T, for both passes: srpc_frames_mixed_legs_tile's
+    if (int rc = legs_describe(req_plans, nplans, d_recs, h_stride, h_leaf_offs, h_fill, &d, &t)) return rc;
+    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_counts, 8) || !aligned(d_ends, 8) ||
+        !aligned(d_scratch, legs ? 16 : 8) || !aligned(d_offs, 4) ||
+        !aos_recs_aligned(req_plans, nplans, d_recs, h_stride, h_leaf_offs))
+        return SRPC_E_ALIGN;
+    if (int rc = mv_cols(req_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
+                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d,
+                         h_stride))
+        return rc;
+    legs_cols(req_plans, nplans, d_recs, h_stride, h_leaf_offs, &d);
+    const MvScratch sc = mv_scratch(d, nframes);
+    const uint64_t tables_at = legs_tables_at(sc);
+    if (index_bytes < mix_index_bytes(nframes, nplans) ||
+        scratch_bytes < (legs ? tables_at + t.x.x.desc_bytes : sc.bytes))
+        return SRPC_E_CAPACITY;
+    auto s = static_cast<hipStream_t>(stream);
+    const MvCarve c(d_scratch, sc);
+    auto* tables = static_cast<uint8_t*>(d_scratch) + tables_at;
+    auto* table = static_cast<uint32_t*>(d_index);
+    const uint64_t rows = mix_rows(nframes);
+    if (d_status && status_reset_launch(d_status, s)) return SRPC_E_HIP;
+    if (int rc = mix_upload(&d, sizeof d, d_scratch, s)) return rc;
+    if (t.x.x.desc_bytes)
+        if (int rc = mix_upload(t.desc.bytes, t.x.x.desc_bytes, tables, s)) return rc;
+    if (nframes) mrv_classify_launch(d, c.dd, d_buf, buf_len, d_offs, nframes, d_class, s);
+    // unknown frames (0xFF) are ids >= K: column K of the index; no status here
+    if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
+    // without a record plan the kernel is mixed_req_var.hip's
+    if (nframes && !t.x.x.desc_bytes)
+        mrv_parse_launch(d, c.dd, d_class, table, rows, d_buf, buf_len, d_offs, nframes, c.srcs, c.counts, d_status, s);
+    else if (nframes)
+        launch(k_mrl_parse, dim3(static_cast<uint32_t>((nframes + d.T - 1) / d.T)), dim3(kBlock), kMixImage + 16, s, c.dd,
+               t.x, reinterpret_cast<const uint4*>(tables), static_cast<const uint8_t*>(d_class),
+               static_cast<const uint32_t*>(table), rows, d_buf, buf_len, d_offs, nframes, c.srcs, c.counts, d_status);
+    return mv_strings_launch(d, c, sc.nb, d_class, table, nframes, d_buf, d_ends, s);
+}
+
 }  // namespace
 }  // namespace srpc_impl
 
@@ -129,79 +184,21 @@ int srpc_frames_unpack_requests_mixed_legs(const srpc_plan* const* req_plans, in
                                            uint8_t* d_class, void* d_index, uint64_t index_bytes, uint64_t* d_counts,
                                            uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
                                            uint64_t scratch_bytes, void* stream) {
-    const TimedCall timed;
-    // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_cols || !d_str_offs || !h_str_cap || !d_recs || !h_stride || !h_leaf_offs || !h_fill ||
-        !h_cap || !d_index || !d_counts || !d_ends || !d_scratch || nplans <= 0 || nplans > kMixPlans ||
-        buf_len >= (1ull << 32) || nframes >= (1ull << 32) || (nframes && (!d_buf || !d_offs || !d_class)))
-        return SRPC_E_INVALID;
-    if (legs_args_invalid(d_recs, h_stride, h_leaf_offs, h_fill, true, h_first, h_cap, nplans)) return SRPC_E_INVALID;
-    static thread_local MvDesc d;
-    d = MvDesc{};
-    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
-    if (int rc = legs_plans_ok(req_plans, nplans, h_stride, true)) return rc;
-    // the record plans' tables and fills, as they will lie in scratch and in LDS
-    LegRecs lr;
-    leg_recs(req_plans, nplans, d_recs, h_stride, h_leaf_offs, h_fill, &lr);
-    AosDesc desc;
-    MixAos xr{};
-    if (lr.n)
-        if (int rc = aos_describe(lr.plans, lr.n, lr.recs, lr.stride, lr.leaf_offs, lr.fill, &desc, &xr)) return rc;
-    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_counts, 8) || !aligned(d_ends, 8) ||
-        !aligned(d_scratch, 16) || !aligned(d_offs, 4))
-        return SRPC_E_ALIGN;
-    for (int k = 0; k < nplans; ++k)
-        if (h_stride[k] && (!aligned(d_recs[k], 16) || !aos_layout_aligned(req_plans[k], h_leaf_offs[k], h_stride[k])))
-            return SRPC_E_ALIGN;
-    if (int rc = mv_cols(req_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
-                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d,
-                         h_stride))
-        return rc;
-    legs_cols(req_plans, nplans, d_recs, h_stride, h_leaf_offs, &d);
-    MvLegs x{};
-    for (int r = 0; r < lr.n; ++r) {
-        const int k = lr.plan[r];
-        x.x.recs[k] = xr.recs[r];
-        x.x.stride[k] = xr.stride[r];
-        x.x.tab[k] = xr.tab[r];
-        x.x.fill[k] = xr.fill[r];
-    }
-    x.x.desc_bytes = xr.desc_bytes;
-    x.window = kMixImage - xr.desc_bytes;
-    d.T = mix_tile(legs_fmax(d), x.window);  // both passes: srpc_frames_mixed_legs_tile's
-    const MvScratch sc = mv_scratch(d, nframes);
-    const uint64_t tables_at = legs_tables_at(sc);
-    if (index_bytes < mix_index_bytes(nframes, nplans) || scratch_bytes < tables_at + xr.desc_bytes)
-        return SRPC_E_CAPACITY;
-    auto s = static_cast<hipStream_t>(stream);
-    auto* base = static_cast<uint8_t*>(d_scratch);
-    const auto* dd = reinterpret_cast<const MvDesc*>(base);
-    auto* counts = reinterpret_cast<uint32_t*>(base + sc.counts);
-    auto* partial = reinterpret_cast<uint64_t*>(base + sc.partial);
-    auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
-    auto* table = static_cast<uint32_t*>(d_index);
-    const uint64_t rows = mix_rows(nframes);
-    if (d_status)
-        if (int rc = mix_status_reset_launch(d_status, s)) return rc;
-    if (int rc = mv_upload(d, d_scratch, s)) return rc;
-    if (xr.desc_bytes)
-        if (int rc = mix_upload(desc.bytes, xr.desc_bytes, base + tables_at, s)) return rc;
-    if (nframes) mrv_classify_launch(d, dd, d_buf, buf_len, d_offs, nframes, d_class, s);
-    // unknown frames (0xFF) are ids >= K: column K of the index; no status here
-    if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
-    // without a record plan the batch is mixed_req_var.hip's, and so is the kernel
-    if (nframes && !lr.n)
-        mrv_parse_launch(d, dd, d_class, table, rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status, s);
-    else if (nframes)
-        launch(k_mrl_parse, dim3(static_cast<uint32_t>((nframes + d.T - 1) / d.T)), dim3(kBlock), kMixImage + 16, s, dd, x,
-               reinterpret_cast<const uint4*>(base + tables_at), static_cast<const uint8_t*>(d_class),
-               static_cast<const uint32_t*>(table), rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status);
-    if (d.nslots) {
-        mv_slots_launch(d, dd, counts, nframes, partial, sc.nb, d_ends, s);
-        if (nframes)
-            mv_copy_launch(dd, d_class, static_cast<const uint32_t*>(table), rows, nframes, d_buf, srcs, s);
-    }
-    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
+    return mv_unpack_requests(true, req_plans, nplans, d_buf, buf_len, d_offs, nframes, d_cols, d_str_offs,
+                              h_str_cap, d_recs, h_stride, h_leaf_offs, h_fill, h_first, h_cap, d_class, d_index,
+                              index_bytes, d_counts, d_ends, d_status, d_scratch, scratch_bytes, stream);
+}
+
+int srpc_frames_unpack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
+                                          uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
+                                          void* const* const* d_cols, uint64_t* const* const* d_str_offs,
+                                          const uint64_t* const* h_str_cap, const uint64_t* h_first,
+                                          const uint64_t* h_cap, uint8_t* d_class, void* d_index, uint64_t index_bytes,
+                                          uint64_t* d_counts, uint64_t* d_ends, srpc_unpack_status* d_status,
+                                          void* d_scratch, uint64_t scratch_bytes, void* stream) {
+    return mv_unpack_requests(false, req_plans, nplans, d_buf, buf_len, d_offs, nframes, d_cols, d_str_offs,
+                              h_str_cap, nullptr, nullptr, nullptr, nullptr, h_first, h_cap, d_class, d_index, index_bytes,
+                              d_counts, d_ends, d_status, d_scratch, scratch_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 // mixed_req_var.hip -- a batch of request frames of several methods, string-
-// bodied ones included, decoded in arrival order (server side;
-// srpc_frames_unpack_requests_mixed_var of include/srpc_gpu.h): mixed_req.hip's
+// bodied ones included, decoded in arrival order (server side): mixed_req.hip's
 // decode over the two plan kinds of mixed_var.hip, the mirror of that file's
-// request pack.
+// request pack: the two kernels over plans that all lie in columns.  The entry
+// point (srpc_frames_unpack_requests_mixed_var) is an adapter in
+// mixed_req_legs.hip, beside the call's one host path (mv_unpack_requests).
 //
 // The class of a frame is found from the frame itself (srpc_frames_classify's
 // rule); its fields go to element first[k] + rank(i) of plan k's columns, rank(i)
@@ -27,11 +28,10 @@
 //       Every read is bounded by the frame's own extent again: the class is
 //       not trusted to keep the walk inside buf_len.  The lane's frame and its
 //       walk (MrvFrame, mrv_lane_walk) live in mixed_req_var_tile.h, which
-//       mixed_req_legs.hip's parse kernel shares; that file also launches
-//       k_mrv_classify and, for a batch without a record plan, this kernel
-//       (mrv_classify_launch, mrv_parse_launch).
-//   the slot scan and the char copy of mixed_var.hip (mv_slots_launch,
-//       mv_copy_launch) with d_class as the method vector.
+//       mixed_req_legs.hip's parse kernel shares; a batch without a record
+//       plan is this kernel's (mrv_parse_launch).
+//   the slot scan and the char copy of mixed_var.hip (mv_strings_launch) with
+//       d_class as the method vector.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -178,57 +178,3 @@ void mrv_parse_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_class,
 }
 
 }  // namespace srpc_impl
-
-using namespace srpc_impl;
-
-extern "C" {
-
-int srpc_frames_unpack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans, const uint8_t* d_buf,
-                                          uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
-                                          void* const* const* d_cols, uint64_t* const* const* d_str_offs,
-                                          const uint64_t* const* h_str_cap, const uint64_t* h_first,
-                                          const uint64_t* h_cap, uint8_t* d_class, void* d_index, uint64_t index_bytes,
-                                          uint64_t* d_counts, uint64_t* d_ends, srpc_unpack_status* d_status,
-                                          void* d_scratch, uint64_t scratch_bytes, void* stream) {
-    const TimedCall timed;
-    // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_cols || !d_str_offs || !h_str_cap || !h_cap || !d_index || !d_counts || !d_ends || !d_scratch ||
-        nplans <= 0 || nplans > kMixPlans || buf_len >= (1ull << 32) || nframes >= (1ull << 32) ||
-        (nframes && (!d_buf || !d_offs || !d_class)))
-        return SRPC_E_INVALID;
-    static thread_local MvDesc d;
-    d = MvDesc{};
-    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
-    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_counts, 8) || !aligned(d_ends, 8) ||
-        !aligned(d_scratch, 8) || !aligned(d_offs, 4))
-        return SRPC_E_ALIGN;
-    if (int rc = mv_cols(req_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
-                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d))
-        return rc;
-    const MvScratch sc = mv_scratch(d, nframes);
-    if (index_bytes < mix_index_bytes(nframes, nplans) || scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
-    auto s = static_cast<hipStream_t>(stream);
-    auto* base = static_cast<uint8_t*>(d_scratch);
-    const auto* dd = reinterpret_cast<const MvDesc*>(base);
-    auto* counts = reinterpret_cast<uint32_t*>(base + sc.counts);
-    auto* partial = reinterpret_cast<uint64_t*>(base + sc.partial);
-    auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
-    auto* table = static_cast<uint32_t*>(d_index);
-    const uint64_t rows = mix_rows(nframes);
-    if (d_status)
-        if (int rc = mix_status_reset_launch(d_status, s)) return rc;
-    if (int rc = mv_upload(d, d_scratch, s)) return rc;
-    if (nframes) mrv_classify_launch(d, dd, d_buf, buf_len, d_offs, nframes, d_class, s);
-    // unknown frames (0xFF) are ids >= K: column K of the index; no status here
-    if (int rc = mix_index_launch(d_class, nframes, nplans, table, d_counts, nullptr, s)) return rc;
-    if (nframes)
-        mrv_parse_launch(d, dd, d_class, table, rows, d_buf, buf_len, d_offs, nframes, srcs, counts, d_status, s);
-    if (d.nslots) {
-        mv_slots_launch(d, dd, counts, nframes, partial, sc.nb, d_ends, s);
-        if (nframes)
-            mv_copy_launch(dd, d_class, static_cast<const uint32_t*>(table), rows, nframes, d_buf, srcs, s);
-    }
-    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
-}
-
-}  // extern "C"

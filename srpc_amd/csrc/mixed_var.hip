@@ -1,17 +1,16 @@
 // mixed_var.hip -- batches of calls of several methods in caller-given order
-// whose plans may have string fields (client side;
-// srpc_frames_pack_requests_mixed_var, srpc_frames_unpack_replies_mixed_var of
-// include/srpc_gpu.h).  The call index and mix_ranks are those of mixed.hip
-// (mixed_common.h).  Nothing here waits on another workgroup.  The server-side
-// request decode (mixed_req_var.hip) uses this file's description of the plans,
-// its slot scan and its char copy through mixed_var_common.h.
+// whose plans may have string fields, every plan in columns (client side): the
+// kernels, their launches and the host-side builders of the plans' description
+// (mixed_var_common.h).  The entry points (srpc_frames_*_mixed_var of
+// include/srpc_gpu.h) are adapters in mixed_legs.hip, beside the one host path
+// of each call.  The call index and mix_ranks are mixed.hip's (mixed_common.h).
+// Nothing here waits on another workgroup.
 //
-// Both calls first put their description of the plans (MvDesc: columns, offsets
-// arrays, layouts, 5.8 KiB -- more than kernel arguments hold) into scratch with
-// a fixed number of k_mv_upload launches; every later kernel reads it there.
-// The bodies of the two tile kernels, k_mv_pack and k_mv_parse, are
-// mixed_var_tile.h's mv_pack_tile<false> and mv_parse_tile<false>:
-// mixed_legs.hip instantiates the same functions for plans held in struct arrays.
+// The description of the plans (MvDesc: columns, offsets arrays, layouts,
+// 5.8 KiB -- more than kernel arguments hold) goes into scratch with a fixed
+// number of k_mv_upload launches; every later kernel reads it there.  The two
+// tile kernels' bodies are mixed_var_tile.h's mv_pack_tile<false> and
+// mv_parse_tile<false>; mixed_legs.hip instantiates them for struct arrays.
 //
 // Pack:
 //   k_mv_sizes   a workgroup per granule of 256 calls: mix_ranks, each lane's
@@ -60,14 +59,6 @@ struct MvChunk {
 
 __global__ void k_mv_upload(MvChunk c, uint4* dst, uint32_t words) {
     for (uint32_t i = threadIdx.x; i < words; i += blockDim.x) dst[i] = c.w[i];
-}
-
-__global__ void k_mv_reset_status(srpc_unpack_status* st) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        st->flags = 0;
-        st->reserved = 0;
-        st->first_bad_record = ~0ull;
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_mv_sizes(const MvDesc* __restrict__ d, const uint8_t* __restrict__ method,
@@ -243,15 +234,9 @@ __global__ __launch_bounds__(kBlock) void k_mv_copy(const MvDesc* __restrict__ d
     }
 }
 
-// ---- host side ----
-
-inline uint32_t mv_tile(uint32_t fmax) {
-    uint32_t t = kMixGranule;
-    while (t > 16 && t * fmax > kMixImage) t >>= 1;
-    return t;
-}
-
 }  // namespace
+
+// ---- host side ----
 
 // The plans of one side into d's layout part.  min_fixed_prefix: 4 (request) or
 // 5 (reply).
@@ -294,7 +279,7 @@ int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefi
     d->nplans = static_cast<uint32_t>(nplans);
     d->nslots = ns;
     d->maxstr = maxstr;
-    d->T = mv_tile(fmax);
+    d->T = mix_tile(fmax);
     d->tmpl_bytes = tb;
     return SRPC_OK;
 }
@@ -344,8 +329,6 @@ int mix_upload(const void* src, size_t bytes, void* d_scratch, hipStream_t s) {
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
 
-int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s) { return mix_upload(&d, sizeof(MvDesc), d_scratch, s); }
-
 void mv_sizes_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
                      uint64_t* gsum, uint64_t out_cap, uint32_t* d_offs, uint64_t* d_total, hipStream_t s) {
     if (rows)
@@ -368,121 +351,18 @@ void mv_parse_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_method,
            table, rows, ncalls, d_buf, buf_len, d_offs, nframes, unanswered, d_codes, srcs, counts, d_status);
 }
 
-void mv_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s) {
-    hipLaunchKernelGGL(k_mv_reset_status, dim3(1), dim3(64), 0, s, d_status);
-}
-
-void mv_slots_launch(const MvDesc& d, const MvDesc* dd, const uint32_t* counts, uint64_t ncalls, uint64_t* partial,
-                     uint32_t nb, uint64_t* d_ends, hipStream_t s) {
-    launch(k_mv_slot_reduce, dim3(nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb);
-    launch(k_mv_slot_partials, dim3(d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb, d_ends);
-    launch(k_mv_slot_apply, dim3(nb, d.nslots), dim3(kBlock), 0, s, dd, counts, ncalls, partial, nb);
-}
-
-void mv_copy_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
-                    const uint8_t* d_buf, const uint32_t* srcs, hipStream_t s) {
-    launch(k_mv_copy, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, dd, d_method, table, rows, ncalls, d_buf,
-           srcs);
-}
-
-}  // namespace srpc_impl
-
-using namespace srpc_impl;
-
-extern "C" {
-
-int srpc_frames_mixed_var_scratch_bytes(const srpc_plan* const* plans, int nplans, uint64_t ncalls, uint64_t* out) {
-    if (!plans || !out || nplans <= 0 || nplans > kMixPlans || ncalls >= (1ull << 32)) return SRPC_E_INVALID;
-    MvDesc d{};
-    if (int rc = mv_plans(plans, nplans, 4, &d)) return rc;
-    *out = mv_scratch(d, ncalls).bytes;
-    return SRPC_OK;
-}
-
-int srpc_frames_mixed_var_tile(const srpc_plan* const* plans, int nplans, uint32_t* calls_per_tile,
-                               uint32_t* image_bytes) {
-    if (!plans || !calls_per_tile || !image_bytes || nplans <= 0 || nplans > kMixPlans) return SRPC_E_INVALID;
-    MvDesc d{};
-    if (int rc = mv_plans(plans, nplans, 4, &d)) return rc;
-    *calls_per_tile = d.T;
-    *image_bytes = kMixImage;
-    return SRPC_OK;
-}
-
-int srpc_frames_pack_requests_mixed_var(const srpc_plan* const* req_plans, int nplans, const void* const* const* d_cols,
-                                        const uint64_t* const* const* d_str_offs, const uint64_t* h_first,
-                                        const uint64_t* h_cap, const uint8_t* d_method, const void* d_index,
-                                        uint64_t ncalls, uint8_t* d_out, uint64_t out_cap, uint32_t* d_offs,
-                                        uint64_t* d_total, srpc_unpack_status* d_status, void* d_scratch,
-                                        uint64_t scratch_bytes, void* stream) {
-    const TimedCall timed;
-    // the arguments themselves are checked before any plan is read
-    if (!req_plans || !d_cols || !d_str_offs || !h_cap || !d_index || !d_offs || !d_total || !d_scratch || nplans <= 0 ||
-        nplans > kMixPlans || ncalls >= (1ull << 32) || out_cap >= (1ull << 32) || (ncalls && (!d_method || !d_out)))
-        return SRPC_E_INVALID;
-    static thread_local MvDesc d;
-    d = MvDesc{};
-    if (int rc = mv_plans(req_plans, nplans, 4, &d)) return rc;
-    if (!aligned(d_out, 16) || !aligned(d_index, 8) || !aligned(d_scratch, 8) || !aligned(d_total, 8) ||
-        !aligned(d_offs, 4))
-        return SRPC_E_ALIGN;
-    if (int rc = mv_cols(req_plans, nplans, d_cols, d_str_offs, nullptr, h_first, h_cap, &d)) return rc;
-    const MvScratch sc = mv_scratch(d, ncalls);
-    if (scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
-    auto s = static_cast<hipStream_t>(stream);
-    auto* base = static_cast<uint8_t*>(d_scratch);
-    const auto* dd = reinterpret_cast<const MvDesc*>(base);
-    auto* gsum = reinterpret_cast<uint64_t*>(base + sc.gsum);
-    const auto* table = static_cast<const uint32_t*>(d_index);
+int mv_strings_launch(const MvDesc& d, const MvCarve& c, uint32_t nb, const uint8_t* d_method, const uint32_t* table,
+                      uint64_t ncalls, const uint8_t* d_buf, uint64_t* d_ends, hipStream_t s) {
     const uint64_t rows = mix_rows(ncalls);
-    if (int rc = mv_upload(d, d_scratch, s)) return rc;
-    mv_sizes_launch(dd, d_method, table, rows, ncalls, gsum, out_cap, d_offs, d_total, s);
-    if (ncalls) mv_pack_launch(d, dd, d_method, table, rows, ncalls, gsum, d_out, out_cap, d_offs, d_status, s);
-    return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
-}
-
-int srpc_frames_unpack_replies_mixed_var(const srpc_plan* const* reply_plans, int nplans, const uint8_t* d_buf,
-                                         uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
-                                         const uint8_t* d_method, const void* d_index, uint64_t ncalls,
-                                         uint8_t unanswered_code, void* const* const* d_cols,
-                                         uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap,
-                                         const uint64_t* h_first, const uint64_t* h_cap, uint8_t* d_codes,
-                                         uint64_t* d_ends, srpc_unpack_status* d_status, void* d_scratch,
-                                         uint64_t scratch_bytes, void* stream) {
-    const TimedCall timed;
-    if (!reply_plans || !d_cols || !d_str_offs || !h_str_cap || !h_cap || !d_index || !d_codes || !d_ends || !d_scratch ||
-        nplans <= 0 || nplans > kMixPlans || nframes > ncalls || buf_len >= (1ull << 32) || ncalls >= (1ull << 32) ||
-        (ncalls && !d_method) || (nframes && (!d_buf || !d_offs)))
-        return SRPC_E_INVALID;
-    static thread_local MvDesc d;
-    d = MvDesc{};
-    if (int rc = mv_plans(reply_plans, nplans, 5, &d)) return rc;
-    if (!aligned(d_buf, 16) || !aligned(d_index, 8) || !aligned(d_scratch, 8) || !aligned(d_ends, 8) ||
-        !aligned(d_offs, 4))
-        return SRPC_E_ALIGN;
-    if (int rc = mv_cols(reply_plans, nplans, reinterpret_cast<const void* const* const*>(d_cols),
-                         reinterpret_cast<const uint64_t* const* const*>(d_str_offs), h_str_cap, h_first, h_cap, &d))
-        return rc;
-    const MvScratch sc = mv_scratch(d, ncalls);
-    if (scratch_bytes < sc.bytes) return SRPC_E_CAPACITY;
-    auto s = static_cast<hipStream_t>(stream);
-    auto* base = static_cast<uint8_t*>(d_scratch);
-    const auto* dd = reinterpret_cast<const MvDesc*>(base);
-    auto* counts = reinterpret_cast<uint32_t*>(base + sc.counts);
-    auto* partial = reinterpret_cast<uint64_t*>(base + sc.partial);
-    auto* srcs = reinterpret_cast<uint32_t*>(base + sc.srcs);
-    const auto* table = static_cast<const uint32_t*>(d_index);
-    const uint64_t rows = mix_rows(ncalls);
-    if (d_status) mv_status_reset_launch(d_status, s);
-    if (int rc = mv_upload(d, d_scratch, s)) return rc;
-    if (ncalls)
-        mv_parse_launch(d, dd, d_method, table, rows, ncalls, d_buf, buf_len, d_offs, nframes,
-                        static_cast<uint32_t>(unanswered_code), d_codes, srcs, counts, d_status, s);
     if (d.nslots) {
-        mv_slots_launch(d, dd, counts, ncalls, partial, sc.nb, d_ends, s);
-        if (ncalls) mv_copy_launch(dd, d_method, table, rows, ncalls, d_buf, srcs, s);
+        launch(k_mv_slot_reduce, dim3(nb, d.nslots), dim3(kBlock), 0, s, c.dd, c.counts, ncalls, c.partial, nb);
+        launch(k_mv_slot_partials, dim3(d.nslots), dim3(kBlock), 0, s, c.dd, c.counts, ncalls, c.partial, nb, d_ends);
+        launch(k_mv_slot_apply, dim3(nb, d.nslots), dim3(kBlock), 0, s, c.dd, c.counts, ncalls, c.partial, nb);
+        if (ncalls)
+            launch(k_mv_copy, dim3(static_cast<uint32_t>(rows)), dim3(kBlock), 0, s, c.dd, d_method, table, rows, ncalls,
+                   d_buf, c.srcs);
     }
     return hipGetLastError() == hipSuccess ? SRPC_OK : SRPC_E_HIP;
 }
 
-}  // extern "C"
+}  // namespace srpc_impl

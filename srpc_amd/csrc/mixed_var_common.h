@@ -85,6 +85,18 @@ inline MvScratch mv_scratch(const MvDesc& d, uint64_t ncalls) {
     return s;
 }
 
+// What a call takes out of its scratch.
+struct MvCarve {
+    const MvDesc* dd;
+    uint64_t *gsum, *partial;
+    uint32_t *counts, *srcs;
+    MvCarve(void* p, const MvScratch& sc)
+        : dd(static_cast<const MvDesc*>(p)), gsum(at<uint64_t>(p, sc.gsum)), partial(at<uint64_t>(p, sc.partial)),
+          counts(at<uint32_t>(p, sc.counts)), srcs(at<uint32_t>(p, sc.srcs)) {}
+    template <class T>
+    static T* at(void* p, uint64_t off) { return reinterpret_cast<T*>(static_cast<uint8_t*>(p) + off); }
+};
+
 // Dynamic LDS of a kernel with the image and the templates.
 inline size_t mv_lds(const MvDesc& d) { return kMixImage + 16 + d.tmpl_bytes + 16; }
 
@@ -99,9 +111,7 @@ int mv_plans(const srpc_plan* const* plans, int nplans, uint32_t min_fixed_prefi
 int mv_cols(const srpc_plan* const* plans, int nplans, const void* const* const* d_cols,
             const uint64_t* const* const* d_str_offs, const uint64_t* const* h_str_cap, const uint64_t* h_first,
             const uint64_t* h_cap, MvDesc* d, const uint64_t* h_stride = nullptr);
-// d -> the head of d_scratch, in kMvChunks launches.
-int mv_upload(const MvDesc& d, void* d_scratch, hipStream_t s);
-// Any description (bytes: a multiple of 16) -> the head of d_scratch (16-byte
+// Any description (MvDesc; bytes: a multiple of 16) -> the head of d_scratch (16-byte
 // aligned), kMvChunk bytes per launch, each chunk a by-value kernel argument:
 // no host copy outlives the call (also mixed_aos.hip's tables and fills).
 int mix_upload(const void* src, size_t bytes, void* d_scratch, hipStream_t s);
@@ -119,15 +129,11 @@ void mv_parse_launch(const MvDesc& d, const MvDesc* dd, const uint8_t* d_method,
                      uint64_t ncalls, const uint8_t* d_buf, uint64_t buf_len, const uint32_t* d_offs, uint64_t nframes,
                      uint32_t unanswered, uint8_t* d_codes, uint32_t* srcs, uint32_t* counts, srpc_unpack_status* d_status,
                      hipStream_t s);
-// *d_status = no flag, no bad record.
-void mv_status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
-// The segmented scan over all string slots (three launches whatever K): the
-// lengths the parse left in the offsets arrays become offsets, d_ends[s] each
-// slot's end.  counts: the chunk's calls per plan (device, u32).
-void mv_slots_launch(const MvDesc& d, const MvDesc* dd, const uint32_t* counts, uint64_t ncalls, uint64_t* partial,
-                     uint32_t nb, uint64_t* d_ends, hipStream_t s);
-// The chars of every good call, from buf + srcs[t * ncalls + i] into the columns.
-void mv_copy_launch(const MvDesc* dd, const uint8_t* d_method, const uint32_t* table, uint64_t rows, uint64_t ncalls,
-                    const uint8_t* d_buf, const uint32_t* srcs, hipStream_t s);
+// The tail of every decode.  The segmented scan over all string slots (three
+// launches whatever K): the lengths the parse left in the offsets arrays become
+// offsets, d_ends[s] each slot's end.  Then the chars of every good call, from
+// buf + c.srcs[t * ncalls + i] into the columns.  Returns the call's code.
+int mv_strings_launch(const MvDesc& d, const MvCarve& c, uint32_t nb, const uint8_t* d_method, const uint32_t* table,
+                      uint64_t ncalls, const uint8_t* d_buf, uint64_t* d_ends, hipStream_t s);
 
 }  // namespace srpc_impl

@@ -125,6 +125,10 @@ inline void launch(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t s,
     }
 }
 
+// *d_status = no flag, no bad record (frames.hip's k_reset_status, never timed):
+// every decode's but var.hip's, whose reset also clears the long-record flags.
+int status_reset_launch(srpc_unpack_status* d_status, hipStream_t s);
+
 // ---- LDS byte access with aligned instructions (every file's kernels) ----
 // The k <= 8 low bytes of v at LDS byte d, each byte written once, with the
 // widest naturally aligned stores that fit.

@@ -38,7 +38,8 @@ if not torch.cuda.is_available():  # pragma: no cover - CPU container
 from tests.test_gpu_parity import dev, empty, host, read_status, status_buf  # noqa: E402
 from tests.test_gpu_mixed_aos import place  # noqa: E402
 from tests.test_gpu_mixed_var import (BARE, NO_CODE, STRING, TIMEOUT, Outs, batch, build_index, check_outs,  # noqa: E402
-                                      check_pack, cumcount, dev_leg, is_var, joined, make_leg, model, plans, run_pack)
+                                      check_pack, cumcount, dev_leg, is_var, joined, make_leg, model, plans, run_pack,
+                                      run_unpack)
 
 PREFIX, BOUNDS = _lib.SRPC_STATUS_PREFIX, _lib.SRPC_STATUS_BOUNDS
 INVALID, ALIGN, UNSUPPORTED, CAPACITY = (_lib.SRPC_E_INVALID, _lib.SRPC_E_ALIGN, _lib.SRPC_E_UNSUPPORTED,
@@ -75,7 +76,7 @@ class Legs:
     keeps the first plans only."""
 
     def __init__(self, name, lay, mode, upto=None):
-        P = self.P = plans(SETS[name])
+        P = self.P = plans(SETS.get(name, name))
         self.K = K = upto or P.K
         fixed = [k for k in range(K) if not is_var(P.methods[k][1]) and not is_var(P.methods[k][2])]
         rec = {"cols": [], "recs": fixed, "mixed": fixed[1::2] if name == "calc_text" else fixed[0::2]}[mode]
@@ -211,13 +212,33 @@ def test_pack_50001():
     check_pack(B, run_pack_legs(legs("calc_text", "natural", "mixed"), B))
 
 
-@pytest.mark.parametrize("name", sorted(SETS))
+PAIR = "calc_text2"  # test_gpu_mixed_var.PAIR_SETS: add, multiply and a method with two strings each way
+
+
+def pair_batch():
+    """600 calls of PAIR in random order (more than two tiles of 256, ending
+    inside one), strings of 0..16 bytes: some empty, some across a 16-byte
+    piece of the stream."""
+    B = batch(PAIR, 600, "uniform", "short")
+    assert B.P.K == 3 and all(B.counts) and plans(PAIR).req.tile[0] == plans(PAIR).rep.tile[0] == 256
+    P = plans(PAIR)
+    for leg, frames, pl in ((B.req[2], B.req_frames(), len(P.req_prefix[2])),
+                            (B.rep[2], B.rep_frames(np.zeros(600, np.int64)), len(P.rep_prefix[2]))):
+        lens = np.diff(np.asarray(leg[1][0], np.int64))  # the first string of every element
+        start = joined(frames)[1][:-1][B.method == 2] + 4 + pl + 8  # its chars' stream offset, by call
+        assert (lens == 0).any() and (start // 16 != (start + np.maximum(lens, 1) - 1) // 16).any()
+    return B
+
+
+@pytest.mark.parametrize("name", sorted(SETS) + [PAIR])
 def test_pack_all_columns_equals_mixed_var(name):
-    T = plans(SETS[name]).req.tile[0]
-    for n in (T + 1, 4097):
-        B = batch(SETS[name], n, "uniform", regime(name))
+    """Every output of the two entry points over one all-column batch is the
+    same, byte for byte: the stream, d_offs, d_total and the status words."""
+    T = plans(SETS.get(name, name)).req.tile[0]
+    for n in ((600,) if name == PAIR else (T + 1, 4097)):
+        B = pair_batch() if name == PAIR else batch(SETS[name], n, "uniform", regime(name))
         L = legs(name, "natural", "cols")
-        assert not L.recs
+        assert not L.recs and B.n == n
         got, ref = run_pack_legs(L, B), run_pack(B)
         check_pack(B, got)
         assert got[0] == ref[0] == 0 and got[3:] == ref[3:]
@@ -430,6 +451,34 @@ def test_decode_one_kind_only(mode):
     L = legs("calc_text", "natural", mode)
     _, full, flags, _, _, _ = decode_and_check(L, B, B.rep_frames(np.zeros(B.n, np.int64)))
     assert full.all() and flags == 0 and len(L.recs) == (4 if mode == "recs" else 0)
+
+
+def test_decode_all_columns_equals_mixed_var():
+    """The two entry points over one all-column batch and one reply stream -- a
+    bare error frame, a junk frame, the last 5 calls unanswered -- leave the same
+    bytes everywhere: codes, d_ends, the status words, every column and every
+    offsets array."""
+    B, L = pair_batch(), legs(PAIR, "natural", "cols")
+    rng = np.random.default_rng(600)
+    parts = B.rep_frames(rng.integers(0, 3, B.n))
+    bare, junk, nframes = int(np.flatnonzero(B.method == 0)[40]), int(np.flatnonzero(B.method == 2)[90]), B.n - 5
+    parts[bare] = BARE
+    parts[junk] = struct.pack(">I", 4092) + b"\x07" + rng.bytes(4091)
+    assert not L.recs and 256 < junk < 512 and bare < nframes
+    buf, offs = joined(parts[:nframes])
+    offs = offs[:nframes]
+    O_var, O_legs = Outs(B), LegOuts(L, B)
+    ref = run_unpack(B, O_var, buf, len(buf), offs, nframes)
+    got = run_unpack_legs(L, B, O_legs, buf, len(buf), offs, nframes)
+    wc, full, wflags, wbad = model(buf, len(buf), offs, nframes, B, [0] * 3, O_var.cap)
+    assert ref[0] == got[0] == 0 and (wflags, wbad) == (PREFIX, junk) and not full[bare] and not full[junk]
+    assert np.array_equal(ref[1][:nframes], wc) and (ref[1][nframes:] == TIMEOUT).all() and ref[1][bare] == BARE[4]
+    print(f"codes {np.bincount(ref[1]).tolist()} ends {ref[2].tolist()} status {ref[3:]} / {got[3:]}")
+    assert np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and got[3:] == ref[3:] == (wflags, wbad)
+    for k in range(3):
+        for a, b in zip(O_legs.cols[k] + O_legs.offs[k], O_var.cols[k] + O_var.offs[k]):
+            assert (a is None) == (b is None) and (a is None or torch.equal(a, b)), k
+    check_outs(B, O_var, np.concatenate([full, np.zeros(5, bool)]), ends=ref[2])
 
 
 def test_decode_50001():

@@ -23,6 +23,7 @@ array has h_first[k] elements in front of the batch's and spare ones behind,
 which must keep 0xA5.  The stream is staged as exactly buf_len bytes.  Every
 case asserts that its input holds what it names."""
 import copy
+import ctypes as C
 import functools
 
 import numpy as np
@@ -67,7 +68,7 @@ def side(name, lay, mode, upto=None):
     Legs (L.req over the request plans with the request structs' layouts), the
     plans the call sees (the first `upto`) as `model` and `compare` take them,
     and a fill record per record plan."""
-    L = legs(SETS[name], lay, mode, upto)
+    L = legs(SETS.get(name, name), lay, mode, upto)
     P, K = L.P, L.K
     S = View(L=L, K=K, name=name, methods=P.methods[:K], req_plans=P.req_plans[:K], rep_plans=P.rep_plans[:K],
              req_prefix=P.req_prefix[:K], req_fixed=P.req_fixed[:K], rec=L.rec, recs=L.recs, qlay=L.qlay, slay=L.slay,
@@ -331,14 +332,26 @@ def test_tight_number_slices_share_pieces_with_neighbouring_tiles():
 
 # ---- equivalence with the calls of one kind ------------------------------------------------------
 
-@pytest.mark.parametrize("name", sorted(SETS))
+PAIR = "calc_text2"  # test_gpu_mixed_var.PAIR_SETS: add, multiply and a method with two strings
+
+
+@pytest.mark.parametrize("name", sorted(SETS) + [PAIR])
 def test_all_columns_equals_mixed_var(name):
+    """Every output of the two entry points over one all-column stream is the
+    same, byte for byte.  PAIR: 600 frames in random order (more than two tiles of
+    256, ending inside one), a tenth of them junk, strings of 0..16 bytes."""
     S = side(name, "natural", "cols")
     P = S.L.P
     assert not S.recs and S.K == P.K
-    B = base_batch(name)
-    for n in (S.req.tile[0] + 1, 4097):
+    B = base_batch(name) if name != PAIR else batch(PAIR, 640, "uniform", "short")
+    for n in ((600,) if name == PAIR else (S.req.tile[0] + 1, 4097)):
         frames, intent, src = stream_of(S, B, pattern("uniform", n, S.K, S.req.tile[0], name), 0.1)
+        if name == PAIR:
+            text = intent == 2
+            lens = np.diff(np.asarray(B.req[2][1][0], np.int64))[src[text]]  # the first string of every string frame
+            start = joined(frames)[1][:-1][text] + 4 + len(P.req_prefix[2]) + 8
+            assert S.K == 3 and S.req.tile[0] == 256 and (intent == UNKNOWN).any() and (lens == 0).any()
+            assert (start // 16 != (start + np.maximum(lens, 1) - 1) // 16).any(), "chars across a 16-byte piece"
         got = check(S, B.req, frames, intent, src)
         chars, scap = sized(S, B.req, got["want"], src, got["f0"], got["cap"], [0] * S.K)
         O = Outs(P, got["alloc"], chars)
@@ -693,3 +706,202 @@ def test_refusals_in_order():
         assert (t.cpu().numpy() == 0xA5).all()  # refused: nothing launched
     offs.zero_()
     assert call(nb_given=nb, sb_given=sb) == 0
+
+
+# ---- the refusals of the six string-aware entry points, one table --------------------------------
+
+def error_table():
+    """-> {entry: {wrong call: status}} of srpc_frames_{pack_requests, unpack_replies,
+    unpack_requests}_mixed_{var, legs}.  Every entry starts from one valid call
+    over 40 calls of Calculator + echo (_legs: add and multiply in records) and
+    gets it back wrong in a single way -- a null for each required pointer,
+    nplans 0 and 17, each size at 2^32, d_scratch off by 8 and by 4, the stream
+    off by 8, the scratch or the index one byte short -- and then in two ways
+    at once, which pins the order of the checks."""
+    from tests import test_gpu_mixed_legs as lg
+    from tests import test_gpu_mixed_var as mv
+    lib = _lib.lib()
+    S = side("calc_echo", "natural", "mixed")
+    L, P, K, n = S.L, S.L.P, S.K, 40
+    B = batch("calc_echo", n, "uniform", "short")
+    assert all(B.counts) and S.rec == [False, True, False, True, False]
+    d_method, d_index, _ = mv.build_index(B.method, K)
+    nb = MixedFrames.index_bytes(n, K)
+    short_req = GpuPacker(srpc_amd.NUMBER, b"abc")  # a framed prefix has 4 bytes at least: UNSUPPORTED on either side
+    bad_plans = (C.c_void_p * K)(short_req._h.value, *[p._h.value for p in P.req_plans[1:]])
+
+    def ptr(t, by=0):
+        return t.data_ptr() + by
+
+    def fills(rows):
+        keep = [None if f is None else C.create_string_buffer(bytes(f), len(bytes(f))) for f in rows]
+        return (C.c_void_p * K)(*[None if b is None else C.cast(b, C.c_void_p).value for b in keep]), keep
+
+    def caps(mf, rows):
+        return mf._table(rows, lambda x: 0 if x is None else int(x), C.c_uint64)
+
+    def cases(entry, good, need, sizes, stream_key, legs_form, bad_plans=bad_plans):
+        fn = getattr(lib, "srpc_frames_" + entry)
+
+        def call(**edit):
+            return int(fn(*dict(good, **edit).values()))  # the arguments in the order of include/srpc_gpu.h
+        assert call() == 0, entry
+        optional = ("h_first", "d_status", "stream")
+        out = {f"null {k}": call(**{k: None}) for k, v in good.items()
+               if k not in optional and (k.startswith("d_") or not isinstance(v, int))}
+        out.update({"nplans 0": call(nplans=0), "nplans 17": call(nplans=17)})
+        out.update({f"{k} 2^32": call(**{k: 1 << 32}) for k in sizes})
+        sc = good["d_scratch"]
+        out.update({"d_scratch + 8": call(d_scratch=sc + 8), "d_scratch + 4": call(d_scratch=sc + 4),
+                    f"{stream_key} + 8": call(**{stream_key: good[stream_key] + 8}),
+                    "scratch one byte short": call(scratch_bytes=need - 1)})
+        if "index_bytes" in good:
+            out["index one byte short"] = call(index_bytes=nb - 1)
+        out["null d_index, d_scratch + 4"] = call(d_index=None, d_scratch=sc + 4)
+        out["bad plan, scratch short"] = call(plans=bad_plans, scratch_bytes=need - 1)
+        if legs_form:
+            off = (C.c_void_p * K)(*good["d_recs"])
+            off[1] += 8
+            out["record array + 8, scratch short"] = call(d_recs=off, scratch_bytes=need - 1)
+        table[entry] = out
+
+    table, keep = {}, []
+    # the request pack
+    out, offs, total = empty(1 << 16), empty(4 * (n + 1)), empty(16)
+    for form, mf in (("var", P.req), ("legs", L.req)):
+        legs_form = form == "legs"
+        cols, so, recs = lg.dev_req(L, B) if legs_form else ([mv.dev_leg(x)[0] for x in B.req],
+                                                            [mv.dev_leg(x)[1] for x in B.req], None)
+        c_arr, s_arr, _, h_cap = mf._args(cols, so, None, B.counts)
+        need = P.req.scratch_bytes(n)  # a pack takes no tables: the _legs form needs what the _var form does
+        scratch = empty(mf.scratch_bytes(n) + 64)
+        good = dict(plans=mf._plans, nplans=K, d_cols=c_arr, d_str_offs=s_arr)
+        if legs_form:
+            good.update(d_recs=mf._recs(recs), h_stride=mf._strides, h_leaf_offs=mf._offs)
+        good.update(h_first=None, h_cap=h_cap, d_method=ptr(d_method), d_index=ptr(d_index), ncalls=n, d_out=ptr(out),
+                    out_cap=1 << 15, d_offs=ptr(offs), d_total=ptr(total), d_status=None, d_scratch=ptr(scratch),
+                    scratch_bytes=need, stream=None)
+        keep += [cols, so, recs, scratch, mf._keep]
+        cases(f"pack_requests_mixed_{form}", good, need, ("ncalls", "out_cap"), "d_out", legs_form)
+    # the reply decode
+    buf, o = joined(B.rep_frames(np.zeros(n, np.int64)))
+    d_buf, d_offs = dev(np.frombuffer(buf, np.uint8)), dev(o[:-1].astype(np.uint32))
+    codes, ends = empty(n + 16), empty(8 * 16)
+    bad_plans_rep = (C.c_void_p * K)(short_req._h.value, *[p._h.value for p in P.rep_plans[1:]])
+    for form, mf, O in (("var", P.rep, mv.Outs(B)), ("legs", L.rep, lg.LegOuts(L, B))):
+        legs_form = form == "legs"
+        c_arr, s_arr, _, h_cap = mf._args(O.cols, O.offs, None, O.cap)
+        cap_arr, k3 = caps(mf, O.scap)
+        need = mf.scratch_bytes(n)
+        scratch = empty(need + 64)
+        good = dict(plans=mf._plans, nplans=K, d_buf=ptr(d_buf), buf_len=len(buf), d_offs=ptr(d_offs), nframes=n,
+                    d_method=ptr(d_method), d_index=ptr(d_index), ncalls=n, unanswered=9, d_cols=c_arr, d_str_offs=s_arr,
+                    h_str_cap=cap_arr)
+        if legs_form:
+            h_fill, kf = fills(L.fill)
+            good.update(d_recs=mf._recs(O.recs), h_stride=mf._strides, h_leaf_offs=mf._offs, h_fill=h_fill)
+            keep += [kf]
+        good.update(h_first=None, h_cap=h_cap, d_codes=ptr(codes), d_ends=ptr(ends), d_status=None,
+                    d_scratch=ptr(scratch), scratch_bytes=need, stream=None)
+        keep += [O, scratch, mf._keep, k3]
+        cases(f"unpack_replies_mixed_{form}", good, need, ("ncalls", "nframes", "buf_len"), "d_buf", legs_form,
+              bad_plans_rep)
+    # the request decode
+    frames, intent, src = stream_of(S, B, B.method)
+    raw, o = joined(frames)
+    d_buf, d_offs = dev(np.frombuffer(raw, np.uint8)), dev(o[:-1].astype(np.uint32))
+    cls, counts, index = empty(n + 16), empty(8 * (K + 1)), empty(nb + 16)
+    alloc = [c + FRONT + SPARE for c in B.counts]
+    chars, scap = sized(S, B.req, intent, src, [0] * K, alloc, [0] * K)
+    for form, mf, O in (("var", P.req, Outs(P, alloc, chars)), ("legs", L.req, LegOuts(S, alloc, chars))):
+        legs_form = form == "legs"
+        c_arr, s_arr, _, h_cap = mf._args(O.cols, O.offs, None, alloc)
+        cap_arr, k3 = caps(mf, scap)
+        need = mf.scratch_bytes(n)
+        scratch = empty(need + 64)
+        good = dict(plans=mf._plans, nplans=K, d_buf=ptr(d_buf), buf_len=len(raw), d_offs=ptr(d_offs), nframes=n,
+                    d_cols=c_arr, d_str_offs=s_arr, h_str_cap=cap_arr)
+        if legs_form:
+            h_fill, kf = fills(S.fill)
+            good.update(d_recs=mf._recs(O.recs), h_stride=mf._strides, h_leaf_offs=mf._offs, h_fill=h_fill)
+            keep += [kf]
+        good.update(h_first=None, h_cap=h_cap, d_class=ptr(cls), d_index=ptr(index), index_bytes=nb, d_counts=ptr(counts),
+                    d_ends=ptr(ends), d_status=None, d_scratch=ptr(scratch), scratch_bytes=need, stream=None)
+        keep += [O, scratch, mf._keep, k3]
+        cases(f"unpack_requests_mixed_{form}", good, need, ("nframes", "buf_len"), "d_buf", legs_form)
+    torch.cuda.synchronize()
+    return table
+
+
+# What the parent commit (2987039) answers to error_table()'s calls, case by case; the fold keeps every one.
+# `d_scratch + 8` is where the forms' scratch alignment shows (8 against 16).
+PARENT_STATUS = {
+    "pack_requests_mixed_var": {
+        INVALID: ["null plans", "null d_cols", "null d_str_offs", "null h_cap", "null d_method", "null d_index",
+                  "null d_out", "null d_offs", "null d_total", "null d_scratch", "nplans 0", "nplans 17",
+                  "ncalls 2^32", "out_cap 2^32", "null d_index, d_scratch + 4"],
+        0: ["d_scratch + 8"],
+        ALIGN: ["d_scratch + 4", "d_out + 8"],
+        CAPACITY: ["scratch one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+    "pack_requests_mixed_legs": {
+        INVALID: ["null plans", "null d_cols", "null d_str_offs", "null d_recs", "null h_stride",
+                  "null h_leaf_offs", "null h_cap", "null d_method", "null d_index", "null d_out", "null d_offs",
+                  "null d_total", "null d_scratch", "nplans 0", "nplans 17", "ncalls 2^32", "out_cap 2^32",
+                  "null d_index, d_scratch + 4"],
+        ALIGN: ["d_scratch + 8", "d_scratch + 4", "d_out + 8", "record array + 8, scratch short"],
+        CAPACITY: ["scratch one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+    "unpack_replies_mixed_var": {
+        INVALID: ["null plans", "null d_buf", "null d_offs", "null d_method", "null d_index", "null d_cols",
+                  "null d_str_offs", "null h_str_cap", "null h_cap", "null d_codes", "null d_ends",
+                  "null d_scratch", "nplans 0", "nplans 17", "ncalls 2^32", "nframes 2^32", "buf_len 2^32",
+                  "null d_index, d_scratch + 4"],
+        0: ["d_scratch + 8"],
+        ALIGN: ["d_scratch + 4", "d_buf + 8"],
+        CAPACITY: ["scratch one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+    "unpack_replies_mixed_legs": {
+        INVALID: ["null plans", "null d_buf", "null d_offs", "null d_method", "null d_index", "null d_cols",
+                  "null d_str_offs", "null h_str_cap", "null d_recs", "null h_stride", "null h_leaf_offs",
+                  "null h_fill", "null h_cap", "null d_codes", "null d_ends", "null d_scratch", "nplans 0",
+                  "nplans 17", "ncalls 2^32", "nframes 2^32", "buf_len 2^32", "null d_index, d_scratch + 4"],
+        ALIGN: ["d_scratch + 8", "d_scratch + 4", "d_buf + 8", "record array + 8, scratch short"],
+        CAPACITY: ["scratch one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+    "unpack_requests_mixed_var": {
+        INVALID: ["null plans", "null d_buf", "null d_offs", "null d_cols", "null d_str_offs", "null h_str_cap",
+                  "null h_cap", "null d_class", "null d_index", "null d_counts", "null d_ends", "null d_scratch",
+                  "nplans 0", "nplans 17", "nframes 2^32", "buf_len 2^32", "null d_index, d_scratch + 4"],
+        0: ["d_scratch + 8"],
+        ALIGN: ["d_scratch + 4", "d_buf + 8"],
+        CAPACITY: ["scratch one byte short", "index one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+    "unpack_requests_mixed_legs": {
+        INVALID: ["null plans", "null d_buf", "null d_offs", "null d_cols", "null d_str_offs", "null h_str_cap",
+                  "null d_recs", "null h_stride", "null h_leaf_offs", "null h_fill", "null h_cap", "null d_class",
+                  "null d_index", "null d_counts", "null d_ends", "null d_scratch", "nplans 0", "nplans 17",
+                  "nframes 2^32", "buf_len 2^32", "null d_index, d_scratch + 4"],
+        ALIGN: ["d_scratch + 8", "d_scratch + 4", "d_buf + 8", "record array + 8, scratch short"],
+        CAPACITY: ["scratch one byte short", "index one byte short"],
+        UNSUPPORTED: ["bad plan, scratch short"],
+    },
+}
+
+
+def test_refusals_are_the_parent_commits():
+    """Each of the six entry points answers every wrong call of error_table() as
+    the parent commit did: the single faults, and the double faults that show
+    which check fires first."""
+    got = error_table()
+    want = {e: {c: rc for rc, cs in by.items() for c in cs} for e, by in PARENT_STATUS.items()}
+    assert got.keys() == want.keys()
+    for e in want:
+        diff = {c: (got[e].get(c), rc) for c, rc in want[e].items() if got[e].get(c) != rc}
+        print(e, "differs in (got, parent):", diff)
+        assert not diff and got[e].keys() == want[e].keys(), e

@@ -69,6 +69,11 @@ if not torch.cuda.is_available():  # pragma: no cover - CPU container
     pytest.skip("no GPU", allow_module_level=True)
 
 from tests import scratch_cases as sc  # noqa: E402
+from tests import test_gpu_mixed as gm  # noqa: E402
+from tests import test_gpu_replies as rp  # noqa: E402
+from tests import test_gpu_replies_aos as rpa  # noqa: E402
+from tests import test_gpu_requests_mixed as rq  # noqa: E402
+from tests import test_gpu_requests_mixed_legs as rql  # noqa: E402
 from tests import var_cases as vc  # noqa: E402
 from tests.test_gpu_geometry import _assert_packed, _assert_unpacked, _pack_guarded, _unpack_guarded  # noqa: E402
 from tests.test_gpu_parity import _model_single_string, dev, empty, host, read_status, status_buf  # noqa: E402
@@ -545,3 +550,93 @@ def test_client_frames_on_used_scratch(kind, after):
     assert dirtied(S, need_b, FRESH), f"{pred} left the scratch of {kind} untouched"
     client_call(kind, SHAPES["B"], S)
     assert bool((S[-16:] == FRESH).all())
+
+
+# ---- one d_status for every decode: the reset all of them share ------------------------------------
+
+NONE = 2**64 - 1
+
+
+def _status_site(site):
+    """-> (module whose runner makes the status, run(cut) -> (flags, first bad)):
+    one decode of a small all-full batch.  With `cut` a reply decode's buffer is
+    that many bytes short (the last frame ends past it) and a request decode's
+    last plan has one element too few (its last frame has none): BOUNDS."""
+    n = 300
+    codes = np.zeros(n, np.int64)
+
+    def status_of(got):
+        return got["flags"], got["bad"]
+    if site in ("requests_mixed", "requests_mixed_aos"):
+        L = rqa.lay_for("calc", "natural")
+        intent = rqa.intent_of("calc", "uniform", n, L.T)
+        buf, offs, buf_len, elem = rqa.stream(L.S, intent)
+        counts = [int((intent == k).sum()) for k in range(L.S.K)]
+        assert counts[-1] > 1
+        cap = lambda cut: counts[:-1] + [counts[-1] - bool(cut)]  # noqa: E731
+        if site == "requests_mixed":
+            return rq, lambda cut: status_of(rq.check(L.S, buf, buf_len, offs, intent, elem, cap=cap(cut), alloc=counts))
+        return rqa, lambda cut: status_of(rqa.check(L, buf, buf_len, offs, intent, elem, cap=cap(cut), others=False))
+    if site in ("requests_mixed_var", "requests_mixed_legs"):
+        B = mv.batch("calc_echo", n, "uniform", "short")
+        if site == "requests_mixed_var":
+            frames, intent, src = rqv.stream(B)
+            cap = lambda cut: B.counts[:-1] + [B.counts[-1] - bool(cut)]  # noqa: E731
+            return rqv, lambda cut: status_of(rqv.check(B.P, B.req, frames, intent, src, cap=cap(cut), alloc=B.counts))
+        S = rql.side("calc_echo", "natural", "mixed")
+        frames, intent, src = rql.stream_of(S, B, B.method)
+        full = [(rql.FRONT if S.rec[k] else 0) + B.counts[k] for k in range(S.K)]
+        assert not S.rec[-1]
+        return rql, lambda cut: status_of(rql.check(S, B.req, frames, intent, src, cap=full[:-1] + [full[-1] - bool(cut)]))
+    if site == "mixed_index":
+        return gm, lambda cut: gm.build_index(np.array([0, 1, 9 if cut else 2, 3], np.uint8), 4)[3:]
+    if site in ("replies_mixed", "replies_mixed_aos"):
+        side, method = _aos_reply(dict(SHAPES["B"], n=n))
+        buf, offs = reply_stream(side.R, method, cumcount(method), codes)
+        index = gm.build_index(method, side.R.K)[:2]  # ahead of the decode: the index resets a status of its own
+        if site == "replies_mixed":
+            return gm, lambda cut: gm.run_unpack(side.R, method, buf, len(buf) - cut, offs, n, index=index)[3:]
+        return ma, lambda cut: ma.run_unpack_aos(side, method, buf, len(buf) - cut, offs, n, index=index)[3:5]
+    if site in ("replies_mixed_var", "replies_mixed_legs"):
+        B = mv.batch("calc_echo", n, "uniform", "short")
+        buf, offs = mv.joined(B.rep_frames(codes))
+        if site == "replies_mixed_var":
+            return mv, lambda cut: mv.run_unpack(B, mv.Outs(B), buf, len(buf) - cut, offs[:n], n)[3:]
+        L = lg.legs(*LEGS)
+        return lg, lambda cut: lg.run_unpack_legs(L, B, lg.LegOuts(L, B), buf, len(buf) - cut, offs[:n], n)[3:]
+    if site in ("replies", "replies_aos"):
+        buf, offs = rp.stream("number", n, codes)
+        p = rp.packer("number")
+        if site == "replies":
+            return rp, lambda cut: rp.run(p, buf, len(buf) - cut, offs, n)[3:]
+        return rpa, lambda cut: rpa.run_aos(p, "number", "natural", buf, len(buf) - cut, offs, n)[3:]
+    assert site == "replies_var"
+    lens = rv.make_lens("mix", n, "0-40")
+    buf, offs = rv.stream("mix", n, lens, codes)
+    p = rv.packer("mix", 2)
+
+    def run(cut):
+        args = rv.run(p, buf, len(buf) - cut, offs, n, call=False)
+        p.unpack_replies_var(*args)
+        return read_status(args[-1])
+    return rv, run
+
+
+STATUS_SITES = ["mixed_index", "replies_mixed", "replies_mixed_aos", "replies_mixed_var", "replies_mixed_legs", "replies",
+                "replies_var", "replies_aos", "requests_mixed", "requests_mixed_aos", "requests_mixed_var",
+                "requests_mixed_legs"]
+
+
+@pytest.mark.parametrize("site", STATUS_SITES)
+def test_decode_resets_the_status_a_flagged_decode_left(site, monkeypatch):
+    """Every decode begins by resetting *d_status, all through one launch
+    (status_reset_launch).  A decode that flags a bad frame, then a clean one
+    on the same d_status: flags 0, no bad record.  (The request decodes'
+    runners also fill the status with 0x5A before every call.)"""
+    module, run = _status_site(site)
+    shared = status_buf()
+    monkeypatch.setattr(module, "status_buf", lambda: shared)
+    flags, first = run(2)
+    print(f"{site}: flagged run left flags={flags} first={first}")
+    assert flags == SRPC_STATUS_BOUNDS and first != NONE and read_status(shared) == (flags, first)
+    assert run(0) == (0, NONE) and read_status(shared) == (0, NONE)
